@@ -13,12 +13,17 @@ N=1 workload = BASELINE.json configs[1]: bert-base shapes, batch 32, 1 positive 
 all-gather.  N>1: the same per-GPU batch on every rank (weak scaling; the global negatives grow with N).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--repeats R] [--batch B] [--negatives 7] [--dim 768]
-                  [--driver graph|graph10|eager] [--no-cpu-baseline] [--no-e2e] [--no-rank-roofline]
+                  [--driver graph|graph10|eager] [--dump-outputs DIR]
+                  [--full [--only BLOCKS] [--no-cpu-baseline] [--no-e2e] [--no-rank-roofline] [--no-scale-roofline]]
 --driver eager: one C-ABI call per step; graph: the step's launches captured once into a HIP graph and replayed; graph10: ten
 steps per graph (K steps = K // 10 replays + K % 10 eager steps; hipGraphLaunch's fixed cost amortised, pace independent of the
-host core); auto (default): an untimed probe picks the fastest of the three on this box (all three rates are reported).
-The K-step timed region (barrier + synchronize on both sides) is repeated R times (default 31) and the MEDIAN is
-reported (min / max next to it): K = 20 steps of ~10 us are a 0.2 ms region, one measurement of it is noise.
+host core); auto (default): a short untimed probe picks the fastest of the three on this box.
+A plain run sets up, warms up (W steps), times exactly K steps in one region (barrier + synchronize on both sides), writes the
+outputs of the last step if --dump-outputs is given, and prints the line.  --full adds everything else as before: each of the
+three issue mechanisms measured in full (other_driver), the timed region repeated R times (default 31 with --full: K = 20
+steps of ~10 us are a 0.2 ms region, one measurement of it is noise) with the MEDIAN reported (min / max next to it), the
+per-kernel roofline, the host identity, the extra-information blocks of bench_blocks.py (CPU baselines, operator, at-scale
+rooflines, end to end, ...) and, at N > 1, the transport x form x wire variants.
 Multi-GPU: `python bench.py --gpus N` launches N ranks itself (torch.distributed.run, one rank per GPU over RCCL) when it
 is not already running under a launcher; it refuses to run when fewer than N devices are visible.  Under a launcher
 (WORLD_SIZE set) it is one of the ranks:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N
@@ -57,31 +62,45 @@ def parse():
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--driver", choices=["auto", "graph", "graph10", "eager"], default="auto",
-                    help="issue mechanism behind `value`: auto (default) = the fastest median of the three below, named in config.driver; "
+                    help="issue mechanism behind `value`: auto (default) = the fastest of the three below (a short probe, driver_probe; "
+                         "with --full the best median of full measurements), named in config.driver; "
                          "eager = one C-ABI call per step from a prepared argument block, what a C / C++ binding of include/dprhot.h pays "
                          "(the Python autograd operator pays more on the host: `operator` block) -- within 1 us of host-bound at cfg2, it "
                          "moves between 9.2 and 11.5 us per step with the host core the process landed on; graph / graph10 = HIP graphs "
-                         "of 1 / 10 steps (graph10 is device-bound: 9.3 us on every box).  The mechanisms not chosen are measured too and "
-                         "reported in other_driver")
-    ap.add_argument("--only", default="", help="comma list of the extra blocks to run (default: all but e2e5): operator, torch_gpu, scale, rank, "
-                                               "router, grad_hook, cpu, e2e, model (scaling_model), e2e5 (BASELINE configs[4]: bert-large "
-                                               "towers, seq 512, B 64 -- minutes); `step` = none of them (the contract line alone)")
+                         "of 1 / 10 steps (graph10 is device-bound: 9.3 us on every box).  With --full the mechanisms not chosen are "
+                         "measured too and reported in other_driver")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline too: every issue mechanism in full (other_driver), R = 31 timed regions by "
+                         "default, the per-kernel roofline, the extra-information blocks (--only) and, at N > 1, the variants matrix")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (loss, row_loss, row_lse, dq, dc) as DIR/<name>.npy, "
+                         "float32, at most 64 MB in all (a fixed, seeded sample of an array above its share)")
+    ap.add_argument("--only", default="", help="with --full: comma list of the extra blocks to run (default: all but e2e5): operator, torch_gpu, "
+                                               "scale, rank, router, grad_hook, cpu, e2e, model (scaling_model), e2e5 (BASELINE configs[4]: "
+                                               "bert-large towers, seq 512, B 64 -- minutes); `step` = none of them (the contract line alone)")
     ap.add_argument("--no-scale-roofline", action="store_true", help="skip the extra 8192x8192 per-kernel roofline block")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--repeats", type=int, default=31, help="timed regions of --steps steps each; the median is reported")
-    ap.add_argument("--e2e", action="store_true", help="(default on; kept for compatibility)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of --steps steps each; the median is reported (default 1, with --full 31)")
+    ap.add_argument("--e2e", action="store_true", help="(default on with --full; kept for compatibility)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the short end-to-end (bert-base towers) block")
     ap.add_argument("--no-rank-roofline", action="store_true", help="skip the cfg3-per-rank (128 x 8256 x 768) block")
     a = ap.parse_args()
+    if a.repeats is None:
+        a.repeats = 31 if a.full else 1
     blocks = {"operator", "torch_gpu", "scale", "rank", "router", "grad_hook", "cpu", "e2e", "model", "e2e5"}
     if a.only:
         want = {x.strip() for x in a.only.split(",") if x.strip()}
         unknown = want - blocks - {"step"}
         if unknown:
             ap.error(f"--only: unknown block(s) {sorted(unknown)}")
+        if want & blocks and not a.full:
+            ap.error(f"--only {a.only}: the extra blocks run with --full only")
         a.blocks = want & blocks
-    else:
+    elif a.full:
         a.blocks = set(blocks) - {"e2e5"}
+    else:
+        a.blocks = set()
     for flag, names in (("no_scale_roofline", ("scale",)), ("no_cpu_baseline", ("cpu",)), ("no_e2e", ("e2e",)),
                         ("no_rank_roofline", ("rank", "router"))):
         if getattr(a, flag):
@@ -257,6 +276,14 @@ class HotPathStep:
                 # the loss numerator (one float).  Plain call: enqueued behind the reduce-scatter, nothing on the host waits for it
                 self.D.all_reduce_sum(self.loss_sum, self.group)
 
+    def outputs(self):
+        """What a caller of the step receives from the last step, copied to the host: the loss numerator (N > 1 packed: the one the
+        reduce-scatter delivers in dc[n_ctx][0]), every local row's loss and logsumexp, this rank's q.grad and c.grad."""
+        torch.cuda.synchronize()
+        loss = self.dc[self.n_ctx, :1] if self.dist and self.packed_step else self.loss_sum
+        return {name: t.detach().float().cpu().numpy() for name, t in
+                (("loss", loss), ("row_loss", self.row_loss), ("row_lse", self.row_lse), ("dq", self.dQ), ("dc", self.dc[:self.n_ctx]))}
+
 
 def _host_identity():
     """CPU model, logical CPUs and the cost of one trivial ctypes call into the library (ns): what the eager driver's step time varies with."""
@@ -382,6 +409,37 @@ def timed_loop(run, steps, W, per_call=1, tail=None):
     return time.perf_counter() - t0
 
 
+def probe_drivers(runs, tail, steps):
+    """--driver auto in a plain run: ms per step of each issue mechanism over a short probe (median of 3 regions of up to 200
+    steps), run before the warmup and the timed region; --full measures every mechanism in full instead."""
+    n = max(10, min(steps, 200))
+    ms = {}
+    for name, (fn, per) in runs.items():
+        for _ in range(max(1, 20 // per)):
+            fn()
+        ts = sorted(timed_loop(fn, n, 1, per, tail) for _ in range(3))
+        ms[name] = ts[1] / n * 1e3
+    return ms
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(outs, path):
+    """outs {name: array} -> path/<name>.npy, float32.  An array above its share of DUMP_BYTES is written as a fixed sample of its
+    flattened elements (seeded by the name and the size, so two builds sample the same positions)."""
+    import zlib
+
+    os.makedirs(path, exist_ok=True)
+    cap = (DUMP_BYTES - 4096) // 4 // max(1, len(outs))  # (4096: the .npy headers)
+    for name, x in outs.items():
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if x.size > cap:
+            rng = np.random.default_rng([zlib.crc32(name.encode()), x.size])
+            x = x.reshape(-1)[np.unique(rng.integers(0, x.size, size=cap))]
+        np.save(os.path.join(path, name + ".npy"), x)
+
+
 def core_line(a, W, B, K, d, T, hp, els, driver, collectives, backend, DM):
     """The contract's keys from the R timed regions (median); roofline / kernels / extras are added by the caller."""
     es = sorted(els)
@@ -400,7 +458,7 @@ def core_line(a, W, B, K, d, T, hp, els, driver, collectives, backend, DM):
                    "ms_per_step_min": round(es[0] / a.steps * 1e3, 5), "ms_per_step_max": round(es[-1] / a.steps * 1e3, 5),
                    # the eager loop is host-paced (two launches + one ctypes call per step against 8.7 us of kernels): which host
                    # this lease ran on, and how fast it makes a foreign call -- other_driver.graph10 is the number that does not move
-                   "host": _host_identity()},
+                   "host": _host_identity() if a.full else None},
         "rccl_ranks": W if (DM and backend == "nccl") else 0,
         "rccl_version": ".".join(str(x) for x in torch.cuda.nccl.version()) if hasattr(torch.cuda, "nccl") else None,
     }
@@ -432,7 +490,8 @@ def main():
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(a)
     sys.modules.setdefault("bench", sys.modules[__name__])  # bench_blocks.py imports the RUNNING bench.py under this name, not a second copy
-    import bench_blocks as BB  # the extra-information blocks (never `value`)
+    if a.full:
+        import bench_blocks as BB  # the extra-information blocks (never `value`)
     W = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -476,6 +535,7 @@ def main():
         return ts
 
     comm, torch_coll, variants, collectives_name = None, None, None, "none"
+    outs, driver_probe = None, None  # the last timed step's outputs (--dump-outputs); the plain run's driver probe (N = 1)
     if DM:
         # N > 1.  `value` is the step in the configuration the PRODUCT defaults to: torch.distributed's own RCCL communicator (the C ABI
         # communicator is opt-in: DPRHOT_DIRECT_RCCL=1) and the FORM of the path's two collectives that dist.choose_path_collectives
@@ -517,7 +577,9 @@ def main():
         state["line"] = core_line(a, W, B, K, d, T, hp, els, "eager", collectives_name, backend, DM) if rank == 0 else None
         if rank == 0 and topo == "allpairs":
             state["line"]["rccl_collective_form"] = {"ms_per_step": round(torch_coll / a.steps * 1e3, 5), "value": round(W * B * a.steps / torch_coll, 1)}
-        if not os.environ.get("DPRHOT_NO_VARIANTS"):
+        if a.dump_outputs and rank == 0:
+            outs = hp.outputs()  # (before the variants: their bf16 dC wire changes c.grad)
+        if a.full and not os.environ.get("DPRHOT_NO_VARIANTS"):
             variants = BB.variants_block(a, W, rank, dev, backend, B, K, d, T, hp, measure, state)
         D.configure(None, None)
         driver = "eager"  # the collectives stay outside graphs
@@ -530,19 +592,44 @@ def main():
         # training iteration gets, and the only one of the three whose pace does not depend on the host core the process landed on:
         # the eager loop is within 1 us of host-bound and flips between 9.9 and 11.5 us per step from run to run)
         runs = {"eager": (hp.c_step, 1)}  # (hp.step without its Python frames: no collectives at N = 1)
-        runs["graph"] = (capture(hp, hp.step), 1)
-        runs["graph10"] = (capture(hp, hp.step, 10), 10)
-        # every mechanism gets the full measurement (W warmup steps, R regions of exactly K steps).  `value` is the one --driver
-        # names: auto by default = the best median of the three (round 6: the eager loop's pace is the host core's -- 9.2 us on one
-        # box, 11.1 on the next, same kernels -- and the 10-step graph's is the device's); the others ride in `other_driver`.
-        measured = {name: measure(fn, per, hp.step) for name, (fn, per) in runs.items()}
-        med = {name: sorted(v)[len(v) // 2] for name, v in measured.items()}
-        if driver == "auto":
-            driver = min(med, key=med.get)
-        els = measured[driver]
+        if a.full or driver in ("auto", "graph"):
+            runs["graph"] = (capture(hp, hp.step), 1)
+        if a.full or driver in ("auto", "graph10"):
+            runs["graph10"] = (capture(hp, hp.step, 10), 10)
+        if a.full:
+            # every mechanism gets the full measurement (W warmup steps, R regions of exactly K steps).  `value` is the one --driver
+            # names: auto by default = the best median of the three (round 6: the eager loop's pace is the host core's -- 9.2 us on one
+            # box, 11.1 on the next, same kernels -- and the 10-step graph's is the device's); the others ride in `other_driver`.
+            measured, snaps = {}, {}
+            for name, (fn, per) in runs.items():
+                measured[name] = measure(fn, per, hp.step)
+                if a.dump_outputs:
+                    snaps[name] = hp.outputs()
+            med = {name: sorted(v)[len(v) // 2] for name, v in measured.items()}
+            if driver == "auto":
+                driver = min(med, key=med.get)
+            els = measured[driver]
+            outs = snaps.get(driver)
+        else:
+            # a plain run times the one mechanism `value` names; auto: the fastest over a short probe (reported in driver_probe)
+            if driver == "auto":
+                driver_probe = probe_drivers(runs, hp.step, a.steps)
+                driver = min(driver_probe, key=driver_probe.get)
+            fn, per = runs[driver]
+            els = measure(fn, per, hp.step)
+            if a.dump_outputs:
+                outs = hp.outputs()
 
     out = None
-    if rank == 0:
+    if rank == 0 and outs is not None:
+        dump_outputs(outs, a.dump_outputs)
+    if rank == 0 and not a.full:
+        out = core_line(a, W, B, K, d, T, hp, els, driver, collectives_name, backend, DM)
+        if driver_probe is not None:
+            out["driver_probe"] = {name: {"ms_per_step": round(v, 5)} for name, v in driver_probe.items()}
+        if DM and state["line"] is not None and "rccl_collective_form" in state["line"]:
+            out["rccl_collective_form"] = state["line"]["rccl_collective_form"]
+    elif rank == 0:
         bn, bd, nd = float(B) * hp.Nc, float(B) * d, float(hp.Nc) * d
         sim_bytes = (4 + 2) * bd + (6 * nd if not DM else 2 * nd) + 4 * bn
         if hp.small:

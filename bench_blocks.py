@@ -357,7 +357,7 @@ def scaling_model(dev, d=768, B=128, K=8):
     host = None
     try:
         env = dict(os.environ, DPRHOT_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29771")
-        base = [sys.executable, os.path.join(ROOT, "bench.py"), "--only", "step", "--steps", "100", "--repeats", "5", "--batch", str(B), "--negatives", str(K - 1)]
+        base = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--only", "step", "--steps", "100", "--repeats", "5", "--batch", str(B), "--negatives", str(K - 1)]
         forced = json.loads(subprocess.run(base, env=env, capture_output=True, text=True, timeout=240).stdout.strip().splitlines()[-1])
         env.pop("DPRHOT_FORCE_DIST")
         plain = json.loads(subprocess.run(base, env=env, capture_output=True, text=True, timeout=240).stdout.strip().splitlines()[-1])

@@ -6,8 +6,8 @@ not importable (not installed in the build image, no network).  With hydra prese
                                        as configs (main.py:25 instantiates the task that way)
   compose(conf_dir, name, overrides)   defaults lists (incl. `override grp: opt`), `# @package _group_` /
                                        `_global_` headers, `${a.b}` interpolation, `k=v` / `+k=v` overrides
-It loads the reference's own conf/ tree unchanged (tests/test_task_dropin.py does so when /root/reference is
-mounted) as well as the small tree under dpr_scale_amd/conf.
+It loads conf trees of the reference's shape (tests/test_task_dropin.py composes one stored under
+tests/golden/conf_tree) as well as the small tree under dpr_scale_amd/conf.
 """
 import copy
 import importlib

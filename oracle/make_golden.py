@@ -19,6 +19,11 @@ Cases (SURVEY.md section 8 notation, BASELINE.json configs):
   router_*                    CITADEL router loss (citadel_task.py:137-153, :240-262) at d = 30522, both sim_score modes
   router_gather_w2            citadel_task.py:97-135 distributed_gather on 2 real gloo ranks, ragged token lengths
   search_ref                  run_retrieval_pytorch.py:141-176 search_index (fp16 einsum + topk, the batched loop and its tail)
+  live_step / live_autocast / live_router
+                              training_step / sim_score on tests/test_oracle_vs_reference.py's inputs, the step under bf16
+                              autocast, citadel_task.py router loss / sim_score at d = 1000 (offsets from the oracle)
+  task_step_ref               DenseRetrieverTask.training_step on the tiny_cpu.yaml task's encoders: loss, encoder outputs and
+                              the gradient into them (tests/test_task_dropin.py)
 """
 import json
 import os
@@ -192,8 +197,121 @@ def search_fixture():
          scores=scores.numpy().astype(np.float32), ids=ids.numpy().astype(np.int64))
 
 
+LIVE_STEP_CASES = [(4, 2, 128, "P", False, 1.0), (16, 4, 256, "U", True, 0.5), (32, 8, 768, "U", True, 0.05)]
+LIVE_ROUTER_CASES = [(True, 0.0), (False, 0.0), (True, 0.3), (False, 1.0)]
+
+
+def live_step_key(B, K, d, distn, ragged, T):
+    return f"B{B}_K{K}_d{d}_{distn}{'r' if ragged else ''}_T{T:g}"
+
+
+def live_reference_fixtures():
+    """What tests/test_oracle_vs_reference.py compares against, one fixture per test: the reference's training_step / sim_score
+    on the inputs those tests draw (live_step: synth_embeddings(900 + B, ...)), the same step in fp32 and under
+    torch.autocast(bf16) (live_autocast: seed 77), citadel_task.py's router loss / sim_score on synth_router(41, 6, 4, 1000)
+    (live_router).  Every array is stored losslessly as offsets from the oracle the test recomputes (oracle/fixture_codec.py):
+    the fp64 numpy / torch oracle, and for the autocast gradients the fp32 reference's, on the bf16 grid."""
+    from oracle import inbatch_oracle as O
+    from oracle import router_oracle as R
+    from oracle.fixture_codec import encode
+
+    t = torch.from_numpy
+    src = "; inputs = oracle.inbatch_oracle.synth_embeddings; stored as offsets from the oracle (oracle/fixture_codec.py)"
+    if wanted("live_step"):
+        arrays = {}
+        for B, K, d, distn, ragged, T in LIVE_STEP_CASES:
+            q, c, y, m = synth_embeddings(900 + B, B, K, d, distn, ragged)
+            loss, dq, dc = ref_shim.reference_training_step(t(q), t(c), t(y), t(m), temperature=T)
+            S = ref_shim.reference_sim_score(t(q), t(c), t(m)).numpy()
+            o = O.training_step_global(q, c, y, m, T)
+            k = live_step_key(B, K, d, distn, ragged, T)
+            for name, x, base in (("loss", loss.item(), o["loss"]), ("dq", dq.numpy(), o["dQ"]), ("dc", dc.numpy(), o["dC"]),
+                                  ("S", S, O.sim_score(q, c, m))):
+                arrays.update(encode(f"{k}_{name}", x, base))
+        save("live_step", dict(case="live_step", cases=LIVE_STEP_CASES,
+                               source="reference dpr_task.py training_step / sim_score, fp32 CPU" + src), **arrays)
+    if wanted("live_autocast"):
+        q, c, y, m = synth_embeddings(77, 32, 8, 768, "U", True)
+        loss32, dq32, dc32 = ref_shim.reference_training_step(t(q), t(c), t(y), t(m), temperature=1.0)
+        with torch.autocast("cpu", dtype=torch.bfloat16):
+            loss16, dq16, dc16 = ref_shim.reference_training_step(t(q), t(c), t(y), t(m), temperature=1.0)
+        o = O.training_step_global(q, c, y, m, 1.0)
+        arrays = {}
+        for name, x32, x16, base in (("loss", loss32.item(), loss16.float().item(), o["loss"]), ("dq", dq32.numpy(), dq16.float().numpy(), o["dQ"]),
+                                     ("dc", dc32.numpy(), dc16.float().numpy(), o["dC"])):
+            arrays.update(encode(name + "32", x32, base))
+            arrays.update(encode(name + "16", x16, x32, shift=0 if name == "loss" else 16))  # (bf16 gradients: on the bf16 grid)
+        save("live_autocast", dict(case="live_autocast", seed=77, B=32, K=8, d=768, dist="U", ragged=True, T=1.0,
+                                   source="reference dpr_task.py training_step in fp32 and under torch.autocast(cpu, bfloat16)" + src),
+             **arrays)
+    if wanted("live_router"):
+        q, c, mask, pos, teacher = R.synth_router(41, 6, 4, 1000)
+        arrays = {}
+        for in_batch, coef in LIVE_ROUTER_CASES:
+            loss, dq, dc, _ = ref_shim.reference_router_loss(t(q), t(c), t(mask), t(pos), t(teacher), in_batch, coef, 2.0)
+            base = R.router_step(q, c, mask, pos, teacher, in_batch, coef, 2.0)
+            k = f"router_{int(in_batch)}_{coef:g}"
+            for name, x, b in zip(("loss", "dq", "dc"), (loss.item(), dq.numpy(), dc.numpy()), base):
+                arrays.update(encode(f"{k}_{name}", x, b))
+        for pairwise in (False, True):
+            S = ref_shim.reference_citadel_sim_score(t(q), t(c), t(mask), pairwise).numpy()
+            arrays.update(encode(f"router_S_{int(pairwise)}", S, R.sim_score(t(q).double(), t(c).double(), t(mask), pairwise).numpy()))
+        save("live_router", dict(case="live_router", cases=LIVE_ROUTER_CASES, tau=2.0,
+                                 source="reference citadel_task.py router_loss / sim_score, fp32 CPU; inputs = "
+                                        "oracle.router_oracle.synth_router; stored as offsets from the oracle (oracle/fixture_codec.py)"),
+             **arrays)
+
+
+def task_step_fixture():
+    """What tests/test_task_dropin.py compares against: the REFERENCE DenseRetrieverTask.training_step on the tiny_cpu.yaml task's
+    own encoders (torch.manual_seed(1), ragged batch, T = 16), both in_batch_negatives branches -- its loss, the encoder outputs it
+    saw and the gradient it sent back into them (the parameter gradients follow from those through the same encoders)."""
+    if not wanted("task_step_ref"):
+        return
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from _oracle_kernels import OracleKernels
+    from dpr_scale_amd import hydra_compat, lightning_compat
+
+    conf = os.path.join(ROOT, "dpr_scale_amd", "conf")
+    arrays, tasks = {}, []
+    for in_batch in (True, False):  # (both set up before the shim's hydra stub is installed)
+        cfg = hydra_compat.compose(conf, "tiny_cpu.yaml", ["datamodule.ragged=true", "task.softmax_temperature=16.0"])
+        torch.manual_seed(1)
+        mine = hydra_compat.instantiate(cfg.task, _recursive_=False)
+        mine.kernels = mine.loss.kernels = OracleKernels()
+        mine.in_batch_negatives = in_batch
+        mine.trainer = lightning_compat.Trainer(device="cpu")
+        mine.setup("fit")
+        tasks.append((in_batch, mine, hydra_compat.instantiate(cfg.datamodule).train_dataloader()[0]))
+    for in_batch, mine, batch in tasks:
+        ref = ref_shim.make_reference_task(False, temperature=16.0, in_batch_negatives=in_batch)
+        ref.query_encoder, ref.context_encoder = mine.query_encoder, mine.context_encoder
+        mine.eval(), ref.eval()
+        seen = {}
+        fwd = ref.forward
+
+        def keep(query_ids, contexts_ids):
+            q, c = fwd(query_ids, contexts_ids)
+            q.retain_grad(), c.retain_grad()
+            seen["q"], seen["c"] = q, c
+            return q, c
+
+        ref.forward = keep
+        loss = ref.training_step(batch, 0)
+        loss.backward()
+        k = f"in_batch_{int(in_batch)}"
+        arrays.update({k + "_loss": np.float32(loss.item()), k + "_q": seen["q"].detach().numpy(), k + "_c": seen["c"].detach().numpy(),
+                       k + "_dq": seen["q"].grad.numpy(), k + "_dc": seen["c"].grad.numpy()})
+    save("task_step_ref", dict(case="task_step_ref", config="dpr_scale_amd/conf/tiny_cpu.yaml", overrides=["datamodule.ragged=true",
+                               "task.softmax_temperature=16.0"], seed=1,
+                               source="reference dpr_task.py DenseRetrieverTask.training_step on the product task's encoders, CPU"),
+         **arrays)
+
+
 def main():
     assert ref_shim.reference_available(), "needs /root/reference"
+    task_step_fixture()
+    live_reference_fixtures()
     router_fixtures()
     search_fixture()
     torch.manual_seed(0)

@@ -2,8 +2,8 @@
 
 This module exists only in the build container (it needs ``/root/reference``); it does not travel to
 the GPU box and nothing in the product path may import it.  It is used by ``oracle/make_golden.py``
-to generate the fixtures under ``tests/golden/`` and by ``tests/test_oracle_vs_reference.py`` (skipped
-when ``/root/reference`` is absent) to pin ``oracle/inbatch_oracle.py`` against the reference.
+to generate the fixtures under ``tests/golden/`` -- among them ``live_step.npz`` and its two siblings, which
+``tests/test_oracle_vs_reference.py`` pins ``oracle/inbatch_oracle.py`` to.
 
 What it does: ``/root/reference/dpr_scale/task/dpr_task.py`` imports ``hydra``, ``pytorch_lightning`` and
 ``pytorch_lightning.strategies`` at module top (dpr_task.py:4,8,9); none is installed here.  Three stub

@@ -6,13 +6,13 @@
 #   tests            pytest -m gpu                                  -> gpurun_out/pytest_gpu.txt
 #   tests:<expr>     pytest -m gpu -k <expr>
 #   smoke            __graft_entry__.smoke()
-#   bench            python bench.py (the driver's command)         -> gpurun_out/bench_n1.json
-#   bench:<args>     python bench.py <args> (use + for spaces)
+#   bench            python bench.py --full (the complete line)      -> $OUT/bench_n1.json
+#   bench:<args>     python bench.py --full <args> (use + for spaces)
 #   prof-bench       rocprofv3 kernel trace + FETCH_SIZE / WRITE_SIZE passes of the cfg2 bench loop -> gpurun_out/prof_summary/
 #   prof-rank        the same three passes of the cfg3-per-rank step (scripts/bench_rankstep.py)   -> gpurun_out/prof_rank_summary/
-#   prof-router      the same three passes of the router-width step (bench.py --only router)               -> gpurun_out/prof_router_summary/
+#   prof-router      the same three passes of the router-width step (bench.py --full --only router)        -> $OUT/prof_router_summary/
 #   prof-8192        the same three passes of the 8192^2 x 768 launches (bench_sweep.py)                   -> gpurun_out/prof_big_summary/
-#   prof-op          kernel trace of the autograd operator loop (bench.py --only operator)        -> gpurun_out/prof_op_summary/
+#   prof-op          kernel trace of the autograd operator loop (bench.py --full --only operator) -> $OUT/prof_op_summary/
 #   pmc8192          SQ counters (MFMA busy, LDS conflicts, waits) of the 8192^2 x 768 launches    -> gpurun_out/pmc_8192.txt
 #   pmc-engine       SQ counters + HBM bytes + durations of scripts/pmc_engine128.py (library GEMM, the 128 x 128 engine's dQ / dC, torch's) -> gpurun_out/pmc_engine128.txt
 #   sweep / eval     bench_sweep.py / bench_eval.py                 -> gpurun_out/sweep.jsonl, eval_search.jsonl
@@ -41,12 +41,12 @@ for task in "$@"; do
   case "$task" in
     tests)  ( timeout 1500 python -m pytest tests -m gpu -x -q --timeout 420 ${arg:+-k "$arg"} ) > $OUT/pytest_gpu.txt 2>&1; echo "pytest rc=$?"; tail -n 15 $OUT/pytest_gpu.txt ;;
     smoke)  timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -n 3 ;;
-    bench)  ( timeout 1500 python bench.py $arg ) > $OUT/bench_n1.log 2>&1; echo "bench rc=$?"; tail -n 1 $OUT/bench_n1.log > $OUT/bench_n1.json; cut -c1-1500 $OUT/bench_n1.json ;;
-    prof-bench) three_passes bench r06_bench_cfg2 python $GRAFT_REPO_ROOT/bench.py --steps 500 --warmup 50 --repeats 3 --only step --driver eager ;;
+    bench)  ( timeout 1500 python bench.py --full $arg ) > $OUT/bench_n1.log 2>&1; echo "bench rc=$?"; tail -n 1 $OUT/bench_n1.log > $OUT/bench_n1.json; cut -c1-1500 $OUT/bench_n1.json ;;
+    prof-bench) three_passes bench r06_bench_cfg2 python $PWD/bench.py --full --steps 500 --warmup 50 --repeats 3 --only step --driver eager ;;
     prof-rank)  three_passes rank r06_cfg3rank python $GRAFT_REPO_ROOT/scripts/bench_rankstep.py --shapes ${arg:-128:8:768:8} --eager --reps 50 ;;
-    prof-router) three_passes router r06_router python $GRAFT_REPO_ROOT/bench.py --only router ;;
+    prof-router) three_passes router r06_router python $PWD/bench.py --full --only router ;;
     prof-8192)  three_passes big r06_8192 python $GRAFT_REPO_ROOT/bench_sweep.py --shapes 8192x8192 ;;
-    prof-op)    three_passes op r06_operator python $GRAFT_REPO_ROOT/bench.py --steps 200 --warmup 20 --repeats 3 --only operator ;;
+    prof-op)    three_passes op r06_operator python $PWD/bench.py --full --steps 200 --warmup 20 --repeats 3 --only operator ;;
     pmc8192)
       i=0
       for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAIT_ANY" "SQ_LDS_BANK_CONFLICT SQ_INSTS_LDS SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR"; do
@@ -69,7 +69,7 @@ for task in "$@"; do
     eval)   ( timeout 900 python bench_eval.py $arg ) > $OUT/eval_search.jsonl 2> $OUT/eval.err; echo "eval rc=$?"; cut -c1-400 $OUT/eval_search.jsonl ;;
     rank)   ( timeout 600 python scripts/bench_rankstep.py $arg ) > $OUT/rankstep.jsonl 2> $OUT/rankstep.err; echo "rank rc=$?"; cat $OUT/rankstep.jsonl ;;
     dist1)
-      Q="--only step --steps 100 --repeats 5"
+      Q="--full --only step --steps 100 --repeats 5"
       ( DPRHOT_FORCE_DIST=1 timeout 300 python bench.py $Q ) > $OUT/bench_force_dist.log 2>&1; echo "one-rank RCCL world rc=$?"; tail -n 1 $OUT/bench_force_dist.log | cut -c1-700
       ( DPRHOT_DIST_BACKEND=gloo DPRHOT_SAME_DEVICE=1 timeout 600 python bench.py --gpus 2 $Q ) > $OUT/bench_w2_gloo.log 2>&1; echo "2 ranks / 1 device / gloo rc=$?"; tail -n 1 $OUT/bench_w2_gloo.log | cut -c1-700 ;;
     fuzz)   ( timeout 900 python scripts/fuzz_step.py --seed 0 ) > $OUT/fuzz_step.txt 2>&1; echo "fuzz_step rc=$?"; tail -n 3 $OUT/fuzz_step.txt

@@ -1,6 +1,6 @@
 """Drop-in boundary: DenseRetrieverTask mirrors the reference class -- constructor kwargs,
 hooks, metric names, checkpoint layout, Hydra config schema -- and its training_step reproduces the REFERENCE
-training_step on the same encoders and batch (reference run live when /root/reference is mounted).
+training_step on the same encoders and batch (tests/golden/task_step_ref.npz, written by the reference).
 
 CPU tests inject the numpy stand-in for the HIP kernels (the product default refuses CPU tensors); the `gpu`
 tests run BASELINE.json configs[0] (tiny BERT, batch 4, 1 pos + 1 hard negative) through libdprhot.so.
@@ -21,7 +21,6 @@ from dpr_scale_amd import hydra_compat, lightning_compat  # noqa: E402
 from dpr_scale_amd.task.dpr_task import DenseRetrieverTask  # noqa: E402
 
 CONF = os.path.join(ROOT, "dpr_scale_amd", "conf")
-REF = "/root/reference"
 
 
 def make_task(cfg, kernels):
@@ -86,13 +85,17 @@ def test_config_groups_defaults_overrides_interpolation(tmp_path):
     assert dict(obj) == {"a": 1}
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted")
-def test_reference_conf_tree_loads_unchanged():
-    cfg = hydra_compat.compose(os.path.join(REF, "dpr_scale", "conf"), "msmarco_baseline.yaml")
-    assert cfg.task._target_ == "dpr_scale.task.dpr_task.DenseRetrieverTask"
-    assert cfg.task.transform.model_path == cfg.task.model.model_path == "bert-base-uncased"  # ${} interpolation
-    assert (cfg.datamodule.batch_size, cfg.datamodule.num_negative, cfg.trainer.strategy) == (8, 7, "ddp")
-    assert cfg.task.optim.lr == 3e-5 and cfg.task.shared_model is False
+def test_reference_shaped_conf_tree_composes():
+    """A recipe on a conf tree of the reference's shape (tests/golden/conf_tree): root defaults from the schema list, the
+    recipe's `override` group choices, nested groups, `${}` interpolation, the recipe's keys over the groups', `4e-5` floats."""
+    cfg = hydra_compat.compose(os.path.join(ROOT, "tests", "golden", "conf_tree"), "recipe.yaml")
+    assert cfg.task._target_ == "dpr_scale_amd.task.dpr_task.DenseRetrieverTask" and cfg.task.softmax_temperature == 1.0
+    assert cfg.task.transform.model_path == cfg.task.model.model_path == "tiny-encoder"  # ${} interpolation
+    assert (cfg.datamodule.batch_size, cfg.datamodule.num_negative, cfg.trainer.strategy) == (16, 3, "ddp")
+    assert (cfg.trainer.gpus, cfg.trainer.max_epochs) == (0, 2)  # override trainer: cpu
+    assert cfg.task.optim._target_ == "torch.optim.SGD" and cfg.task.optim.momentum == 0.9  # override task/optim: sgd
+    assert cfg.task.optim.lr == 4e-5 and isinstance(cfg.task.optim.lr, float) and cfg.task.shared_model is False
+    assert cfg.checkpoint_callback.monitor == "valid_loss" and cfg.test_only is False
 
 
 def test_cfg1_plumbing_run_cpu(tmp_path):
@@ -116,12 +119,14 @@ def test_cfg1_plumbing_run_cpu(tmp_path):
         assert k1 == k2 and torch.equal(v1.cpu(), v2)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not mounted")
 @pytest.mark.parametrize("in_batch", [True, False])
 def test_training_step_equals_reference_training_step(in_batch):
-    """Same encoders, same batch: loss and every parameter gradient vs the reference class, run verbatim."""
+    """Same encoders, same batch: loss and every parameter gradient vs the reference class.  tests/golden/task_step_ref.npz holds
+    what the reference's training_step did with these very encoders (oracle/make_golden.py): its loss, the encoder outputs it saw
+    and the gradient it returned into them; the reference's parameter gradients are that gradient carried back through the same
+    encoders."""
     from _oracle_kernels import OracleKernels
-    from oracle import ref_shim
+    from conftest import load_golden
 
     cfg = hydra_compat.compose(CONF, "tiny_cpu.yaml", ["datamodule.ragged=true", "task.softmax_temperature=16.0"])
     torch.manual_seed(1)
@@ -130,12 +135,15 @@ def test_training_step_equals_reference_training_step(in_batch):
     mine.trainer = lightning_compat.Trainer(device="cpu")
     mine.setup("fit")
     batch = hydra_compat.instantiate(cfg.datamodule).train_dataloader()[0]
-    ref = ref_shim.make_reference_task(False, temperature=16.0, in_batch_negatives=in_batch)
-    ref.query_encoder, ref.context_encoder = mine.query_encoder, mine.context_encoder  # the very same modules
-    mine.eval(), ref.eval()  # (T=16 keeps the softmax of unit-variance LayerNorm outputs out of saturation)
-    l_ref = ref.training_step(batch, 0)
-    l_ref.backward()
-    g_ref = {n: p.grad.clone() for n, p in mine.named_parameters() if p.grad is not None}
+    ref = {k: torch.from_numpy(v) for k, v in load_golden("task_step_ref")[1].items() if k.startswith(f"in_batch_{int(in_batch)}_")}
+    ref = {k.split("_")[-1]: v for k, v in ref.items()}
+    mine.eval()  # (T=16 keeps the softmax of unit-variance LayerNorm outputs out of saturation)
+    q, c = mine.forward(batch["query_ids"], batch["contexts_ids"])
+    assert torch.allclose(q, ref["q"], rtol=1e-4, atol=1e-5) and torch.allclose(c, ref["c"], rtol=1e-4, atol=1e-5)  # the same encoders
+    l_ref = ref["loss"]
+    params = [p for _, p in mine.named_parameters()]
+    grads = torch.autograd.grad((q, c), params, (ref["dq"], ref["dc"]), allow_unused=True)
+    g_ref = {n: g for (n, _), g in zip(mine.named_parameters(), grads) if g is not None}
     mine.zero_grad()
     l_mine = mine.training_step(batch, 0)
     l_mine.backward()
