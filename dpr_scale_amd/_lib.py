@@ -100,6 +100,12 @@ SIGNATURES = {
     "dprhot_fwd_no_logits": (c_int, [c_int, c_int, c_int, POINTER(c_int)]),
     "dprhot_fwd_one_pass": (c_int, [c_int, c_int, c_int, POINTER(c_int)]),
     "dprhot_reducescatter_allpairs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int, c_int, c_void_p]),
+    "dprhot_maxsim_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "dprhot_maxsim_fwd": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dprhot_maxsim_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p]),
     "dprhot_inbatch_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_size_t, c_void_p]),
 }
@@ -180,6 +186,12 @@ def fwd_one_pass(B: int, Nc: int, d: int) -> int:
     out = c_int(0)
     check(lib.dprhot_fwd_one_pass(B, Nc, d, ctypes.byref(out)), "dprhot_fwd_one_pass")
     return int(out.value)
+
+
+def maxsim_workspace_bytes(Nq: int, LQ: int, KQ: int, Ny: int, has_weights: bool) -> int:
+    out = c_size_t(0)
+    check(lib.dprhot_maxsim_workspace_bytes(Nq, LQ, KQ, Ny, int(bool(has_weights)), ctypes.byref(out)), "dprhot_maxsim_workspace_bytes")
+    return out.value
 
 
 def workspace_bytes(B: int, Nc: int, d: int) -> int:

@@ -30,6 +30,7 @@
 #include "gradcomm.h"
 #include "wide.h"
 #include "wideselect.h"
+#include "maxsim.h"
 
 using namespace dprhot;
 
@@ -973,6 +974,80 @@ int sk_step(const float* q, const dprhot_bf16* Cb, dprhot_bf16* Qb, int B, int N
 }
 
 }  // namespace
+
+// ---- late-interaction expert scoring (maxsim.h) ---------------------------------------------------------------------------
+// Workspace: val [Ny, RK] f32 | arg [Ny, RK] i32 | raw [Ny, RK] f32 (weights only) | parg [Nq, Ny] i32, each 256-byte aligned.
+static size_t ms_align(size_t b) { return (b + 255) & ~(size_t)255; }
+static int ms_ws_layout(int Nq, int LQ, int KQ, int Ny, int has_w, size_t off[4], size_t* total) {
+  REQUIRE(Nq > 0 && LQ > 0 && Ny > 0, "bad shape Nq=%d LQ=%d Ny=%d", Nq, LQ, Ny);
+  REQUIRE(KQ >= 1 && KQ <= MS_KMAX, "KQ=%d: 1 <= KQ <= %d", KQ, MS_KMAX);
+  const size_t tab = (size_t)Ny * Nq * LQ * KQ * 4;
+  off[0] = 0;
+  off[1] = ms_align(tab);
+  off[2] = off[1] + ms_align(tab);
+  off[3] = off[2] + (has_w ? ms_align(tab) : 0);
+  *total = off[3] + ms_align((size_t)Nq * Ny * 4);
+  return DPRHOT_OK;
+}
+
+static int ms_setup(MsArgs& p, const void* q_tok, const void* c_tok, int Nq, int LQ, int Nc, int LD, int dp, const int* q_ids,
+                    const int* c_ids, const float* q_w, const float* c_w, int KQ, int KD, int pool, int M, const uint8_t* mask,
+                    const void* ws, size_t ws_bytes) {
+  REQUIRE(q_tok && c_tok && ws, "NULL pointer (q_tok, c_tok and the workspace are required)");
+  REQUIRE(Nq > 0 && Nc > 0 && LQ > 0 && LD > 0, "bad shape Nq=%d LQ=%d Nc=%d LD=%d", Nq, LQ, Nc, LD);
+  REQUIRE(LQ <= DPRHOT_MAXSIM_MAX_LEN && LD <= DPRHOT_MAXSIM_MAX_LEN, "LQ=%d LD=%d: token counts are limited to %d", LQ, LD,
+          DPRHOT_MAXSIM_MAX_LEN);
+  REQUIRE(dp >= 32 && dp % 32 == 0, "dp=%d must be a positive multiple of 32 (zero-pad the features)", dp);
+  REQUIRE(KQ >= 1 && KQ <= MS_KMAX && KD >= 1 && KD <= MS_KMAX, "KQ=%d KD=%d: expert slots per token are limited to 1..%d", KQ, KD,
+          MS_KMAX);
+  REQUIRE((q_ids == nullptr) == (c_ids == nullptr), "expert ids are required on both sides or on neither");
+  REQUIRE((q_w == nullptr) == (c_w == nullptr), "expert weights are required on both sides or on neither");
+  REQUIRE(q_ids || (KQ == 1 && KD == 1), "KQ=%d KD=%d without expert ids (ColBERT has one slot per token)", KQ, KD);
+  REQUIRE(pool == DPRHOT_POOL_SUM || pool == DPRHOT_POOL_MAX, "pool=%d (0 sum, 1 max)", pool);
+  REQUIRE(M >= 0, "M=%d", M);
+  REQUIRE(M == 0 || (long)Nq * M == (long)Nc, "pairwise: Nc=%d must equal Nq * M = %d * %d", Nc, Nq, M);
+  REQUIRE(((uintptr_t)q_tok & 15) == 0 && ((uintptr_t)c_tok & 15) == 0, "token rows must be 16-byte aligned");
+  REQUIRE((long)Nq * LQ * KQ <= 0x7fffffffL && (long)Nc * LD * KD <= 0x7fffffffL, "too many token slots");
+  const int Ny = M > 0 ? M : Nc;
+  const long ntiles = M > 0 ? (long)Nq * ((LQ + MS_BM - 1) / MS_BM) : ((long)Nq * LQ + MS_BM - 1) / MS_BM;
+  REQUIRE(ntiles * Ny <= 0x7fffffffL && (long)Nq * Ny <= 0x7fffffffL, "grid too large (Nq=%d Nc=%d)", Nq, Nc);
+  size_t off[4], total = 0;
+  const int rc = ms_ws_layout(Nq, LQ, KQ, Ny, q_w != nullptr, off, &total);
+  if (rc) return rc;
+  REQUIRE(ws_bytes >= total, "workspace of %zu bytes, %zu needed (dprhot_maxsim_workspace_bytes)", ws_bytes, total);
+  char* w = (char*)ws;
+  p = MsArgs{(const uint16_t*)q_tok, (const uint16_t*)c_tok, q_ids, c_ids, q_w, c_w, mask, Nq, LQ, Nc, LD, dp, KQ, KD, M, Ny, pool,
+             (float*)(w + off[0]), (int*)(w + off[1]), q_w ? (float*)(w + off[2]) : nullptr, (int*)(w + off[3]), nullptr};
+  return DPRHOT_OK;
+}
+
+template <int KQT>
+static void ms_launch_fwd(const MsArgs& p, unsigned blocks, hipStream_t st) {
+  if (p.qid && p.qw) hipLaunchKernelGGL((ms_fwd_kernel<KQT, true, true>), dim3(blocks), dim3(256), 0, st, p);
+  else if (p.qid) hipLaunchKernelGGL((ms_fwd_kernel<KQT, true, false>), dim3(blocks), dim3(256), 0, st, p);
+  else if (p.qw) hipLaunchKernelGGL((ms_fwd_kernel<KQT, false, true>), dim3(blocks), dim3(256), 0, st, p);
+  else hipLaunchKernelGGL((ms_fwd_kernel<KQT, false, false>), dim3(blocks), dim3(256), 0, st, p);
+}
+
+template <bool IDS, bool W>
+static int ms_launch_bwd(const MsArgs& p, const MsBwd& g, hipStream_t st) {
+  const int R = p.Nq * p.LQ;
+  if (g.dq || g.dwq)
+    hipLaunchKernelGGL((ms_dq_kernel<IDS, W>), dim3((unsigned)((R + 3) / 4), (unsigned)(g.dq ? (p.dp + MS_DQ_CHUNK - 1) / MS_DQ_CHUNK : 1)),
+                       dim3(256), 0, st, p, g);
+  if (g.dc || g.dwc) {
+    const size_t lds = ((size_t)p.LD * MS_DC_SLICE + (size_t)p.LD * p.KD) * 4;
+    auto kern = ms_dc_kernel<IDS, W>;
+    static AttrOnce attr_done;
+    if (!attr_done) {
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)(((size_t)DPRHOT_MAXSIM_MAX_LEN * (MS_DC_SLICE + MS_KMAX)) * 4)));
+      attr_done = true;
+    }
+    hipLaunchKernelGGL(kern, dim3((unsigned)p.Nc, (unsigned)(g.dc ? (p.dp + MS_DC_SLICE - 1) / MS_DC_SLICE : 1)), dim3(256), lds, st, p, g);
+  }
+  return DPRHOT_OK;
+}
 
 extern "C" {
 
@@ -2305,6 +2380,54 @@ int dprhot_reducescatter_allpairs(void* h, const void* send, void* tmp, void* re
   if (rc != 0) return fail(DPRHOT_E_HIP, "ncclSend / ncclRecv: %s", rccl().GetErrorString(rc));
   if (rc2 != 0) return fail(DPRHOT_E_HIP, "ncclGroupEnd: %s", rccl().GetErrorString(rc2));
   return dprhot_grad_sum_shards(tmp, c->W, count_per_rank, kind, out_kind, recv, stream);  // fp32 accumulation, rank order
+}
+
+int dprhot_maxsim_workspace_bytes(int Nq, int LQ, int KQ, int Ny, int has_weights, size_t* bytes) {
+  REQUIRE(bytes, "NULL pointer");
+  size_t off[4];
+  return ms_ws_layout(Nq, LQ, KQ, Ny, has_weights != 0, off, bytes);
+}
+
+int dprhot_maxsim_fwd(const void* q_tok, const void* c_tok, int Nq, int LQ, int Nc, int LD, int dp, const int* q_ids, const int* c_ids,
+                      const float* q_w, const float* c_w, int KQ, int KD, int pool, int M, const uint8_t* mask, float* S, void* ws,
+                      size_t ws_bytes, void* stream) {
+  MsArgs p;
+  const int rc = ms_setup(p, q_tok, c_tok, Nq, LQ, Nc, LD, dp, q_ids, c_ids, q_w, c_w, KQ, KD, pool, M, mask, ws, ws_bytes);
+  if (rc) return rc;
+  REQUIRE(S, "NULL pointer (S)");
+  p.S = S;
+  hipStream_t st = (hipStream_t)stream;
+  const long ntiles = M > 0 ? (long)Nq * ((LQ + MS_BM - 1) / MS_BM) : ((long)Nq * LQ + MS_BM - 1) / MS_BM;
+  const unsigned blocks = (unsigned)(ntiles * p.Ny);
+  if (KQ == 1) ms_launch_fwd<1>(p, blocks, st);
+  else if (KQ == 2) ms_launch_fwd<2>(p, blocks, st);
+  else if (KQ <= 4) ms_launch_fwd<4>(p, blocks, st);
+  else ms_launch_fwd<8>(p, blocks, st);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(ms_pool_kernel, dim3((unsigned)(((long)Nq * p.Ny + 3) / 4)), dim3(256), 0, st, p);
+  HIP_TRY(hipGetLastError());
+  return DPRHOT_OK;
+}
+
+int dprhot_maxsim_bwd(const float* dS, const void* q_tok, const void* c_tok, int Nq, int LQ, int Nc, int LD, int dp, const int* q_ids,
+                      const int* c_ids, const float* q_w, const float* c_w, int KQ, int KD, int pool, int M, const uint8_t* mask,
+                      const void* ws, size_t ws_bytes, float* dq, float* dc, float* dwq, float* dwc, void* stream) {
+  MsArgs p;
+  const int rc = ms_setup(p, q_tok, c_tok, Nq, LQ, Nc, LD, dp, q_ids, c_ids, q_w, c_w, KQ, KD, pool, M, mask, ws, ws_bytes);
+  if (rc) return rc;
+  REQUIRE(dS, "NULL pointer (dS)");
+  REQUIRE(!(dwq || dwc) || q_w, "weight gradients need the expert weights");
+  MsBwd g{dS, dq, dc, q_w ? dwq : nullptr, q_w ? dwc : nullptr};
+  if (!(dq || dc || g.dwq || g.dwc)) return DPRHOT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  int r2;
+  if (q_ids && q_w) r2 = ms_launch_bwd<true, true>(p, g, st);
+  else if (q_ids) r2 = ms_launch_bwd<true, false>(p, g, st);
+  else if (q_w) r2 = ms_launch_bwd<false, true>(p, g, st);
+  else r2 = ms_launch_bwd<false, false>(p, g, st);
+  if (r2) return r2;
+  HIP_TRY(hipGetLastError());
+  return DPRHOT_OK;
 }
 
 }  // extern "C"

@@ -422,6 +422,38 @@ class HipKernels:
                         "dprhot_pairwise_bwd")
         return dq, dc
 
+    def maxsim_fwd(self, Qb, Cb, qids, cids, qw, cw, KQ, KD, pool, M, m8):
+        """Late-interaction expert scores (dprhot_maxsim_fwd).  Qb [Nq, LQ, dp] / Cb [Nc, LD, dp] bf16 with dp % 32 == 0; ids int32 and
+        weights fp32 flattened per token slot (or None); pool 0 sum / 1 max; M = 0 in-batch, else contexts per query; m8 uint8 [Nc]
+        or None.  Returns (S fp32 [Nq, M or Nc], state): `state` is what maxsim_bwd needs (the argmax tables)."""
+        self._require_gpu(Qb, Cb, qids, cids, qw, cw, m8)
+        Nq, LQ, dp = Qb.shape
+        Nc, LD, _ = Cb.shape
+        Ny = M if M else Nc
+        ws = torch.empty(self._lib.maxsim_workspace_bytes(Nq, LQ, KQ, Ny, qw is not None), dtype=torch.uint8, device=Qb.device)
+        S = torch.empty((Nq, Ny), dtype=torch.float32, device=Qb.device)
+        self._lib.check(self.lib.dprhot_maxsim_fwd(_ptr(Qb), _ptr(Cb), Nq, LQ, Nc, LD, dp, _ptr(qids), _ptr(cids), _ptr(qw), _ptr(cw),
+                                                   KQ, KD, pool, M, _ptr(m8), _ptr(S), _ptr(ws), ws.numel(), self._stream()),
+                        "dprhot_maxsim_fwd")
+        return S, ws
+
+    def maxsim_bwd(self, dS, Qb, Cb, qids, cids, qw, cw, KQ, KD, pool, M, m8, state, need_dq=True, need_dc=True, need_dw=False):
+        """Backward of maxsim_fwd from dS [Nq, Ny] fp32: (dq fp32 [Nq, LQ, dp], dc fp32 [Nc, LD, dp], dwq [Nq, LQ, KQ], dwc [Nc, LD, KD]),
+        each None unless asked for."""
+        self._require_gpu(dS, Qb, Cb)
+        Nq, LQ, dp = Qb.shape
+        Nc, LD, _ = Cb.shape
+        dev = Qb.device
+        dq = torch.empty((Nq, LQ, dp), dtype=torch.float32, device=dev) if need_dq else None
+        dc = torch.empty((Nc, LD, dp), dtype=torch.float32, device=dev) if need_dc else None
+        dwq = torch.empty((Nq, LQ, KQ), dtype=torch.float32, device=dev) if need_dw and qw is not None else None
+        dwc = torch.empty((Nc, LD, KD), dtype=torch.float32, device=dev) if need_dw and qw is not None else None
+        self._lib.check(self.lib.dprhot_maxsim_bwd(_ptr(dS), _ptr(Qb), _ptr(Cb), Nq, LQ, Nc, LD, dp, _ptr(qids), _ptr(cids), _ptr(qw),
+                                                   _ptr(cw), KQ, KD, pool, M, _ptr(m8), _ptr(state), state.numel(), _ptr(dq), _ptr(dc),
+                                                   _ptr(dwq), _ptr(dwc), self._stream()),
+                        "dprhot_maxsim_bwd")
+        return dq, dc, dwq, dwc
+
     def rank_of_gold(self, S, y, y_offset=0):
         self._require_gpu(S, y)
         rows, cols = S.shape
@@ -1237,3 +1269,77 @@ class CorpusSearch:
             if bool(err.any()):  # (one sync, where the caller is about to read the result anyway; no condition sets the word today)
                 raise RuntimeError("dprhot_topk_update_wide reported rows it could not update: " + str(torch.nonzero(err).flatten().tolist()[:8]))
         return self.values, self.indices
+
+
+# ---- late-interaction expert scoring (citadel_task.py:155-238) ------------------------------------------------------------------
+_POOL = {"sum": 0, "max": 1}
+MAXSIM_MAX_SLOTS = 8
+
+
+class MaxSimScore(torch.autograd.Function):
+    """MultiVecRetrieverTask.expert_sim_score (citadel_task.py:215-238) without the token-level score tensor: the token GEMM with a
+    running max / argmax per query slot (HIP, bf16 MFMA, fp32 accumulation), pooled to [Nq, Nc] (or [B, M] pairwise); the backward
+    works from the argmax tables alone.  Gradients flow to both token tensors and, when they require it, to both weight tensors."""
+
+    @staticmethod
+    def forward(ctx, q, c, qw, cw, qids, cids, m8, KQ, KD, pool, M, kernels):
+        kn = kernels if kernels is not None else default_kernels()
+        d = q.shape[-1]
+        pad = (-d) % 32
+        Qb = torch.nn.functional.pad(q.detach(), (0, pad)).to(_BF16).contiguous()
+        Cb = torch.nn.functional.pad(c.detach(), (0, pad)).to(_BF16).contiguous()
+        qwf = None if qw is None else qw.detach().float().contiguous()
+        cwf = None if cw is None else cw.detach().float().contiguous()
+        S, state = kn.maxsim_fwd(Qb, Cb, qids, cids, qwf, cwf, KQ, KD, pool, M, m8)
+        ctx.kn, ctx.meta = kn, (d, KQ, KD, pool, M, q.dtype, c.dtype, None if qw is None else (qw.shape, qw.dtype),
+                                None if cw is None else (cw.shape, cw.dtype))
+        ctx.save_for_backward(Qb, Cb, qwf, cwf, qids, cids, m8, state)
+        return S
+
+    @staticmethod
+    def backward(ctx, dS):
+        Qb, Cb, qwf, cwf, qids, cids, m8, state = ctx.saved_tensors
+        d, KQ, KD, pool, M, qdt, cdt, qws, cws = ctx.meta
+        need_dw = qwf is not None and (ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
+        dq, dc, dwq, dwc = ctx.kn.maxsim_bwd(dS.detach().float().contiguous(), Qb, Cb, qids, cids, qwf, cwf, KQ, KD, pool, M, m8, state,
+                                             ctx.needs_input_grad[0], ctx.needs_input_grad[1], need_dw)
+        gq = dq[..., :d].to(qdt) if dq is not None else None
+        gc = dc[..., :d].to(cdt) if dc is not None else None
+        gqw = dwq.reshape(qws[0]).to(qws[1]) if dwq is not None and ctx.needs_input_grad[2] else None
+        gcw = dwc.reshape(cws[0]).to(cws[1]) if dwc is not None and ctx.needs_input_grad[3] else None
+        return gq, gc, gqw, gcw, None, None, None, None, None, None, None, None
+
+
+def _slots(ids, name):
+    k = 1 if ids.dim() == 2 else ids.shape[2]
+    if not 1 <= k <= MAXSIM_MAX_SLOTS:
+        raise ValueError(f"{name}: {k} expert slots per token; the fused expert score supports 1..{MAXSIM_MAX_SLOTS}")
+    return k
+
+
+def expert_sim_score(query_repr, context_repr, mask=None, pairwise=False, query_pool="sum", kernels=None):
+    """citadel_task.py:215-238 on the repr dicts of ColBERT (expert_repr), COIL (+ expert_ids [B, L], expert_weights [B, L]) and CITADEL
+    (+ expert_ids [B, L, K], expert_weights [B, L, K]).  Returns [Nq, Nc] (or [B, M] with pairwise=True), -inf at masked contexts."""
+    if query_pool not in _POOL:
+        raise NotImplementedError("Invalid query pooling! Available: [max, sum]")
+    q, c = query_repr["expert_repr"], context_repr["expert_repr"]
+    B, Nc = q.shape[0], c.shape[0]
+    M = Nc // B if pairwise else 0
+    if pairwise and M * B != Nc:
+        raise ValueError(f"pairwise expert score: {Nc} contexts is not a multiple of {B} queries")
+    qids = cids = qw = cw = None
+    KQ = KD = 1
+    if "expert_ids" in query_repr:
+        KQ, KD = _slots(query_repr["expert_ids"], "query expert_ids"), _slots(context_repr["expert_ids"], "context expert_ids")
+        qids = query_repr["expert_ids"].to(torch.int32).contiguous()  # int64 -> int32 once
+        cids = context_repr["expert_ids"].to(torch.int32).contiguous()
+        if "expert_weights" in query_repr:
+            qw, cw = query_repr["expert_weights"], context_repr["expert_weights"]
+            if not qw.is_floating_point():  # COIL: the integer attention mask, no gradient
+                qw, cw = qw.float(), cw.float()
+    m8 = None
+    if mask is not None:
+        m8 = mask.reshape(-1).to(torch.uint8).contiguous()
+        if m8.numel() != Nc:
+            raise ValueError(f"expert score: mask of {m8.numel()} entries for {Nc} contexts")
+    return MaxSimScore.apply(q, c, qw, cw, qids, cids, m8, KQ, KD, _POOL[query_pool], M, kernels)

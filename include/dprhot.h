@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DPRHOT_VERSION 172 /* 0.1.72: + dprhot_fwd_one_pass; options nl128, nl128_max_tiles, loss_with_dq, dq_cap_few, pair128, pair128_slices */
+#define DPRHOT_VERSION 173 /* 0.1.73: + dprhot_maxsim_workspace_bytes / _fwd / _bwd (late-interaction expert scoring) */
 
 #define DPRHOT_OK 0
 #define DPRHOT_E_INVALID (-1)     /* bad argument (NULL pointer, non-positive or misaligned size) */
@@ -293,6 +293,31 @@ int dprhot_pairwise_fwd(const float* q, const float* c, const uint8_t* mask, int
 /* Its backward: dq[b] = sum_j g[b][j] c[b*M+j] and dc[b*M+j] = g[b][j] q[b]; g [B,M] fp32 with 0 at masked pairs.
  * dq / dc may each be NULL. */
 int dprhot_pairwise_bwd(const float* g, const float* q, const float* c, int B, int M, int d, float* dq, float* dc, void* stream);
+
+/* Late-interaction ("MaxSim") expert scoring of ColBERT / COIL / CITADEL (dpr_scale/task/citadel_task.py:155-238), without the
+ * token-level score tensor:
+ *   S[q][y] = POOL_{i,kq} MAX_{j,kd} <Q[q,i], C[ctx,j]> * [q_ids[q,i,kq] == c_ids[ctx,j,kd]] * q_w[q,i,kq] * c_w[ctx,j,kd]
+ * q_tok bf16 [Nq, LQ, dp], c_tok bf16 [Nc, LD, dp], dp a multiple of 32 (zero-pad the features), 16-byte aligned rows.
+ * q_ids int32 [Nq, LQ, KQ] / c_ids [Nc, LD, KD], both or neither (ColBERT: neither, KQ = KD = 1); q_w / c_w fp32 of the same shapes,
+ * both or neither.  Unmatched slots score exactly 0.  1 <= KQ, KD <= 8; 1 <= LQ, LD <= DPRHOT_MAXSIM_MAX_LEN.
+ * pool DPRHOT_POOL_SUM: max over context slots, sum over query slots; DPRHOT_POOL_MAX: max over both.
+ * M = 0: in-batch, S [Nq, Nc], y = ctx.  M > 0: pairwise (Nc = Nq * M), S [Nq, M], query q against contexts q*M .. q*M+M-1.
+ * mask uint8 [Nc] (may be NULL): S = -inf at masked contexts, and no gradient flows through them.
+ * Ties go to the LOWEST flattened context slot j * KD + kd (torch.max(dim)).
+ * The workspace (dprhot_maxsim_workspace_bytes(Nq, LQ, KQ, Ny = M ? M : Nc, weights != NULL)) holds the per-row-slot max / argmax
+ * tables that the backward reads: keep it unchanged between the forward and its backward.
+ * Backward: dq fp32 [Nq, LQ, dp], dc fp32 [Nc, LD, dp], dwq fp32 [Nq, LQ, KQ], dwc fp32 [Nc, LD, KD]; each may be NULL and is
+ * fully written otherwise.  No atomics: bit-identical run to run. */
+#define DPRHOT_MAXSIM_MAX_LEN 512
+#define DPRHOT_POOL_SUM 0
+#define DPRHOT_POOL_MAX 1
+int dprhot_maxsim_workspace_bytes(int Nq, int LQ, int KQ, int Ny, int has_weights, size_t* bytes);
+int dprhot_maxsim_fwd(const void* q_tok, const void* c_tok, int Nq, int LQ, int Nc, int LD, int dp, const int* q_ids, const int* c_ids,
+                      const float* q_w, const float* c_w, int KQ, int KD, int pool, int M, const uint8_t* mask, float* S, void* ws,
+                      size_t ws_bytes, void* stream);
+int dprhot_maxsim_bwd(const float* dS, const void* q_tok, const void* c_tok, int Nq, int LQ, int Nc, int LD, int dp, const int* q_ids,
+                      const int* c_ids, const float* q_w, const float* c_w, int KQ, int KD, int pool, int M, const uint8_t* mask,
+                      const void* ws, size_t ws_bytes, float* dq, float* dc, float* dwq, float* dwc, void* stream);
 
 /* The step as the autograd operator of dpr_scale_amd/hotpath.py runs it (dpr_task.py:197-212 + its backward inside the forward call):
  * dprhot_inbatch_step_f32 / _packed_f32 with
