@@ -106,6 +106,12 @@ SIGNATURES = {
     "dprhot_maxsim_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p]),
+    "dprhot_ivf_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "dprhot_ivf_score": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                 c_int, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "dprhot_ivf_search": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                  c_int, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p,
+                                  c_int, c_void_p, c_size_t, c_void_p]),
     "dprhot_inbatch_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_size_t, c_void_p]),
 }
@@ -191,6 +197,12 @@ def fwd_one_pass(B: int, Nc: int, d: int) -> int:
 def maxsim_workspace_bytes(Nq: int, LQ: int, KQ: int, Ny: int, has_weights: bool) -> int:
     out = c_size_t(0)
     check(lib.dprhot_maxsim_workspace_bytes(Nq, LQ, KQ, Ny, int(bool(has_weights)), ctypes.byref(out)), "dprhot_maxsim_workspace_bytes")
+    return out.value
+
+
+def ivf_workspace_bytes(nq: int, n_entries: int, chunk: int, has_cls: bool) -> int:
+    out = c_size_t(0)
+    check(lib.dprhot_ivf_workspace_bytes(int(nq), int(n_entries), int(chunk), int(bool(has_cls)), ctypes.byref(out)), "dprhot_ivf_workspace_bytes")
     return out.value
 
 

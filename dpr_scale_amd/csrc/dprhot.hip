@@ -31,6 +31,7 @@
 #include "wide.h"
 #include "wideselect.h"
 #include "maxsim.h"
+#include "ivf.h"
 
 using namespace dprhot;
 
@@ -2427,6 +2428,109 @@ int dprhot_maxsim_bwd(const float* dS, const void* q_tok, const void* c_tok, int
   else r2 = ms_launch_bwd<false, false>(p, g, st);
   if (r2) return r2;
   HIP_TRY(hipGetLastError());
+  return DPRHOT_OK;
+}
+
+// ---- inverted-index retrieval (csrc/ivf.h) ----
+constexpr int IVF_MAX_ENTRIES_PER_QUERY = 4096;
+static size_t ivf_ws_bytes(int nq, int chunk) { return align256((size_t)nq * (size_t)chunk * 4); }
+
+static int ivf_check_batch(int nq, int n_entries, int n_bexp, const void* ent_vec, const void* ent_q, const void* bexp, const void* bexp_off) {
+  REQUIRE(nq > 0, "bad shape nq=%d", nq);
+  REQUIRE(n_entries >= 0 && n_bexp >= 0 && n_bexp <= n_entries, "bad batch n_entries=%d n_bexp=%d", n_entries, n_bexp);
+  REQUIRE((long long)n_entries <= (long long)nq * IVF_MAX_ENTRIES_PER_QUERY, "n_entries=%d: at most %d entries per query", n_entries,
+          IVF_MAX_ENTRIES_PER_QUERY);
+  REQUIRE(n_entries == 0 || n_bexp > 0, "entries without a batch expert list");
+  REQUIRE(n_entries == 0 || (ent_vec && ent_q && bexp && bexp_off), "NULL pointer (query batch)");
+  REQUIRE(n_entries == 0 || aligned16(ent_vec), "entry vectors must be 16-byte aligned");
+  return DPRHOT_OK;
+}
+
+static int ivf_check_index(const void* post_vec, const void* post_doc, const void* exp_off, int64_t n_postings, int n_experts, int dp) {
+  REQUIRE(n_postings >= 0 && n_postings < (1ll << 40), "n_postings=%lld out of range (< 2^40)", (long long)n_postings);
+  REQUIRE(n_experts > 0 && exp_off, "bad index: n_experts=%d", n_experts);
+  REQUIRE(dp > 0 && dp % 32 == 0, "dp=%d must be a positive multiple of 32 (pad with zeros)", dp);
+  REQUIRE(n_postings == 0 || (post_vec && post_doc), "NULL pointer (postings)");
+  REQUIRE(n_postings == 0 || aligned16(post_vec), "posting vectors must be 16-byte aligned");
+  return DPRHOT_OK;
+}
+
+int dprhot_ivf_workspace_bytes(int nq, int n_entries, int chunk, int has_cls, size_t* bytes) {
+  REQUIRE(bytes != nullptr, "NULL out pointer");
+  REQUIRE(nq > 0 && chunk > 0 && chunk % 8 == 0, "bad shape nq=%d chunk=%d (chunk: a positive multiple of 8)", nq, chunk);
+  REQUIRE(n_entries >= 0 && (long long)n_entries <= (long long)nq * IVF_MAX_ENTRIES_PER_QUERY, "n_entries=%d: at most %d entries per query",
+          n_entries, IVF_MAX_ENTRIES_PER_QUERY);
+  (void)has_cls;  // the CLS scores are written straight into the chunk's score buffer
+  *bytes = ivf_ws_bytes(nq, chunk);
+  return DPRHOT_OK;
+}
+
+int dprhot_ivf_score(const dprhot_bf16* post_vec, const int32_t* post_doc, const int64_t* exp_off, int64_t n_postings, int n_experts, int dp,
+                     const dprhot_bf16* ent_vec, const int32_t* ent_q, int n_entries, const int32_t* bexp, const int32_t* bexp_off,
+                     int n_bexp, int nq, int64_t doc_begin, int cols, float* S, int64_t ld, void* stream) {
+  if (int rc = ivf_check_index(post_vec, post_doc, exp_off, n_postings, n_experts, dp)) return rc;
+  if (int rc = ivf_check_batch(nq, n_entries, n_bexp, ent_vec, ent_q, bexp, bexp_off)) return rc;
+  REQUIRE(S != nullptr, "NULL pointer (S)");
+  REQUIRE(cols > 0 && ld >= cols, "bad shape cols=%d ld=%lld", cols, (long long)ld);
+  REQUIRE(doc_begin >= 0 && doc_begin + cols < (1ll << 31), "doc ids %lld .. +%d must stay below 2^31", (long long)doc_begin, cols);
+  if (n_entries == 0 || n_postings == 0) return DPRHOT_OK;
+  IvfArgs a{reinterpret_cast<const uint16_t*>(post_vec), post_doc, reinterpret_cast<const long long*>(exp_off), n_experts, dp,
+            reinterpret_cast<const uint16_t*>(ent_vec), ent_q, bexp, bexp_off, n_bexp, nq, (long long)doc_begin, cols, S, (long long)ld};
+  const unsigned blocks = (unsigned)cdiv(cdiv(cols, IVF_T), IVF_WAVES);
+  hipLaunchKernelGGL(ivf_score_kernel, dim3(blocks), dim3(64 * IVF_WAVES), 0, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return DPRHOT_OK;
+}
+
+int dprhot_ivf_search(const dprhot_bf16* post_vec, const int32_t* post_doc, const int64_t* exp_off, int64_t n_postings, int n_experts, int dp,
+                      const dprhot_bf16* ent_vec, const int32_t* ent_q, int n_entries, const int32_t* bexp, const int32_t* bexp_off,
+                      int n_bexp, int nq, const dprhot_bf16* cls_q, const dprhot_bf16* cls_doc, int dc, int64_t cls_rows,
+                      int64_t corpus_len, int64_t id_begin, int64_t id_end, int k, int chunk, float* values, int64_t* indices, int first,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = ivf_check_index(post_vec, post_doc, exp_off, n_postings, n_experts, dp)) return rc;
+  if (int rc = ivf_check_batch(nq, n_entries, n_bexp, ent_vec, ent_q, bexp, bexp_off)) return rc;
+  REQUIRE(values && indices, "NULL pointer");
+  REQUIRE(corpus_len > 0 && corpus_len < (1ll << 31), "corpus_len=%lld out of range (1 .. 2^31 - 1)", (long long)corpus_len);
+  REQUIRE(k >= 1 && k <= corpus_len, "topk=%d out of range (1 .. corpus_len=%lld)", k, (long long)corpus_len);
+  REQUIRE(0 <= id_begin && id_begin < id_end && id_end <= corpus_len, "bad doc-id range [%lld, %lld) of %lld", (long long)id_begin,
+          (long long)id_end, (long long)corpus_len);
+  REQUIRE(chunk > 0 && chunk % 8 == 0, "chunk=%d must be a positive multiple of 8", chunk);
+  const bool has_cls = cls_q != nullptr || cls_doc != nullptr;
+  if (has_cls) {
+    REQUIRE(cls_q && cls_doc, "CLS vectors of one side only");
+    REQUIRE(dc > 0 && dc % 8 == 0, "dc=%d must be a positive multiple of 8 (pad with zeros)", dc);
+    REQUIRE(cls_rows >= id_end + 7, "cls_doc has %lld rows; %lld needed (corpus_len + 7, zero rows behind the corpus)", (long long)cls_rows,
+            (long long)(id_end + 7));
+    REQUIRE(aligned16(cls_q) && aligned16(cls_doc), "CLS vectors must be 16-byte aligned");
+  }
+  const bool wide = k > TK_KWIDE;
+  const size_t s_bytes = ivf_ws_bytes(nq, chunk);
+  const size_t need = s_bytes + (wide ? wsel_ws_bytes(nq, k) : 0);
+  if (workspace == nullptr || workspace_bytes < need)
+    return fail(DPRHOT_E_WORKSPACE, "ivf_search needs %zu workspace bytes (dprhot_ivf_workspace_bytes%s), got %zu", need,
+                wide ? " + dprhot_topk_wide_workspace_bytes" : "", workspace_bytes);
+  REQUIRE(aligned16(workspace), "workspace must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  float* S = static_cast<float*>(workspace);
+  void* wide_ws = static_cast<char*>(workspace) + s_bytes;
+  for (int64_t j0 = id_begin; j0 < id_end; j0 += chunk) {
+    const int cols = (int)(id_end - j0 < chunk ? id_end - j0 : chunk);
+    const int ld = (cols + 7) / 8 * 8;  // (<= chunk: chunk is a multiple of 8)
+    if (has_cls) {
+      if (int rc = dprhot_sim_fwd(cls_q, nq, cls_doc + (size_t)j0 * dc, ld, dc, nullptr, 1.0f, S, stream)) return rc;
+    } else {
+      HIP_TRY(hipMemsetAsync(S, 0, (size_t)nq * ld * sizeof(float), st));
+    }
+    if (int rc = dprhot_ivf_score(post_vec, post_doc, exp_off, n_postings, n_experts, dp, ent_vec, ent_q, n_entries, bexp, bexp_off, n_bexp,
+                                  nq, j0, cols, S, ld, stream))
+      return rc;
+    const int f = (first && j0 == id_begin) ? 1 : 0;
+    if (wide) {
+      if (int rc = dprhot_topk_update_wide(S, nq, cols, ld, j0, k, values, indices, f, wide_ws, workspace_bytes - s_bytes, stream)) return rc;
+    } else {
+      if (int rc = dprhot_topk_update(S, nq, cols, ld, j0, k, values, indices, f, stream)) return rc;
+    }
+  }
   return DPRHOT_OK;
 }
 

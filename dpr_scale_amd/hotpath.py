@@ -530,6 +530,34 @@ class HipKernels:
                                                _ptr(values), _ptr(indices), int(bool(first)), _ptr(ws), ws.numel(),
                                                self._stream()), "dprhot_search")
 
+    # -- inverted-index retrieval (csrc/ivf.h; dpr_scale_amd/ivf.py owns the packing) ---------------------
+    def ivf_workspace(self, nq, n_entries, chunk, has_cls, k, like):
+        n = self._lib.ivf_workspace_bytes(nq, n_entries, chunk, has_cls)
+        if k > 4096:  # the HBM-resident selection's state lives behind the score buffer
+            m = ctypes.c_size_t(0)
+            self._lib.check(self.lib.dprhot_topk_wide_workspace_bytes(int(nq), int(k), ctypes.byref(m)), "dprhot_topk_wide_workspace_bytes")
+            n += m.value
+        return torch.empty(n, dtype=torch.uint8, device=like.device)
+
+    def ivf_score(self, index, qb, doc_begin, cols, S):
+        """Adds the expert part of doc ids doc_begin .. doc_begin + cols into S [nq, >= cols] fp32 (dprhot_ivf_score)."""
+        self._require_gpu(index.post_vec, index.post_doc, index.exp_off, qb.ent_vec, qb.ent_q, qb.bexp, qb.boff, S)
+        self._lib.check(self.lib.dprhot_ivf_score(_ptr(index.post_vec), _ptr(index.post_doc), _ptr(index.exp_off), index.n_postings,
+                                                  index.n_experts, index.dp, _ptr(qb.ent_vec), _ptr(qb.ent_q), qb.n_entries, _ptr(qb.bexp),
+                                                  _ptr(qb.boff), int(qb.bexp.shape[0]), qb.nq, int(doc_begin), int(cols), _ptr(S),
+                                                  S.stride(0), self._stream()), "dprhot_ivf_score")
+
+    def ivf_search(self, index, qb, id_begin, id_end, values, indices, first, chunk, ws):
+        """Folds doc ids [id_begin, id_end) of a device-resident index into the running top-k (dprhot_ivf_search)."""
+        self._require_gpu(index.post_vec, index.post_doc, index.exp_off, index.cls, qb.ent_vec, qb.ent_q, qb.bexp, qb.boff, qb.cls, values,
+                          indices, ws)
+        self._lib.check(self.lib.dprhot_ivf_search(_ptr(index.post_vec), _ptr(index.post_doc), _ptr(index.exp_off), index.n_postings,
+                                                   index.n_experts, index.dp, _ptr(qb.ent_vec), _ptr(qb.ent_q), qb.n_entries, _ptr(qb.bexp),
+                                                   _ptr(qb.boff), int(qb.bexp.shape[0]), qb.nq, _ptr(qb.cls), _ptr(index.cls), index.dc,
+                                                   0 if index.cls is None else index.cls.shape[0], index.corpus_len, int(id_begin),
+                                                   int(id_end), values.shape[1], int(chunk), _ptr(values), _ptr(indices),
+                                                   int(bool(first)), _ptr(ws), ws.numel(), self._stream()), "dprhot_ivf_search")
+
 
 _DEFAULT = None
 

@@ -1,0 +1,184 @@
+"""Drop-in for dpr_scale.task.citadel_retrieval_task.CITADELRetrievalTask (reference: dpr_scale/task/citadel_retrieval_task.py).
+
+Same constructor kwargs (:15-30), `_eval_step` (:84-140), `test_epoch_end` (:145-177), `merge_trec_results` (:179-201) and
+`merge_qa_results` (:204-231).  The reference builds `self.index` from dpr_scale/index/inverted_vector_index.py, which it does not
+ship; here the index is dpr_scale_amd.ivf.load_index (one device-resident inverted index, scored by libdprhot.so).
+
+Scope: `quantizer="pq"`, `cuda=False`, `portion` below 1.0 and `hnsw_index` raise NotImplementedError; `expert_parallel` (the
+reference's split of experts across GPUs) is accepted and ignored: the index lives on one device.
+"""
+import collections
+import json
+import os
+import time
+
+import torch
+
+from .. import ivf
+from .citadel_task import MultiVecRetrieverTask
+
+_SCOPE = "inverted-index retrieval supports the plain GPU index only (no product quantisation, CPU index, partial index or hnsw)"
+
+
+class PassageTable:
+    """The passages file of the reference's IDCSVDataset(path, use_id=True): a tab-separated file with a header row and an `id`
+    column; rows are looked up by their id string."""
+
+    def __init__(self, path, sep="\t"):
+        self.rows = {}
+        with open(path, encoding="utf-8") as f:
+            self.columns = self._parse(f.readline(), sep)
+            for line in f:
+                vals = self._parse(line, sep)
+                if len(vals) == len(self.columns):
+                    row = dict(zip(self.columns, vals))
+                    self.rows[row["id"]] = row
+
+    @staticmethod
+    def _parse(line, sep):
+        row = line.rstrip("\r\n").split(sep)
+        return [v.strip('"').replace('""', '"') if v and v[0] == '"' and v[-1] == '"' else v for v in row]
+
+    def __len__(self):
+        return len(self.rows)
+
+    def __getitem__(self, key):
+        return self.rows[key]
+
+
+class CITADELRetrievalTask(MultiVecRetrieverTask):
+    def __init__(
+        self,
+        ctx_embeddings_dir,
+        checkpoint_path,
+        index2docid_path=None,
+        hnsw_index=False,
+        output_path="/tmp/results.jsonl",
+        passages="",
+        topk=100,
+        cuda=True,
+        portion=1.0,
+        quantizer=None,
+        sub_vec_dim=4,
+        expert_parallel=True,
+        **kwargs,
+    ):
+        super().__init__(**kwargs)
+        self.ctx_embeddings_dir = ctx_embeddings_dir
+        self.checkpoint_path = checkpoint_path
+        self.index2docid_path = index2docid_path
+        self.hnsw_index = hnsw_index
+        self.output_path = output_path
+        self.passages = passages
+        self.topk = topk
+        self.cuda = cuda
+        self.quantizer = quantizer if quantizer != "None" else None
+        self.sub_vec_dim = sub_vec_dim
+        self.portion = portion
+        self.expert_parallel = expert_parallel
+        self.latency = collections.defaultdict(float)
+        if self.quantizer == "pq":
+            raise NotImplementedError(f'quantizer="pq": {_SCOPE}')
+        if self.quantizer is not None:
+            raise NotImplementedError(f"quantizer={self.quantizer!r}: {_SCOPE}")
+        if not self.cuda:
+            raise NotImplementedError(f"cuda=False: {_SCOPE}")
+        if self.portion != 1.0 or self.hnsw_index:
+            raise NotImplementedError(f"portion={self.portion}, hnsw_index={self.hnsw_index}: {_SCOPE}")
+
+    def setup(self, stage: str):
+        super().setup("train")
+        print(f"Loading checkpoint from {self.checkpoint_path}")
+        checkpoint = torch.load(self.checkpoint_path, map_location="cpu", weights_only=False)
+        self.load_state_dict(checkpoint["state_dict"])
+        print(f"Loading passages from {self.passages}")
+        self.ctxs = PassageTable(self.passages)
+        print("Setting up index...")
+        self.index = ivf.load_index(self.ctx_embeddings_dir, len(self.ctxs), self.device if self.device.type == "cuda" else None)
+
+    def forward(self, query_ids):
+        return self.encode_queries(query_ids)
+
+    def _eval_step(self, batch, batch_idx):
+        tic = time.perf_counter()
+        query_ids = batch["query_ids"]
+        topic_ids = batch["topic_ids"] if "topic_ids" in batch else []
+        answers = batch["answers"] if "answers" in batch else []
+        questions = batch["question"] if "question" in batch else []
+        queries_repr = {k: v.detach() for k, v in self(query_ids).items()}
+        batch_cls = queries_repr["cls_repr"] if "cls_repr" in queries_repr else []
+        coil = queries_repr["expert_ids"].dim() == 2
+        n = len(topic_ids) if len(topic_ids) > 0 else len(query_ids["input_ids"])
+        # one transfer instead of one per token: the per-token work below is host work on small tensors
+        reprs, ids, wts, att = (queries_repr[k].cpu() for k in ("expert_repr", "expert_ids", "expert_weights", "attention_mask"))
+        batch_embeddings, batch_weights = [], []
+        for b in range(n):
+            embeddings, weights = collections.defaultdict(list), collections.defaultdict(list)
+            for x, e, w, a in zip(reprs[b], ids[b], wts[b], att[b]):
+                if a > 0:
+                    if coil:  # fp32 entries (:116-117)
+                        embeddings[e.item()].append((w * x).to(torch.float32))
+                        weights[e.item()].append(w.to(torch.float32))
+                    else:  # CITADEL: fp16 entries, zero weights dropped (:119-122)
+                        for ek, wk in zip(e, w):
+                            if wk > 0:
+                                embeddings[ek.item()].append((wk * x).to(torch.float16))
+                                weights[ek.item()].append(wk.to(torch.float16))
+            batch_embeddings.append(embeddings)
+            batch_weights.append(weights)
+        self.latency["encode_time"] += time.perf_counter() - tic
+        batch_top_scores, batch_top_ids = self.index.search(batch_cls, batch_embeddings, batch_weights, self.topk)
+        return batch_top_scores.cpu().tolist(), batch_top_ids.cpu().tolist(), topic_ids, questions, answers
+
+    def test_step(self, batch, batch_idx):
+        return self._eval_step(batch, batch_idx)
+
+    def test_epoch_end(self, queries_reprs):
+        top_scores, top_ids, topic_ids, questions, answers = [], [], [], [], []
+        for b_scores, b_ids, b_topics, b_questions, b_answers in queries_reprs:
+            top_scores.extend(b_scores)
+            top_ids.extend(b_ids)
+            topic_ids.extend(b_topics)
+            questions.extend(b_questions)
+            answers.extend(b_answers)
+        self.latency["encode_time"] += self.index.latency["encode_time"]
+        self.index.latency.pop("encode_time")
+        print(dict(self.latency))
+        print(dict(self.index.latency))
+        if len(topic_ids) > 0:
+            lines = self.merge_trec_results(topic_ids, top_ids, top_scores)
+            os.makedirs(self.output_path, exist_ok=True)
+            with open(os.path.join(self.output_path, f"retrieval_{self.global_rank:04}.trec"), "w") as g:
+                g.writelines(lines)
+        elif len(answers) > 0:
+            qa = self.merge_qa_results(questions, answers, top_ids, top_scores)
+            os.makedirs(self.output_path, exist_ok=True)
+            with open(os.path.join(self.output_path, f"retrieval_{self.global_rank:04}.json"), "w") as g:
+                g.write(json.dumps(qa, indent=4))
+                g.write("\n")
+        if torch.distributed.is_available() and torch.distributed.is_initialized():
+            torch.distributed.barrier()
+
+    def merge_trec_results(self, topic_ids, top_doc_ids, scores_list):
+        i2d = []
+        if self.index2docid_path is not None and os.path.exists(self.index2docid_path):
+            with open(self.index2docid_path) as f:
+                i2d = [line.strip() for line in f]
+        assert len(top_doc_ids) == len(topic_ids) == len(scores_list)
+        out = []
+        for topic_id, doc_ids, scores in zip(topic_ids, top_doc_ids, scores_list):
+            for rank, (doc_id, score) in enumerate(zip(doc_ids, scores)):
+                name = i2d[doc_id] if i2d else doc_id
+                out.append(f"{topic_id} Q0 {name} {rank + 1} {score:.6f} dpr-scale\n")
+        return out
+
+    def merge_qa_results(self, questions, answers, top_doc_ids, scores_list):
+        assert len(top_doc_ids) == len(answers) == len(scores_list)
+        out = []
+        for question, answer, doc_ids, scores in zip(questions, answers, top_doc_ids, scores_list):
+            ctxs = []
+            for doc_id, score in zip(doc_ids, scores):
+                row = self.ctxs[str(doc_id)]
+                ctxs.append({"id": row["id"], "title": row["title"], "text": row["text"], "score": float(score)})
+            out.append({"question": question, "answers": answer, "ctxs": ctxs})
+        return out

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DPRHOT_VERSION 173 /* 0.1.73: + dprhot_maxsim_workspace_bytes / _fwd / _bwd (late-interaction expert scoring) */
+#define DPRHOT_VERSION 174 /* 0.1.74: + dprhot_ivf_workspace_bytes / _score / _search (inverted-index retrieval for CITADEL / COIL) */
 
 #define DPRHOT_OK 0
 #define DPRHOT_E_INVALID (-1)     /* bad argument (NULL pointer, non-positive or misaligned size) */
@@ -318,6 +318,34 @@ int dprhot_maxsim_fwd(const void* q_tok, const void* c_tok, int Nq, int LQ, int 
 int dprhot_maxsim_bwd(const float* dS, const void* q_tok, const void* c_tok, int Nq, int LQ, int Nc, int LD, int dp, const int* q_ids,
                       const int* c_ids, const float* q_w, const float* c_w, int KQ, int KD, int pool, int M, const uint8_t* mask,
                       const void* ws, size_t ws_bytes, float* dq, float* dc, float* dwq, float* dwc, void* stream);
+
+/* Inverted-index retrieval for CITADEL / COIL (the search the reference's citadel_retrieval_task.py:136 asks of its absent
+ * dpr_scale/index/inverted_vector_index.py; csrc/ivf.h):
+ *   score(n, doc) = sum over entries (e, u) of query n of max(0, max over postings (doc, v) of expert e of <u, v>)  [+ <cls_q[n], cls_doc[doc]>]
+ * Index (device, built once): postings sorted by (expert, doc) -- post_vec bf16 [n_postings, dp] (dp = d zero-padded to a multiple of
+ * 32), post_doc int32 [n_postings] -- and exp_off int64 [n_experts + 1], offsets by expert id.  Query batch: entries sorted by
+ * (expert, query, slot) -- ent_vec bf16 [n_entries, dp], ent_q int32 [n_entries] query rows -- plus bexp int32 [n_bexp], the distinct
+ * experts of the batch ascending, and bexp_off int32 [n_bexp + 1], their entry ranges (an expert >= n_experts has no postings).
+ * dprhot_ivf_score ADDS the expert part for doc ids doc_begin .. doc_begin + cols into S[nq, ld].  Every cell has one owner that adds
+ * its entries in the order (expert ascending, the query's entries as listed); no floating-point atomics: two runs are bit-identical
+ * and a cell's value does not depend on the chunk or on the other queries of the batch.  An entry adds max(0, .): a NaN product adds 0.
+ * dprhot_ivf_search runs doc ids [id_begin, id_end) in chunks of `chunk` (a multiple of 8): S = CLS scores (dprhot_sim_fwd on the
+ * chunk's rows of cls_doc bf16 [cls_rows >= corpus_len + 7, dc], dc % 8 == 0, zero rows behind the corpus; cls_q bf16 [nq, dc]) or
+ * zeros when both CLS pointers are NULL, then dprhot_ivf_score, then the streaming top-k (dprhot_topk_update; dprhot_topk_update_wide
+ * for k > 4096) with col_offset = the chunk's first id.  values / indices / first as in dprhot_search: disjoint id ranges may be folded
+ * into one result.  Every doc id of the range competes, also one without a posting (score: the CLS part or 0).
+ * Limits (DPRHOT_E_INVALID): corpus_len < 2^31, n_postings < 2^40, 1 <= k <= corpus_len, n_entries <= 4096 * nq (the packer checks
+ * 4096 per query).  workspace: dprhot_ivf_workspace_bytes(nq, n_entries, chunk, has_cls) (+ dprhot_topk_wide_workspace_bytes(nq, k)
+ * behind it when k > 4096); DPRHOT_E_WORKSPACE when smaller. */
+int dprhot_ivf_workspace_bytes(int nq, int n_entries, int chunk, int has_cls, size_t* bytes);
+int dprhot_ivf_score(const dprhot_bf16* post_vec, const int32_t* post_doc, const int64_t* exp_off, int64_t n_postings, int n_experts, int dp,
+                     const dprhot_bf16* ent_vec, const int32_t* ent_q, int n_entries, const int32_t* bexp, const int32_t* bexp_off,
+                     int n_bexp, int nq, int64_t doc_begin, int cols, float* S, int64_t ld, void* stream);
+int dprhot_ivf_search(const dprhot_bf16* post_vec, const int32_t* post_doc, const int64_t* exp_off, int64_t n_postings, int n_experts, int dp,
+                      const dprhot_bf16* ent_vec, const int32_t* ent_q, int n_entries, const int32_t* bexp, const int32_t* bexp_off,
+                      int n_bexp, int nq, const dprhot_bf16* cls_q, const dprhot_bf16* cls_doc, int dc, int64_t cls_rows,
+                      int64_t corpus_len, int64_t id_begin, int64_t id_end, int k, int chunk, float* values, int64_t* indices, int first,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* The step as the autograd operator of dpr_scale_amd/hotpath.py runs it (dpr_task.py:197-212 + its backward inside the forward call):
  * dprhot_inbatch_step_f32 / _packed_f32 with
