@@ -20,6 +20,7 @@
 
 #include <type_traits>
 #include "gemm_bf16.h"
+#include "sim_small.h"
 #include "gemm256.h"
 #include "gemm8p.h"
 #include "gemm8pb.h"
@@ -133,7 +134,7 @@ struct AttrOnce {
 // ---- explicit process-wide options (dprhot_set_option): test and A/B switches of the plans.  Production never sets one; they replace
 // the environment switches the library used to cache on first use (hidden configuration behind an ABI that advertises none).
 enum OptId { OPT_TILE, OPT_NO_TR, OPT_UNFUSED_BWD, OPT_BIG_MIN, OPT_NO_NL, OPT_NO_BIG_BWD, OPT_NO_SKINNY, OPT_NO_SMALL_STEP, OPT_NO_SHORT,
-             OPT_SK_COLS, OPT_SEARCH_UNFUSED, OPT_NO_8PB, OPT_NO_WIDE, OPT_WIDE_NOCOPY, OPT_NO_8P_STORE, OPT_NO_WIDE_BWD, OPT_NT_STORES, OPT_SK_DQ_SLICES, OPT_SK_FUSED, OPT_SK_DBG, OPT_SK_W8, OPT_SK_PAIR, OPT_SK_SIM_W8, OPT_SK_SIM_PRIV, OPT_SK_TAIL, OPT_SK_DC_REGSCALE, OPT_G8_ONE_TILE, OPT_NL_P16, OPT_SK_DQ_ATOMIC, OPT_NL_MIN, OPT_G128_DMA, OPT_DC_ALONE_8P, OPT_DQ_ONE_ROUND, OPT_DQ_CAP_FEW, OPT_LOSS_WITH_DQ, OPT_NL128, OPT_NL128_BELOW, OPT_PAIR128, OPT_PAIR128_CAP, OPT_NL128_MIN_TILES, OPT_P16_STAGED, OPT_COUNT };
+             OPT_SK_COLS, OPT_SEARCH_UNFUSED, OPT_NO_8PB, OPT_NO_WIDE, OPT_WIDE_NOCOPY, OPT_NO_8P_STORE, OPT_NO_WIDE_BWD, OPT_NT_STORES, OPT_SK_DQ_SLICES, OPT_SK_FUSED, OPT_SK_DBG, OPT_SK_W8, OPT_SK_PAIR, OPT_SK_SIM_W8, OPT_SK_SIM_PRIV, OPT_SK_TAIL, OPT_SK_DC_REGSCALE, OPT_G8_ONE_TILE, OPT_NL_P16, OPT_SK_DQ_ATOMIC, OPT_NL_MIN, OPT_G128_DMA, OPT_DC_ALONE_8P, OPT_DQ_ONE_ROUND, OPT_DQ_CAP_FEW, OPT_LOSS_WITH_DQ, OPT_NL128, OPT_NL128_BELOW, OPT_PAIR128, OPT_PAIR128_CAP, OPT_NL128_MIN_TILES, OPT_P16_STAGED, OPT_SMALL_SIM, OPT_COUNT };
 struct OptDef { OptId id; const char* name; int def; const char* what; };
 constexpr OptDef kOptDefs[OPT_COUNT] = {
     {OPT_TILE, "tile", -1, "0..5 pins the tile of the single-GEMM launches (gemm_bf16.h), -1 = plan"},
@@ -177,6 +178,7 @@ constexpr OptDef kOptDefs[OPT_COUNT] = {
     {OPT_PAIR128_CAP, "pair128_slices", 0, "K slices of a dQ tile in the 128 x 128 backward pair: 0 = the rule of pair128_plan, else that many (A/B)"},
     {OPT_NL128_MIN_TILES, "nl128_min_tiles", 32, "fewest 128 x 128 tiles for the 128-tile one-pass forward (32 against 128, step us: 512 x 2048 44.1 -> 40.7, 768 x 2048 49.7 -> 42.5, 1024 x 1024 47.3 -> 43.5, 256 x 4096 / 192 x 4096 / 256 x 2048 level)"},
     {OPT_P16_STAGED, "p16_staged", 1, "one-pass forward on the 256 x 256 kernel: the fp16 numerators leave through the per-wave LDS patch (64-byte pieces of 16 rows per store instruction instead of 32-byte pieces of 32 rows; bit-identical): 1 = except where the row pitch of G is a multiple of 128 KiB (forward us, arms alternating, profiles/r06_p16_staged_ab.txt: 8192^2 155.4 -> 147.8, 4096 x 8192 83.2 -> 79.3, 4096 x 16384 153 -> 146 and its step 390 -> 372; at 65536 columns the forward gains nothing and the step of 8192 x 65536 LOSES 100 us of 2880), 2 = always, 0 = never"},
+    {OPT_SMALL_SIM, "small_sim", 1, "sim launch of the batch-32 step (B <= 32, fp32 q, 256-deep K chunks: sim_small.h): 1 = one wave per 16 x 16 tile and K chunk, whole-line loads rounded into a wave-private LDS patch, no barrier (bit-identical to the engine; 32 x 256 x 768 step 9.19 -> 8.29 us); 0 = the GEMM engine (tile 5); A/B only: 2 = fp32 straight into fragment registers, no LDS (8.52 us), 3 / 4 = forms 1 / 2 with two waves per workgroup (8.70 / 9.41 us)"},
 };
 constexpr bool opt_table_in_enum_order() {  // (round 6: a row added in the wrong place made two options answer to each other's names)
   for (int i = 0; i < OPT_COUNT; ++i)
@@ -717,6 +719,31 @@ bool wide_sim_ok(int B, int Nc, int d, const FwdPlan& fp) {
 bool wide_bwd_ok(int B, int Nc, int d) {
   return !opt(OPT_NO_WIDE_BWD) && !opt(OPT_NO_SKINNY) && force_tile() < 0 && !unfused_bwd() && d >= 4096 && d % 64 == 0 && B <= SK_MAXB &&
          B % 32 == 0 && Nc % 8 == 0 && Nc >= 64 && Nc <= 1536 && (double)Nc * d < 4.0e9;
+}
+
+// The barrier-free sim launch (sim_small.h) takes the short-row plan's tile 5 where every K chunk is one whole 256-deep step of a
+// wave: B <= 32, d a multiple of 256, kchunk == 256 (so not the single-slab plan above 768 columns, whose one chunk is all of d: a
+// wave would chain d / 32 MFMAs behind 2 x 16 x d x 4 bytes of loads -- it stays on the engine).  Shapes it takes are the ones it was
+// measured at (profiles/small_sim_ab.txt): d = 768 and 1024, up to 768 columns.
+bool small_sim_ok(int B, int Nc, int d, const FwdPlan& fp) {
+  return opt(OPT_SMALL_SIM) != 0 && force_tile() < 0 && fp.short_rows && fp.tile == 5 && B <= 32 && fp.kchunk == SMS_KC && d % SMS_KC == 0 &&
+         d >= 768 && d <= 1024 && Nc <= 768 && fp.splits * SMS_KC == d;
+}
+int launch_sim_small(bool b_f32, const GemmArgs& a, const EpiSim& epi, int splits, hipStream_t st) {
+  const int v = opt(OPT_SMALL_SIM);
+  const int form = (v == 2 || v == 4) ? SS_REG : SS_PATCH, wpg = (v == 3 || v == 4) ? 2 : 1;
+  const int nrt = cdiv(a.M, 16), nct = cdiv(a.N, 16), total = nrt * nct * splits;
+  const dim3 grid(cdiv(total, wpg)), block(64 * wpg);
+  const size_t lds = sim_small_lds(form, b_f32, wpg);
+  if (form == SS_REG) {
+    if (b_f32) hipLaunchKernelGGL((sim_small_kernel<true, SS_REG>), grid, block, lds, st, a, epi, nrt, nct, total);
+    else hipLaunchKernelGGL((sim_small_kernel<false, SS_REG>), grid, block, lds, st, a, epi, nrt, nct, total);
+  } else {
+    if (b_f32) hipLaunchKernelGGL((sim_small_kernel<true, SS_PATCH>), grid, block, lds, st, a, epi, nrt, nct, total);
+    else hipLaunchKernelGGL((sim_small_kernel<false, SS_PATCH>), grid, block, lds, st, a, epi, nrt, nct, total);
+  }
+  HIP_TRY(hipGetLastError());
+  return DPRHOT_OK;
 }
 
 // the loss launch of the no-logits forward -- or, inside the one-call step, a note for launch_dq
@@ -1494,6 +1521,7 @@ int dprhot_sim_stats_f32(const float* q, const float* c, dprhot_bf16* Qb, dprhot
     EpiSim epi{reinterpret_cast<float*>(ws + wl.logits), colmask, B, Nc, inv_T, nullptr, nullptr, nullptr, 0, nullptr,
                reinterpret_cast<unsigned long long*>(ws + wl.header), 2, (size_t)B * Nc};
     epi = with_packed_mask(epi);
+    if (small_sim_ok(B, Nc, d, fp)) return launch_sim_small(c != nullptr, a, epi, fp.splits, (hipStream_t)stream);
     return c ? launch_sim_f32<true, true>(fp.tile, a, epi, fp.splits, (hipStream_t)stream)
              : launch_sim_f32<true, false>(fp.tile, a, epi, fp.splits, (hipStream_t)stream);
   }

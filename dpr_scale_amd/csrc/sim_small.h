@@ -1,0 +1,161 @@
+// sim_small.h -- the similarity launch of the latency-bound training step (B <= 32 query rows, fp32 q, K-major operands,
+// split-K slabs of partial logits: fwd_plan's short rows on tile 5) without the GEMM engine's machinery.
+//
+// At these shapes every workgroup of gemm_tile has ONE K step: its double buffer, its register stages, the hop of both operands
+// through a workgroup-shared LDS image and the two barriers around it serve a loop that runs once, on 24 of 256 CUs.  Here one
+// wave owns one 16 x 16 output tile of one 256-deep K chunk and shares nothing: no barrier, no workgroup-shared LDS, 96 waves at
+// 32 x 256 x 768 instead of 24 workgroups, all of their first (and only) trips to memory side by side.
+//
+// Arithmetic is the engine's bit for bit: the same v_cvt_pk_bf16_f32 of both operands, the same v_mfma_f32_16x16x32_bf16 with
+// the operand placement of load_frag<..., KMAJOR> (lane (g, i) holds row / column i, k = kk * 32 + g * 8 .. + 7), kk ascending
+// inside the chunk into one accumulator, chunks never split between waves.  The slabs, Qb and Cb hold the bits the engine writes.
+//
+// How fp32 reaches the fragment registers (FORM), both kept for the A/B (option small_sim; step of 32 x 256 x 768 on the ten-step
+// graph, engine 9.19 us):
+//   SS_PATCH whole-line loads (8 rows x 128 B per instruction) rounded into a WAVE-PRIVATE bf16 patch in LDS (the engine's
+//            BK = 256 swizzle), then the wave's own fragment reads: program order within the wave is all the synchronisation.
+//            8.29 us: the form the launch takes.
+//   SS_REG   straight to registers in fragment shape: each lane loads its own 32 contiguous bytes per kk (2 x dwordx4).  No LDS
+//            at all, but an instruction touches 16 lines and half of each: 8.52 us.
+// One wave per workgroup; two (the two row tiles of one column tile and chunk) measured 8.70 / 9.41 us.
+// Every load of the chunk is issued back to back before anything looks at a loaded value; the waits the compiler places are then
+// counted vmcnt(N) in issue order (plain loads: hipcc counts them itself, nothing here is hand-counted), so the conversions and
+// the MFMA chain follow the data in.  The mask byte is fetched first, as EpiSim::begin does.
+#pragma once
+#include "gemm_bf16.h"
+
+namespace dprhot {
+
+constexpr int SS_REG = 1, SS_PATCH = 2;
+constexpr int SMS_KC = 256;         // K chunk of a wave (tile 5's BK): 8 MFMA steps
+constexpr int SMS_KK = SMS_KC / 32;
+constexpr int SMS_MAXW = 2;         // most waves per workgroup
+constexpr int SMS_PATCH = 16 * SMS_KC;  // bf16 elements of one operand's patch [16 rows][256 k]
+
+inline size_t sim_small_lds(int form, bool b_f32, int wpg) {
+  return form == SS_PATCH ? (size_t)wpg * SMS_PATCH * 2 * (b_f32 ? 2 : 1) : 0;
+}
+
+__device__ __forceinline__ bf16x8 sms_round(const float4& a, const float4& b) {
+  const uint4 v = make_uint4(cvt_pk_bf16(a.x, a.y), cvt_pk_bf16(a.z, a.w), cvt_pk_bf16(b.x, b.y), cvt_pk_bf16(b.z, b.w));
+  return __builtin_bit_cast(bf16x8, v);
+}
+
+__device__ __forceinline__ void sms_patch_store(const float4 (&raw)[2 * SMS_KK], uint16_t* T, int lane) {
+#pragma unroll
+  for (int j = 0; j < 2 * SMS_KK; ++j) {
+    const int row = (j & 1) * 8 + (lane >> 3), ch = (j >> 1) * 4 + ((lane & 7) >> 1);  // 16-byte chunk of the row
+    const uint2 v = make_uint2(cvt_pk_bf16(raw[j].x, raw[j].y), cvt_pk_bf16(raw[j].z, raw[j].w));
+    *reinterpret_cast<uint2*>(T + row * SMS_KC + kswz<SMS_KC>(row, ch) * 8 + (lane & 1) * 4) = v;
+  }
+}
+__device__ __forceinline__ bf16x8 sms_patch_frag(const uint16_t* T, int kk, int lane) {
+  const int i = lane & 15, g = lane >> 4;
+  return *reinterpret_cast<const bf16x8*>(T + i * SMS_KC + kswz<SMS_KC>(i, kk * 4 + g) * 8);
+}
+
+// p.kchunk == SMS_KC and p.K % SMS_KC == 0 (the launch guard): every chunk is whole, nothing lies beyond K.
+// Waves are numbered row tile fastest, then column tile, then K chunk: the waves of one workgroup read the same context rows.
+template <bool B_F32, int FORM>
+__global__ __launch_bounds__(64 * SMS_MAXW) void sim_small_kernel(GemmArgs p, EpiSim epi, int nrt, int nct, int total) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t sms_smem[];
+  const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int wid = blockIdx.x * (blockDim.x >> 6) + wave;
+  if (wid >= total) return;  // (no barrier anywhere below)
+  const int rt = wid % nrt, ct = (wid / nrt) % nct, bz = wid / (nrt * nct);
+  const int m0 = rt * 16, n0 = ct * 16, kbeg = bz * SMS_KC;
+  DPRHOT_TM(0);
+
+  // ---- every global read, back to back: mask byte, then the chunk of both operands
+  const int ncl = min(n0 + i, epi.N - 1);
+  const uint8_t mraw = epi.mask_raw(ncl);
+  const float* const Af = reinterpret_cast<const float*>(p.A);
+  const int arow = min(m0 + i, p.M - 1), brow = min(n0 + i, p.N - 1);
+  bf16x8 af[SMS_KK], bfr[SMS_KK];
+  float4 araw[2 * SMS_KK], braw[2 * SMS_KK];
+  const float* const Bf = reinterpret_cast<const float*>(p.B);
+  if constexpr (FORM == SS_REG) {
+    // lane (g, i): its own 8 floats of row i per kk (2 x 16 bytes); a and b of one kk next to each other, kk ascending
+    const float* const ap = Af + (size_t)arow * p.lda + kbeg + g * 8;
+    const float* const bp = Bf + (size_t)brow * p.ldb + kbeg + g * 8;
+#pragma unroll
+    for (int kk = 0; kk < SMS_KK; ++kk) {
+      araw[2 * kk] = *reinterpret_cast<const float4*>(ap + kk * 32);
+      araw[2 * kk + 1] = *reinterpret_cast<const float4*>(ap + kk * 32 + 4);
+      if constexpr (B_F32) {
+        braw[2 * kk] = *reinterpret_cast<const float4*>(bp + kk * 32);
+        braw[2 * kk + 1] = *reinterpret_cast<const float4*>(bp + kk * 32 + 4);
+      }
+    }
+  } else {
+    // whole lines: instruction j covers rows (j & 1) * 8 + (lane >> 3) of k line j >> 1 (32 floats = one kk), lane & 7 = 16-byte piece
+    const int ar0 = min(m0 + (lane >> 3), p.M - 1), ar1 = min(m0 + 8 + (lane >> 3), p.M - 1);
+    const int br0 = min(n0 + (lane >> 3), p.N - 1), br1 = min(n0 + 8 + (lane >> 3), p.N - 1);
+    const float* const ap[2] = {Af + (size_t)ar0 * p.lda + kbeg + (lane & 7) * 4, Af + (size_t)ar1 * p.lda + kbeg + (lane & 7) * 4};
+    const float* const bp[2] = {Bf + (size_t)br0 * p.ldb + kbeg + (lane & 7) * 4, Bf + (size_t)br1 * p.ldb + kbeg + (lane & 7) * 4};
+#pragma unroll
+    for (int j = 0; j < 2 * SMS_KK; ++j) {
+      araw[j] = *reinterpret_cast<const float4*>(ap[j & 1] + (j >> 1) * 32);
+      if constexpr (B_F32) braw[j] = *reinterpret_cast<const float4*>(bp[j & 1] + (j >> 1) * 32);
+    }
+  }
+  if constexpr (!B_F32) {  // gathered bf16 contexts: the fragments as they lie in memory
+#pragma unroll
+    for (int kk = 0; kk < SMS_KK; ++kk) bfr[kk] = *reinterpret_cast<const bf16x8*>(p.B + (size_t)brow * p.ldb + kbeg + kk * 32 + g * 8);
+  }
+  __builtin_amdgcn_sched_barrier(0);  // nothing above uses a loaded value
+  DPRHOT_TM(1);
+
+  const bool masked = n0 + i >= epi.N || mraw != 0 || epi.mask_pad(ncl);
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+  if constexpr (FORM == SS_REG) {
+#pragma unroll
+    for (int kk = 0; kk < SMS_KK; ++kk) {
+      af[kk] = sms_round(araw[2 * kk], araw[2 * kk + 1]);
+      if constexpr (B_F32) bfr[kk] = sms_round(braw[2 * kk], braw[2 * kk + 1]);
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[kk], bfr[kk], acc, 0, 0, 0);
+    }
+  } else {
+    uint16_t* const Ta = sms_smem + wave * (SMS_PATCH * (B_F32 ? 2 : 1));
+    uint16_t* const Tb = Ta + SMS_PATCH;
+    sms_patch_store(araw, Ta, lane);
+    if constexpr (B_F32) sms_patch_store(braw, Tb, lane);
+    // (wave-private patch: the wave's own reads follow its own writes in program order)
+#pragma unroll
+    for (int kk = 0; kk < SMS_KK; ++kk) {
+      af[kk] = sms_patch_frag(Ta, kk, lane);
+      if constexpr (B_F32) bfr[kk] = sms_patch_frag(Tb, kk, lane);
+    }
+#pragma unroll
+    for (int kk = 0; kk < SMS_KK; ++kk) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[kk], bfr[kk], acc, 0, 0, 0);
+  }
+  DPRHOT_TM(4);
+
+  // ---- the bf16 copies the backward reads: each operand row by exactly one wave per chunk (16-byte pieces, 16 rows x 64 B each)
+  if (p.Acopy != nullptr && ct == 0 && m0 + i < p.M) {
+#pragma unroll
+    for (int kk = 0; kk < SMS_KK; ++kk)
+      *reinterpret_cast<bf16x8*>(p.Acopy + (size_t)(m0 + i) * p.lda + kbeg + kk * 32 + g * 8) = af[kk];
+  }
+  if constexpr (B_F32) {
+    if (p.Bcopy != nullptr && rt == 0 && n0 + i < p.N) {
+#pragma unroll
+      for (int kk = 0; kk < SMS_KK; ++kk)
+        *reinterpret_cast<bf16x8*>(p.Bcopy + (size_t)(n0 + i) * p.ldb + kbeg + kk * 32 + g * 8) = bfr[kk];
+    }
+  }
+  if (epi.zero_words != nullptr && wid == 0 && lane < epi.n_zero) epi.zero_words[lane] = 0ull;
+
+  // ---- EpiSim::finish in its slab form (statistics off): * 1/T, masked columns -> -inf, fp32 partial logits of this chunk
+  float* const S = epi.S + (size_t)bz * epi.slab_stride;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int m = m0 + g * 4 + r;
+    const float v = masked ? -INFINITY : acc[r] * epi.inv_T;
+    if (m < epi.M && n0 + i < epi.N) S[(size_t)m * epi.N + n0 + i] = v;
+  }
+  DPRHOT_TM(6);
+}
+
+}  // namespace dprhot

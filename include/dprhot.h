@@ -53,6 +53,7 @@ const char* dprhot_last_error(void);
  *   sk_fused (1: the few-rows step without its dScores launch from 2^19 scores up | 2: wherever it exists | 0: never)
  *   sk_w8 (1) / sk_sim_w8 (1): eight waves per workgroup in the few-rows backward / sim launch   sk_pair (0): one kind of backward unit
  *   sk_dbg (0; timing experiments only)
+ *   small_sim (1: the batch-32 step's sim launch on csrc/sim_small.h | 0: on the GEMM engine | 2..4: its other forms; same bits from all)
  * Setting one changes the plans of every later call on every thread (workspace sizes included: query them after setting).
  * DPRHOT_E_INVALID for an unknown name. */
 int dprhot_set_option(const char* name, int value);
