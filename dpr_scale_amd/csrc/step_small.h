@@ -18,6 +18,10 @@
 #include "gemm_bf16.h"
 #include "rowwise.h"
 
+// stamps of the timing build (scratch/step_small_stamps.hip; nothing in the library): slot i of workgroup 0 as before, and the same
+// instant in slot i - 8 of the stamping workgroup's own row (the lead does extra stores, an ordinary workgroup does not)
+#define SS_TM(i) do { DPRHOT_TM(i); DPRHOT_TMB(0, (i) - 8); } while (0)
+
 namespace dprhot {
 
 constexpr int SS_ROWS = 32;     // query rows of one row block (rows beyond B are zero)
@@ -124,7 +128,7 @@ __global__ __launch_bounds__(1024) void step_small_kernel(StepSmallArgs p) {
 #pragma unroll
   for (int rb = 0; rb < NRB; ++rb) {
   // ---- all global reads of the block, back to back (nothing is used before the last one is issued) ----
-  DPRHOT_TM(8);
+  SS_TM(8);
   const int row = rb * SS_ROWS + lrow;
   const bool active = row < p.B;
   const int64_t yraw = active ? p.y[row] : (int64_t)-1;
@@ -157,7 +161,7 @@ __global__ __launch_bounds__(1024) void step_small_kernel(StepSmallArgs p) {
   }
 
   // ---- operand tiles -> LDS ----
-  DPRHOT_TM(9);
+  SS_TM(9);
   if (rb > 0) __syncthreads();  // the previous block's readers of Gs / Qs / red are done
   if (tr < TC) *reinterpret_cast<uint4*>(Qs + lrow * TS + tr * 8) = qreg;
   if (rb == 0) {
@@ -169,7 +173,7 @@ __global__ __launch_bounds__(1024) void step_small_kernel(StepSmallArgs p) {
   }
 
   // ---- row softmax (32 lanes per row: DPP over 16, one lane exchange across the two halves), loss, G ----
-  DPRHOT_TM(10);
+  SS_TM(10);
   float v[CPT][8];
 #pragma unroll
   for (int k = 0; k < CPT; ++k) {
@@ -184,7 +188,7 @@ __global__ __launch_bounds__(1024) void step_small_kernel(StepSmallArgs p) {
     v[k][0] = ok ? a.x : -INFINITY; v[k][1] = ok ? a.y : -INFINITY; v[k][2] = ok ? a.z : -INFINITY; v[k][3] = ok ? a.w : -INFINITY;
     v[k][4] = ok ? b.x : -INFINITY; v[k][5] = ok ? b.y : -INFINITY; v[k][6] = ok ? b.z : -INFINITY; v[k][7] = ok ? b.w : -INFINITY;
   }
-  DPRHOT_TM(11);
+  SS_TM(11);
   const int yi = active ? (int)(yraw + p.y_offset) : -1;
   float m = -INFINITY;
 #pragma unroll
@@ -253,9 +257,9 @@ __global__ __launch_bounds__(1024) void step_small_kernel(StepSmallArgs p) {
       *reinterpret_cast<uint4*>(Gs + lrow * gs + chunk * 8) = gv;
     }
   }
-  DPRHOT_TM(12);
+  SS_TM(12);
   __syncthreads();
-  DPRHOT_TM(13);
+  SS_TM(13);
   if constexpr (NRB == 1) {  // one block: the loss is complete here, summed under the GEMMs
     if (lead && tid == 0) {
       double tot = 0.0;
@@ -291,7 +295,7 @@ __global__ __launch_bounds__(1024) void step_small_kernel(StepSmallArgs p) {
   }
   __syncthreads();
   // ---- dC_part[0:Nc, n0:n0+TW] += G^T[Nc, 32] x Q[32, TW]: one 16-row block of contexts per wave and round ----
-  DPRHOT_TM(14);
+  SS_TM(14);
   {
     bf16x8 bq[NF];
 #pragma unroll
@@ -387,7 +391,279 @@ __global__ __launch_bounds__(1024) void step_small_kernel(StepSmallArgs p) {
     }
   }
   }  // NRB > 1
-  DPRHOT_TM(15);
+  SS_TM(15);
+}
+
+// ---- the same launch split by role (option small_step_roles; B <= 32, Nc <= 768) ------------------------------------------------
+// dQ of rows 0-15 never touches the softmax of rows 16-31, dC needs neither the C tile nor the dQ slice buffer, and 48 workgroups
+// leave 208 CUs idle: one grid, blockIdx.x picks the role.
+//   dC role, blocks 0 .. d/16 - 1 (first to start): slabs + Q tile, the full softmax, G image, ONE barrier, dC product and stores.
+//                                                   The workgroup of tile 0 is the lead, as in step_small_kernel.
+//   dQ role, one block per (16-row half, QTW columns): its 16 rows of the slabs (waves 0-7: 32 lanes per row, as ever) while waves
+//                                                   8-15 fetch the C tile; G half image, dQ product in 8 K slices, slice sum, store.
+// Every value is formed by the instruction sequence of step_small_kernel -- the softmax below is its text -- so the outputs are the
+// same bits (tests/test_small_step_roles.py).
+inline size_t step_roles_lds(int Nc, int QTW) {
+  const int ncp = (Nc + 31) / 32 * 32, gs = ncp + 8;
+  const size_t dc = (size_t)SS_ROWS * gs * 2 + (size_t)SS_ROWS * 24 * 2 + SS_MAXB * sizeof(float);
+  const size_t dq = (size_t)16 * gs * 2 + (size_t)ncp * (QTW + 8) * 2 + (size_t)8 * 16 * QTW * sizeof(float);
+  return dc > dq ? dc : dq;
+}
+
+// The row softmax of step_small_kernel for the thread's 8 * CPT scores of `row` (32 lanes per row): slabs added in slab order, one
+// exponential per score, G (bf16) into row `lrow` of the LDS image.  Returns the row loss (lane tr == 0 uses it).
+template <int CPT, int NS>
+__device__ __forceinline__ float ss_row_softmax(const StepSmallArgs& p, float4 (&sa)[CPT][NS], float4 (&sb)[CPT][NS], int row, bool active,
+                                                int64_t yraw, int tr, bool lead, uint16_t* Gs_row, int ncp) {
+  const int Nc = p.Nc, cpr = Nc >> 3;
+  float v[CPT][8];
+#pragma unroll
+  for (int k = 0; k < CPT; ++k) {
+    float4 a = sa[k][0], b = sb[k][0];
+#pragma unroll
+    for (int z = 1; z < NS; ++z) {
+      const bool on = z < p.splits;
+      a.x += on ? sa[k][z].x : 0.f; a.y += on ? sa[k][z].y : 0.f; a.z += on ? sa[k][z].z : 0.f; a.w += on ? sa[k][z].w : 0.f;
+      b.x += on ? sb[k][z].x : 0.f; b.y += on ? sb[k][z].y : 0.f; b.z += on ? sb[k][z].z : 0.f; b.w += on ? sb[k][z].w : 0.f;
+    }
+    const bool ok = active && (tr + k * 32) < cpr;
+    v[k][0] = ok ? a.x : -INFINITY; v[k][1] = ok ? a.y : -INFINITY; v[k][2] = ok ? a.z : -INFINITY; v[k][3] = ok ? a.w : -INFINITY;
+    v[k][4] = ok ? b.x : -INFINITY; v[k][5] = ok ? b.y : -INFINITY; v[k][6] = ok ? b.z : -INFINITY; v[k][7] = ok ? b.w : -INFINITY;
+  }
+  const int yi = active ? (int)(yraw + p.y_offset) : -1;
+  float m = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < CPT; ++k)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) m = fmaxf(m, v[k][e]);
+  m = dprhot_row16_max(m);
+  m = fmaxf(m, __shfl_xor(m, 16));
+  float sm = 0.f, gold = 0.f;  // exactly one lane of the row holds the gold column
+#pragma unroll
+  for (int k = 0; k < CPT; ++k) {
+    const int c0 = (tr + k * 32) * 8;
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      if (yi == c0 + e) gold = v[k][e];
+  }
+  float ex[CPT][8];
+  const bool dead = m == -INFINITY;  // a row with every column masked (the reference yields NaN there as well)
+#pragma unroll
+  for (int k = 0; k < CPT; ++k)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      ex[k][e] = dead ? 0.f : __expf(v[k][e] - m);
+      sm += ex[k][e];
+    }
+  sm = dprhot_row16_sum(sm);
+  gold = dprhot_row16_sum(gold);
+  sm += __shfl_xor(sm, 16);
+  gold += __shfl_xor(gold, 16);
+  const float lse = m + logf(sm);
+  const float inv_sm = 1.0f / sm;  // sm = 0 (dead row): inf * 0 = NaN, like exp(v - lse) with lse = NaN
+  const float l = active ? lse - gold : 0.f;
+  if (tr == 0 && lead && active) {
+    if (p.row_lse) p.row_lse[row] = lse;
+    if (p.row_loss) p.row_loss[row] = l;
+  }
+#pragma unroll
+  for (int k = 0; k < CPT; ++k) {
+    const int chunk = tr + k * 32;
+    if (chunk * 8 < ncp) {
+      uint4 gv = make_uint4(0u, 0u, 0u, 0u);
+      if (active && chunk < cpr) {
+        const int c0 = chunk * 8;
+        float gg[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          float pr = ex[k][e] * inv_sm;
+          if (c0 + e == yi) pr -= 1.0f;
+          gg[e] = pr * p.grad_scale;
+        }
+        gv = make_uint4(pk_bf16(gg[0], gg[1]), pk_bf16(gg[2], gg[3]), pk_bf16(gg[4], gg[5]), pk_bf16(gg[6], gg[7]));
+        if (lead) {
+          if (p.G != nullptr) *reinterpret_cast<uint4*>(p.G + (size_t)row * Nc + c0) = gv;
+          if (p.S_out != nullptr) {
+            float* dst = p.S_out + (size_t)row * Nc + c0;
+            *reinterpret_cast<float4*>(dst) = make_float4(v[k][0], v[k][1], v[k][2], v[k][3]);
+            *reinterpret_cast<float4*>(dst + 4) = make_float4(v[k][4], v[k][5], v[k][6], v[k][7]);
+          }
+        }
+      }
+      *reinterpret_cast<uint4*>(Gs_row + chunk * 8) = gv;
+    }
+  }
+  return l;
+}
+
+// the thread's chunks of every slab, issued back to back on valid addresses (absent slabs re-read slab 0: step_small_kernel)
+template <int CPT, int NS>
+__device__ __forceinline__ void ss_load_slabs(const StepSmallArgs& p, float4 (&sa)[CPT][NS], float4 (&sb)[CPT][NS], int row, bool active, int tr) {
+  const int Nc = p.Nc, cpr = Nc >> 3;
+#pragma unroll
+  for (int k = 0; k < CPT; ++k) {
+    const int chunk = tr + k * 32;
+    const bool ok = active && chunk < cpr;
+    const float* src = p.slabs + (ok ? (size_t)row * Nc + (size_t)chunk * 8 : (size_t)0);
+#pragma unroll
+    for (int z = 0; z < NS; ++z) {
+      const float* sz = src + (z < p.splits ? (size_t)z * p.slab_stride : (size_t)0);
+      sa[k][z] = *reinterpret_cast<const float4*>(sz);
+      sb[k][z] = *reinterpret_cast<const float4*>(sz + 4);
+    }
+  }
+}
+
+// CPT, NS: as in step_small_kernel (CPT <= 3).  QTW: columns of d per dQ workgroup (16 or 32; d % QTW == 0).
+// Grid: d / 16 dC blocks, then 2 * d / QTW dQ blocks.
+template <int CPT, int NS, int QTW>
+__global__ __launch_bounds__(1024) void step_small_kernel_roles(StepSmallArgs p) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t ss_smem[];
+  constexpr int TW = 16, TS = TW + 8, TC = TW / 8;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int Nc = p.Nc;
+  const int ncp = (Nc + 31) / 32 * 32, gs = ncp + 8;
+  const int lrow = tid >> 5, tr = tid & 31;
+  const float dsc = p.d_scale ? *p.d_scale : 1.0f;
+  const float sc = p.h_scale * dsc;
+  const int i = lane & 15, g = lane >> 4;
+  const int ndc = p.d / TW;  // dC blocks
+  uint16_t* const Gs = ss_smem;  // [32][gs] (dC role) / [16][gs] (dQ role)  G, row-major
+
+  if ((int)blockIdx.x < ndc) {
+    // ---------------- dC role: dC_part[0:Nc, n0:n0+16] = G^T x Q[:, n0:n0+16] ----------------
+    // the XCD-aware tile mapping of step_small_kernel (linear ids are dealt round-robin to the 8 XCDs)
+    const int tile = (ndc % 8 == 0) ? ((int)blockIdx.x % 8) * (ndc / 8) + (int)blockIdx.x / 8 : (int)blockIdx.x;
+    const int n0 = tile * TW;
+    const bool lead = tile == 0;
+    uint16_t* const Qs = Gs + SS_ROWS * gs;                           // [32][TS]  Q[:, n0:n0+16]
+    float* const s_rl = reinterpret_cast<float*>(Qs + SS_ROWS * TS);  // [32] row losses
+    DPRHOT_TMB(1, 0);
+    const int row = lrow;
+    const bool active = row < p.B;
+    const int64_t yraw = active ? p.y[row] : (int64_t)-1;
+    uint4 qreg = make_uint4(0u, 0u, 0u, 0u);
+    if (active && tr < TC) qreg = *reinterpret_cast<const uint4*>(p.Qb + (size_t)row * p.d + n0 + tr * 8);
+    float4 sa[CPT][NS], sb[CPT][NS];
+    ss_load_slabs<CPT, NS>(p, sa, sb, row, active, tr);
+    DPRHOT_TMB(1, 1);
+    if (tr < TC) *reinterpret_cast<uint4*>(Qs + lrow * TS + tr * 8) = qreg;
+    const float l = ss_row_softmax<CPT, NS>(p, sa, sb, row, active, yraw, tr, lead, Gs + lrow * gs, ncp);
+    if (tr == 0) s_rl[lrow] = l;
+    DPRHOT_TMB(1, 2);
+    __syncthreads();
+    DPRHOT_TMB(1, 3);
+    const bool stamp = lead && p.stamp_period > 0;  // column 0 of d belongs to the lead
+    if (lead) {                                     // workgroup-uniform
+      if (tid == 0) {
+        double tot = 0.0;
+        for (int r = 0; r < p.B; ++r) tot += (double)s_rl[r];
+        p.loss_sum[0] = (float)tot * p.loss_scale;
+        s_rl[0] = (float)tot * p.loss_scale;  // (row losses are no longer needed) for the stamp below
+      }
+      if (stamp) __syncthreads();  // only the stamping launch of the packed step pays this second barrier
+    }
+    const bf16x8 bq = ss_tr_frag(Qs, TS, 0, 0, lane);
+    float* out = p.dC + (size_t)(wave * 16 + g * 4) * p.d + n0 + i;
+    const size_t step = (size_t)256 * p.d;
+#pragma unroll
+    for (int it = 0; it < CPT; ++it) {  // Nc <= 256 * CPT rows, 256 per round of the sixteen waves
+      const int j0 = wave * 16 + it * 256;
+      if (j0 < Nc) {
+        const bf16x8 af = ss_tr_frag(Gs, gs, 0, j0, lane);  // A(m = context j0 + i, k = query row) = G[k][m]
+        const f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bq, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        float* o = out;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          if (j0 + g * 4 + r < Nc) {
+            float vv = acc[r] * sc;
+            if (i == 0 && stamp && (j0 + g * 4 + r) % p.stamp_period == p.stamp_row) vv = s_rl[0];
+            o[0] = vv;
+          }
+          o += p.d;
+        }
+      }
+      out += step;
+    }
+    DPRHOT_TMB(1, 4);
+    return;
+  }
+
+  // ---------------- dQ role: dQ[r0:r0+16, n0:n0+QTW] = G[r0:r0+16, :] x C[:, n0:n0+QTW] ----------------
+  constexpr int QTS = QTW + 8, QTC = QTW / 8, NF = QTW / 16;
+  constexpr int CUQ = (256 * CPT * QTC + 511) / 512;  // C-tile chunks per thread of waves 8-15
+  const int u = (int)blockIdx.x - ndc, nqt = p.d / QTW;
+  // both halves of a tile, and the tiles that share the 128-byte lines of C rows, in the XCD of the dC blocks of the same columns
+  int qt, half;
+  if (ndc % 8 == 0 && nqt % 8 == 0) {
+    const int per = nqt / 8;
+    qt = (u % 8) * per + (u / 8) % per;
+    half = (u / 8) / per;
+  } else {
+    qt = u % nqt;
+    half = u / nqt;
+  }
+  const int n0 = qt * QTW, r0 = half * 16;
+  if (r0 >= p.B) return;  // (fewer rows than one half: nothing of dQ is this block's to write)
+  uint16_t* const Cs = Gs + 16 * gs;                             // [ncp][QTS]  C[:, n0:n0+QTW]
+  float* const red = reinterpret_cast<float*>(Cs + ncp * QTS);   // [8][16][QTW] dQ partial sums
+  DPRHOT_TMB(2, 0);
+  if (tid < 512) {  // waves 0-7: the softmax of the half's 16 rows
+    const int row = r0 + lrow;
+    const bool active = row < p.B;
+    const int64_t yraw = active ? p.y[row] : (int64_t)-1;
+    float4 sa[CPT][NS], sb[CPT][NS];
+    ss_load_slabs<CPT, NS>(p, sa, sb, row, active, tr);
+    DPRHOT_TMB(2, 1);
+    (void)ss_row_softmax<CPT, NS>(p, sa, sb, row, active, yraw, tr, false, Gs + lrow * gs, ncp);
+  } else {  // waves 8-15: the C tile
+    const int t2 = tid - 512;
+    uint4 creg[CUQ];
+#pragma unroll
+    for (int c = 0; c < CUQ; ++c) {
+      const int q = t2 + c * 512, j = q / QTC, cc = q % QTC;
+      creg[c] = make_uint4(0u, 0u, 0u, 0u);
+      if (j < Nc) creg[c] = *reinterpret_cast<const uint4*>(p.Cb + (size_t)j * p.d + n0 + cc * 8);
+    }
+#pragma unroll
+    for (int c = 0; c < CUQ; ++c) {
+      const int q = t2 + c * 512, j = q / QTC, cc = q % QTC;
+      if (j < ncp) *reinterpret_cast<uint4*>(Cs + j * QTS + cc * 8) = creg[c];
+    }
+  }
+  DPRHOT_TMB(2, 2);
+  __syncthreads();
+  DPRHOT_TMB(2, 3);
+  {
+    // K slice ks of 8 (kk = ks + 8 t, ascending t); QTW = 32: the wave pair of a slice takes one 16-column fragment each
+    const int ks = NF == 2 ? wave >> 1 : wave, b = NF == 2 ? wave & 1 : 0;
+    if (ks < 8) {
+      f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int t = 0; t < CPT; ++t) {
+        const int kk = ks + t * 8;
+        if (kk * 32 < ncp) {
+          const bf16x8 af = *reinterpret_cast<const bf16x8*>(Gs + i * gs + kk * 32 + g * 8);
+          const bf16x8 bfr = ss_tr_frag(Cs, QTS, kk * 32, b * 16, lane);
+          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfr, acc, 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[(ks * 16 + g * 4 + r) * QTW + b * 16 + i] = acc[r];
+    }
+  }
+  __syncthreads();
+  DPRHOT_TMB(2, 4);
+  if (tid < 16 * QTW) {  // add the 8 K slices in order
+    const int e = tid, r = e / QTW, ccol = e - r * QTW;
+    if (r0 + r < p.B) {
+      float s = red[e];
+#pragma unroll
+      for (int k = 1; k < 8; ++k) s += red[k * 16 * QTW + e];
+      p.dQ[(size_t)(r0 + r) * p.d + n0 + ccol] = s * sc;
+    }
+  }
+  DPRHOT_TMB(2, 5);
 }
 
 }  // namespace dprhot

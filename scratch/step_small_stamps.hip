@@ -1,0 +1,84 @@
+// experiment: per-workgroup wall-clock stamps (10 ns ticks) of the batch-32 step's softmax + backward launch, as it is (small_step_roles = 0:
+// step_small_kernel, slots = DPRHOT_TM 8..15) and split by role (1 / 2: step_small_kernel_roles).  Not shipped.
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 scratch/step_small_stamps.hip -o scratch/step_small_stamps
+//   scratch/step_small_stamps [Nc = 256] [d = 768] [small_step_roles = 0] [launches = 41]
+// Prints, per role: workgroup 0 (the lead), a middle one and the last to finish -- start and end since the launch's first stamp and the
+// time between consecutive stamps, each the median over the launches.
+#define DPRHOT_TIMING 1
+#include <hip/hip_runtime.h>
+__device__ unsigned long long g_dprhot_tm[64];
+__device__ unsigned long long g_dprhot_tmb[4 * 4096 * 8];
+#include "../dpr_scale_amd/csrc/dprhot.hip"
+#include <algorithm>
+#include <stdio.h>
+#include <vector>
+#define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); return 1; } } while (0)
+static double med(std::vector<double> v) { std::sort(v.begin(), v.end()); return v.empty() ? 0.0 : v[v.size() / 2]; }
+int main(int argc, char** argv) {
+  const int B = 32, Nc = argc > 1 ? atoi(argv[1]) : 256, d = argc > 2 ? atoi(argv[2]) : 768, roles = argc > 3 ? atoi(argv[3]) : 0;
+  const int launches = argc > 4 ? atoi(argv[4]) : 41;
+  if (dprhot_set_option("small_step_roles", roles)) { printf("%s\n", dprhot_last_error()); return 1; }
+  float *q, *c, *dq, *dc; uint16_t *Qb, *Cb, *G; int64_t* y; float *loss, *lse, *sum; void* ws; size_t wsb;
+  dprhot_workspace_bytes(B, Nc, d, &wsb);
+  CK(hipMalloc(&q, (size_t)B * d * 4)); CK(hipMalloc(&c, (size_t)Nc * d * 4)); CK(hipMalloc(&Qb, (size_t)B * d * 2)); CK(hipMalloc(&Cb, (size_t)Nc * d * 2));
+  CK(hipMalloc(&G, (size_t)B * Nc * 2)); CK(hipMalloc(&dq, (size_t)B * d * 4)); CK(hipMalloc(&dc, (size_t)Nc * d * 4));
+  CK(hipMalloc(&y, B * 8)); CK(hipMalloc(&loss, B * 4)); CK(hipMalloc(&lse, B * 4)); CK(hipMalloc(&sum, 4)); CK(hipMalloc(&ws, wsb));
+  std::vector<float> h((size_t)Nc * d);
+  unsigned s = 12345;
+  for (auto& v : h) { s = s * 1664525u + 1013904223u; v = (((s >> 8) & 0xffff) / 65536.0f - 0.5f) * 0.4f; }
+  CK(hipMemcpy(q, h.data() + 17, (size_t)B * d * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(c, h.data(), (size_t)Nc * d * 4, hipMemcpyHostToDevice));
+  std::vector<int64_t> hy(B); for (int i = 0; i < B; ++i) hy[i] = i * (Nc / B); CK(hipMemcpy(y, hy.data(), B * 8, hipMemcpyHostToDevice));
+  unsigned long long* dptr; CK(hipGetSymbolAddress((void**)&dptr, HIP_SYMBOL(g_dprhot_tmb)));
+  std::vector<unsigned long long> t(4 * 4096 * 8);
+  const char* rname[3] = {"step_small_kernel (both products per workgroup)", "dC role", "dQ role"};
+  const int nst[3] = {8, 5, 6};
+  const char* pname[3][8] = {{"", "issue loads", "tiles->LDS (waits for Q, C)", "slab sum (waits for slabs)", "softmax + G", "barrier", "dQ MFMA + slice store + barrier", "dC MFMA + stores + dQ slice sum"},
+                             {"", "issue loads", "softmax + G (waits for slabs)", "barrier", "dC MFMA + stores", "", "", ""},
+                             {"", "issue loads (waves 0-7)", "softmax + G half (thread 0)", "barrier (C tile of waves 8-15)", "dQ MFMA + slice store + barrier", "slice sum + store", "", ""}};
+  // [role][which workgroup: 0 = wg 0, 1 = middle, 2 = last to finish][column: 0 = start, 1.. = phases, nst = end] -> samples
+  std::vector<double> samp[3][3][10], span, spank[3];
+  int nwg[3] = {0, 0, 0};
+  for (int it = 0; it < launches + 3; ++it) {
+    CK(hipMemset(dptr, 0, t.size() * 8));
+    int rc = dprhot_inbatch_step_f32(q, c, Qb, Cb, B, Nc, d, y, 0, nullptr, 1.f, 1.f / B, 1.f, nullptr, nullptr, loss, lse, sum, G, dq, dc, ws, wsb, nullptr);
+    if (rc) { printf("rc=%d %s\n", rc, dprhot_last_error()); return 1; }
+    CK(hipDeviceSynchronize());
+    CK(hipMemcpy(t.data(), dptr, t.size() * 8, hipMemcpyDeviceToHost));
+    if (it < 3) continue;
+    unsigned long long g0 = ~0ull, g1 = 0;
+    for (int k = 0; k < 3; ++k)
+      for (int b = 0; b < 4096; ++b) { const unsigned long long* r = &t[((size_t)k * 4096 + b) * 8]; if (r[0]) { g0 = std::min(g0, r[0]); if (r[nst[k] - 1]) g1 = std::max(g1, r[nst[k] - 1]); } }
+    if (g1 == 0) { printf("no stamps: did the shape take the small step?\n"); return 1; }
+    span.push_back((g1 - g0) * 0.01);
+    for (int k = 0; k < 3; ++k) {
+      std::vector<int> ids;
+      for (int b = 0; b < 4096; ++b) { const unsigned long long* r = &t[((size_t)k * 4096 + b) * 8]; if (r[0] && r[nst[k] - 1]) ids.push_back(b); }
+      nwg[k] = (int)ids.size();
+      if (ids.empty()) continue;
+      int last = ids[0];
+      for (int b : ids) if (t[((size_t)k * 4096 + b) * 8 + nst[k] - 1] > t[((size_t)k * 4096 + last) * 8 + nst[k] - 1]) last = b;
+      spank[k].push_back((t[((size_t)k * 4096 + last) * 8 + nst[k] - 1] - g0) * 0.01);
+      const int pick[3] = {ids[0], ids[ids.size() / 2], last};
+      for (int w = 0; w < 3; ++w) {
+        const unsigned long long* r = &t[((size_t)k * 4096 + pick[w]) * 8];
+        samp[k][w][0].push_back((r[0] - g0) * 0.01);
+        for (int i = 1; i < nst[k]; ++i) samp[k][w][i].push_back((r[i] - r[i - 1]) * 0.01);
+        samp[k][w][nst[k]].push_back((r[nst[k] - 1] - g0) * 0.01);
+      }
+    }
+  }
+  printf("B=%d Nc=%d d=%d small_step_roles=%d, %d launches; us, medians; time zero = first stamp of the launch\n", B, Nc, d, roles, launches);
+  printf("launch, first stamp -> last stamp: %.2f\n", med(span));
+  const char* wname[3] = {"first workgroup ", "middle workgroup", "last to finish  "};
+  for (int k = 0; k < 3; ++k) {
+    if (!nwg[k]) continue;
+    printf("%s: %d workgroups, its last one ends at %.2f\n", rname[k], nwg[k], med(spank[k]));
+    for (int w = 0; w < 3; ++w) {
+      printf("  %s start %.2f |", wname[w], med(samp[k][w][0]));
+      for (int i = 1; i < nst[k]; ++i) printf(" %s %.2f |", pname[k][i], med(samp[k][w][i]));
+      printf(" end %.2f\n", med(samp[k][w][nst[k]]));
+    }
+  }
+  float hs; CK(hipMemcpy(&hs, sum, 4, hipMemcpyDeviceToHost)); printf("loss_sum %.4f\n", hs);
+  return 0;
+}

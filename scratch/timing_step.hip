@@ -2,6 +2,7 @@
 #define DPRHOT_TIMING 1
 #include <hip/hip_runtime.h>
 __device__ unsigned long long g_dprhot_tm[64];
+__device__ unsigned long long g_dprhot_tmb[4 * 4096 * 8];  // the kernel now stamps per workgroup as well (step_small_stamps.hip reads those)
 #include "../dpr_scale_amd/csrc/dprhot.hip"
 #include <vector>
 #include <stdio.h>
