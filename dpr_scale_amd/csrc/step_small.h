@@ -397,22 +397,29 @@ __global__ __launch_bounds__(1024) void step_small_kernel(StepSmallArgs p) {
 // ---- the same launch split by role (option small_step_roles; B <= 32, Nc <= 768) ------------------------------------------------
 // dQ of rows 0-15 never touches the softmax of rows 16-31, dC needs neither the C tile nor the dQ slice buffer, and 48 workgroups
 // leave 208 CUs idle: one grid, blockIdx.x picks the role.
-//   dC role, blocks 0 .. d/16 - 1 (first to start): slabs + Q tile, the full softmax, G image, ONE barrier, dC product and stores.
-//                                                   The workgroup of tile 0 is the lead, as in step_small_kernel.
+//   dC role, d / 16 blocks (first to start):        slabs + Q tile, the full softmax, G image, ONE barrier, dC product and stores.
 //   dQ role, one block per (16-row half, QTW columns): its 16 rows of the slabs (waves 0-7: 32 lanes per row, as ever) while waves
 //                                                   8-15 fetch the C tile; G half image, dQ product in 8 K slices, slice sum, store.
+//   who writes loss / logsumexp / G / logits:       step_small_kernel_roles (forms 1, 2): the dC workgroup of tile 0, the lead, as in
+//                                                   step_small_kernel -- and it ended the launch 0.36 us behind the other 47.
+//                                                   step_small_kernel_out (form 3): one output workgroup of the same grid that has
+//                                                   no product to do; every dC workgroup is a plain one.
 // Every value is formed by the instruction sequence of step_small_kernel -- the softmax below is its text -- so the outputs are the
-// same bits (tests/test_small_step_roles.py).
+// same bits (tests/test_small_step_roles.py, tests/test_small_step_out.py).
 inline size_t step_roles_lds(int Nc, int QTW) {
   const int ncp = (Nc + 31) / 32 * 32, gs = ncp + 8;
   const size_t dc = (size_t)SS_ROWS * gs * 2 + (size_t)SS_ROWS * 24 * 2 + SS_MAXB * sizeof(float);
   const size_t dq = (size_t)16 * gs * 2 + (size_t)ncp * (QTW + 8) * 2 + (size_t)8 * 16 * QTW * sizeof(float);
-  return dc > dq ? dc : dq;
+  const size_t out = SS_ROWS * sizeof(float);  // the output role keeps the row losses only (never the largest of the three)
+  const size_t m = dc > dq ? dc : dq;
+  return m > out ? m : out;
 }
 
 // The row softmax of step_small_kernel for the thread's 8 * CPT scores of `row` (32 lanes per row): slabs added in slab order, one
 // exponential per score, G (bf16) into row `lrow` of the LDS image.  Returns the row loss (lane tr == 0 uses it).
-template <int CPT, int NS>
+// G_IMAGE = false (the output role: nobody reads its image) drops the LDS store of G and nothing else: the values are formed all
+// the same for the global store.
+template <int CPT, int NS, bool G_IMAGE = true>
 __device__ __forceinline__ float ss_row_softmax(const StepSmallArgs& p, float4 (&sa)[CPT][NS], float4 (&sb)[CPT][NS], int row, bool active,
                                                 int64_t yraw, int tr, bool lead, uint16_t* Gs_row, int ncp) {
   const int Nc = p.Nc, cpr = Nc >> 3;
@@ -490,7 +497,7 @@ __device__ __forceinline__ float ss_row_softmax(const StepSmallArgs& p, float4 (
           }
         }
       }
-      *reinterpret_cast<uint4*>(Gs_row + chunk * 8) = gv;
+      if constexpr (G_IMAGE) *reinterpret_cast<uint4*>(Gs_row + chunk * 8) = gv;
     }
   }
   return l;
@@ -514,11 +521,13 @@ __device__ __forceinline__ void ss_load_slabs(const StepSmallArgs& p, float4 (&s
   }
 }
 
-// CPT, NS: as in step_small_kernel (CPT <= 3).  QTW: columns of d per dQ workgroup (16 or 32; d % QTW == 0).
-// Grid: d / 16 dC blocks, then 2 * d / QTW dQ blocks.
-template <int CPT, int NS, int QTW>
-__global__ __launch_bounds__(1024) void step_small_kernel_roles(StepSmallArgs p) {
-  extern __shared__ __attribute__((aligned(16))) uint16_t ss_smem[];
+// ---- the role bodies (step_small_kernel_roles and step_small_kernel_out call the same text) ----
+
+// dC role: dC_part[0:Nc, n0:n0+16] = G^T x Q[:, n0:n0+16] for column tile `tile`.  LEAD: the workgroup of tile 0 also writes the
+// loss / logsumexp / G / logits and, in the stamping launch of the packed step, the loss into its column 0 of dC (forms 1, 2);
+// false: no workgroup of this role does (form 3).
+template <int CPT, int NS, bool LEAD>
+__device__ __forceinline__ void ss_role_dc(const StepSmallArgs& p, uint16_t* Gs, int tile) {  // Gs: [32][gs]  G, row-major
   constexpr int TW = 16, TS = TW + 8, TC = TW / 8;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int Nc = p.Nc;
@@ -527,82 +536,74 @@ __global__ __launch_bounds__(1024) void step_small_kernel_roles(StepSmallArgs p)
   const float dsc = p.d_scale ? *p.d_scale : 1.0f;
   const float sc = p.h_scale * dsc;
   const int i = lane & 15, g = lane >> 4;
-  const int ndc = p.d / TW;  // dC blocks
-  uint16_t* const Gs = ss_smem;  // [32][gs] (dC role) / [16][gs] (dQ role)  G, row-major
-
-  if ((int)blockIdx.x < ndc) {
-    // ---------------- dC role: dC_part[0:Nc, n0:n0+16] = G^T x Q[:, n0:n0+16] ----------------
-    // the XCD-aware tile mapping of step_small_kernel (linear ids are dealt round-robin to the 8 XCDs)
-    const int tile = (ndc % 8 == 0) ? ((int)blockIdx.x % 8) * (ndc / 8) + (int)blockIdx.x / 8 : (int)blockIdx.x;
-    const int n0 = tile * TW;
-    const bool lead = tile == 0;
-    uint16_t* const Qs = Gs + SS_ROWS * gs;                           // [32][TS]  Q[:, n0:n0+16]
-    float* const s_rl = reinterpret_cast<float*>(Qs + SS_ROWS * TS);  // [32] row losses
-    DPRHOT_TMB(1, 0);
-    const int row = lrow;
-    const bool active = row < p.B;
-    const int64_t yraw = active ? p.y[row] : (int64_t)-1;
-    uint4 qreg = make_uint4(0u, 0u, 0u, 0u);
-    if (active && tr < TC) qreg = *reinterpret_cast<const uint4*>(p.Qb + (size_t)row * p.d + n0 + tr * 8);
-    float4 sa[CPT][NS], sb[CPT][NS];
-    ss_load_slabs<CPT, NS>(p, sa, sb, row, active, tr);
-    DPRHOT_TMB(1, 1);
-    if (tr < TC) *reinterpret_cast<uint4*>(Qs + lrow * TS + tr * 8) = qreg;
-    const float l = ss_row_softmax<CPT, NS>(p, sa, sb, row, active, yraw, tr, lead, Gs + lrow * gs, ncp);
+  const int n0 = tile * TW;
+  const bool lead = LEAD && tile == 0;
+  uint16_t* const Qs = Gs + SS_ROWS * gs;                           // [32][TS]  Q[:, n0:n0+16]
+  float* const s_rl = reinterpret_cast<float*>(Qs + SS_ROWS * TS);  // [32] row losses
+  DPRHOT_TMB(1, 0);
+  const int row = lrow;
+  const bool active = row < p.B;
+  const int64_t yraw = active ? p.y[row] : (int64_t)-1;
+  uint4 qreg = make_uint4(0u, 0u, 0u, 0u);
+  if (active && tr < TC) qreg = *reinterpret_cast<const uint4*>(p.Qb + (size_t)row * p.d + n0 + tr * 8);
+  float4 sa[CPT][NS], sb[CPT][NS];
+  ss_load_slabs<CPT, NS>(p, sa, sb, row, active, tr);
+  DPRHOT_TMB(1, 1);
+  if (tr < TC) *reinterpret_cast<uint4*>(Qs + lrow * TS + tr * 8) = qreg;
+  const float l = ss_row_softmax<CPT, NS>(p, sa, sb, row, active, yraw, tr, lead, Gs + lrow * gs, ncp);
+  if constexpr (LEAD) {
     if (tr == 0) s_rl[lrow] = l;
-    DPRHOT_TMB(1, 2);
-    __syncthreads();
-    DPRHOT_TMB(1, 3);
-    const bool stamp = lead && p.stamp_period > 0;  // column 0 of d belongs to the lead
-    if (lead) {                                     // workgroup-uniform
-      if (tid == 0) {
-        double tot = 0.0;
-        for (int r = 0; r < p.B; ++r) tot += (double)s_rl[r];
-        p.loss_sum[0] = (float)tot * p.loss_scale;
-        s_rl[0] = (float)tot * p.loss_scale;  // (row losses are no longer needed) for the stamp below
-      }
-      if (stamp) __syncthreads();  // only the stamping launch of the packed step pays this second barrier
-    }
-    const bf16x8 bq = ss_tr_frag(Qs, TS, 0, 0, lane);
-    float* out = p.dC + (size_t)(wave * 16 + g * 4) * p.d + n0 + i;
-    const size_t step = (size_t)256 * p.d;
-#pragma unroll
-    for (int it = 0; it < CPT; ++it) {  // Nc <= 256 * CPT rows, 256 per round of the sixteen waves
-      const int j0 = wave * 16 + it * 256;
-      if (j0 < Nc) {
-        const bf16x8 af = ss_tr_frag(Gs, gs, 0, j0, lane);  // A(m = context j0 + i, k = query row) = G[k][m]
-        const f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bq, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-        float* o = out;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          if (j0 + g * 4 + r < Nc) {
-            float vv = acc[r] * sc;
-            if (i == 0 && stamp && (j0 + g * 4 + r) % p.stamp_period == p.stamp_row) vv = s_rl[0];
-            o[0] = vv;
-          }
-          o += p.d;
-        }
-      }
-      out += step;
-    }
-    DPRHOT_TMB(1, 4);
-    return;
   }
+  DPRHOT_TMB(1, 2);
+  __syncthreads();
+  DPRHOT_TMB(1, 3);
+  const bool stamp = lead && p.stamp_period > 0;  // column 0 of d belongs to the lead
+  if (lead) {                                     // workgroup-uniform
+    if (tid == 0) {
+      double tot = 0.0;
+      for (int r = 0; r < p.B; ++r) tot += (double)s_rl[r];
+      p.loss_sum[0] = (float)tot * p.loss_scale;
+      s_rl[0] = (float)tot * p.loss_scale;  // (row losses are no longer needed) for the stamp below
+    }
+    if (stamp) __syncthreads();  // only the stamping launch of the packed step pays this second barrier
+  }
+  const bf16x8 bq = ss_tr_frag(Qs, TS, 0, 0, lane);
+  float* out = p.dC + (size_t)(wave * 16 + g * 4) * p.d + n0 + i;
+  const size_t step = (size_t)256 * p.d;
+#pragma unroll
+  for (int it = 0; it < CPT; ++it) {  // Nc <= 256 * CPT rows, 256 per round of the sixteen waves
+    const int j0 = wave * 16 + it * 256;
+    if (j0 < Nc) {
+      const bf16x8 af = ss_tr_frag(Gs, gs, 0, j0, lane);  // A(m = context j0 + i, k = query row) = G[k][m]
+      const f32x4 acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bq, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+      float* o = out;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if (j0 + g * 4 + r < Nc) {
+          float vv = acc[r] * sc;
+          if (i == 0 && stamp && (j0 + g * 4 + r) % p.stamp_period == p.stamp_row) vv = s_rl[0];
+          o[0] = vv;
+        }
+        o += p.d;
+      }
+    }
+    out += step;
+  }
+  DPRHOT_TMB(1, 4);
+}
 
-  // ---------------- dQ role: dQ[r0:r0+16, n0:n0+QTW] = G[r0:r0+16, :] x C[:, n0:n0+QTW] ----------------
+// dQ role: dQ[r0:r0+16, n0:n0+QTW] = G[r0:r0+16, :] x C[:, n0:n0+QTW] for column tile qt and 16-row half `half`
+template <int CPT, int NS, int QTW>
+__device__ __forceinline__ void ss_role_dq(const StepSmallArgs& p, uint16_t* Gs, int qt, int half) {  // Gs: [16][gs]  G, row-major
   constexpr int QTS = QTW + 8, QTC = QTW / 8, NF = QTW / 16;
   constexpr int CUQ = (256 * CPT * QTC + 511) / 512;  // C-tile chunks per thread of waves 8-15
-  const int u = (int)blockIdx.x - ndc, nqt = p.d / QTW;
-  // both halves of a tile, and the tiles that share the 128-byte lines of C rows, in the XCD of the dC blocks of the same columns
-  int qt, half;
-  if (ndc % 8 == 0 && nqt % 8 == 0) {
-    const int per = nqt / 8;
-    qt = (u % 8) * per + (u / 8) % per;
-    half = (u / 8) / per;
-  } else {
-    qt = u % nqt;
-    half = u / nqt;
-  }
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int Nc = p.Nc;
+  const int ncp = (Nc + 31) / 32 * 32, gs = ncp + 8;
+  const int lrow = tid >> 5, tr = tid & 31;
+  const float dsc = p.d_scale ? *p.d_scale : 1.0f;
+  const float sc = p.h_scale * dsc;
+  const int i = lane & 15, g = lane >> 4;
   const int n0 = qt * QTW, r0 = half * 16;
   if (r0 >= p.B) return;  // (fewer rows than one half: nothing of dQ is this block's to write)
   uint16_t* const Cs = Gs + 16 * gs;                             // [ncp][QTS]  C[:, n0:n0+QTW]
@@ -664,6 +665,110 @@ __global__ __launch_bounds__(1024) void step_small_kernel_roles(StepSmallArgs p)
     }
   }
   DPRHOT_TMB(2, 5);
+}
+
+// output role (form 3): what the lead did besides its dC tile, and nothing else -- the full softmax with its stores of G, the logits,
+// logsumexp and row loss (ss_row_softmax with lead = true: the same bits), then the loss.  No Q tile, no C tile, no product, and no
+// G image in LDS.
+template <int CPT, int NS>
+__device__ __forceinline__ void ss_role_out(const StepSmallArgs& p, float* s_rl) {  // s_rl: [32] row losses
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int ncp = (p.Nc + 31) / 32 * 32;
+  const int lrow = tid >> 5, tr = tid & 31;
+  DPRHOT_TMB(3, 0);
+  const int row = lrow;
+  const bool active = row < p.B;
+  const int64_t yraw = active ? p.y[row] : (int64_t)-1;
+  float4 sa[CPT][NS], sb[CPT][NS];
+  ss_load_slabs<CPT, NS>(p, sa, sb, row, active, tr);
+  DPRHOT_TMB(3, 1);
+  const float l = ss_row_softmax<CPT, NS, false>(p, sa, sb, row, active, yraw, tr, true, nullptr, ncp);
+  if (tr == 0) s_rl[lrow] = l;
+  DPRHOT_TMB(3, 2);
+  __syncthreads();
+  DPRHOT_TMB(3, 3);
+  if (tid < 64) {  // wave 0
+    // The loss: double accumulator, rows 0 .. B-1 in ascending order, as the lead's walk over s_rl added them -- but that walk was B
+    // dependent trips to LDS (read, convert, add, next address).  ONE read, lane r holding row r and widening it (exact), then the
+    // lane reads -- none depends on the sum, and the guard r < B is a select, not a branch (32 scalar branches in a row cost 0.5 us)
+    // -- and the same B additions in the same order out of registers.  A row beyond B contributes a +0.0 that changes no bit: the
+    // sum starts at +0.0 and an addition in round-to-nearest never yields -0.0 from there.
+    const double mine = (double)s_rl[lane & (SS_ROWS - 1)];
+    const int mlo = __double2loint(mine), mhi = __double2hiint(mine);
+    double x[SS_ROWS];
+#pragma unroll
+    for (int r = 0; r < SS_ROWS; ++r) {
+      const double xr = __hiloint2double(__builtin_amdgcn_readlane(mhi, r), __builtin_amdgcn_readlane(mlo, r));
+      x[r] = r < p.B ? xr : 0.0;
+    }
+    double tot = 0.0;
+#pragma unroll
+    for (int r = 0; r < SS_ROWS; ++r) tot += x[r];
+    if (tid == 0) p.loss_sum[0] = (float)tot * p.loss_scale;
+  }
+  DPRHOT_TMB(3, 4);
+}
+
+// CPT, NS: as in step_small_kernel (CPT <= 3).  QTW: columns of d per dQ workgroup (16 or 32; d % QTW == 0).
+// Grid: d / 16 dC blocks, then 2 * d / QTW dQ blocks.
+template <int CPT, int NS, int QTW>
+__global__ __launch_bounds__(1024) void step_small_kernel_roles(StepSmallArgs p) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t ss_smem[];
+  const int ndc = p.d / 16;  // dC blocks
+  if ((int)blockIdx.x < ndc) {
+    // the XCD-aware tile mapping of step_small_kernel (linear ids are dealt round-robin to the 8 XCDs)
+    const int tile = (ndc % 8 == 0) ? ((int)blockIdx.x % 8) * (ndc / 8) + (int)blockIdx.x / 8 : (int)blockIdx.x;
+    ss_role_dc<CPT, NS, true>(p, ss_smem, tile);
+    return;
+  }
+  const int u = (int)blockIdx.x - ndc, nqt = p.d / QTW;
+  // both halves of a tile, and the tiles that share the 128-byte lines of C rows, in the XCD of the dC blocks of the same columns
+  int qt, half;
+  if (ndc % 8 == 0 && nqt % 8 == 0) {
+    const int per = nqt / 8;
+    qt = (u % 8) * per + (u / 8) % per;
+    half = (u / 8) / per;
+  } else {
+    qt = u % nqt;
+    half = u / nqt;
+  }
+  ss_role_dq<CPT, NS, QTW>(p, ss_smem, qt, half);
+}
+
+// Form 3.  Grid: ONE output block, then d / 16 dC blocks, then 2 * d / QTW dQ blocks.
+// The output block is physical block 0.  Workgroups are handed out in index order, and the roles kernel's stamps show what a late
+// index costs: its dQ blocks, behind the 48 dC blocks, take their first stamp 0.2-0.3 us after block 0 does.  The output block
+// carries a full 32-row softmax -- the longest phase of the launch -- and then a barrier and the loss, so it has to be among the
+// first to start, not behind 96 others; being first costs every other block one place in the queue and nothing else (97 of 256
+// CUs are taken).  It lands in XCD 0, which then holds 13 workgroups on its 32 CUs where the others hold 12.
+// Block index b -> XCD is b % 8, so the tile mappings below are computed from the physical index b, not from b - 1: the blocks of
+// XCD x are b = x + 8 k (x = 0: 8 + 8 k), k = (b - 1) / 8 counts them, and XCD x owns the same contiguous run of column tiles in
+// both roles -- the neighbouring tiles of one 128-byte line of Q / C rows still meet in one L2.
+template <int CPT, int NS, int QTW>
+__global__ __launch_bounds__(1024) void step_small_kernel_out(StepSmallArgs p) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t ss_smem[];
+  const int b = (int)blockIdx.x;
+  if (b == 0) {
+    ss_role_out<CPT, NS>(p, reinterpret_cast<float*>(ss_smem));
+    return;
+  }
+  const int ndc = p.d / 16, nqt = p.d / QTW;
+  if (b <= ndc) {
+    const int tile = (ndc % 8 == 0) ? (b % 8) * (ndc / 8) + (b - 1) / 8 : b - 1;
+    ss_role_dc<CPT, NS, false>(p, ss_smem, tile);
+    return;
+  }
+  const int u = b - 1 - ndc;
+  int qt, half;
+  if (ndc % 8 == 0 && nqt % 8 == 0) {  // b % 8 == (u + 1) % 8, and u / 8 counts the dQ blocks of that XCD
+    const int per = nqt / 8;
+    qt = (b % 8) * per + (u / 8) % per;
+    half = (u / 8) / per;
+  } else {
+    qt = u % nqt;
+    half = u / nqt;
+  }
+  ss_role_dq<CPT, NS, QTW>(p, ss_smem, qt, half);
 }
 
 }  // namespace dprhot

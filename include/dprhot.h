@@ -54,6 +54,8 @@ const char* dprhot_last_error(void);
  *   sk_w8 (1) / sk_sim_w8 (1): eight waves per workgroup in the few-rows backward / sim launch   sk_pair (0): one kind of backward unit
  *   sk_dbg (0; timing experiments only)
  *   small_sim (1: the batch-32 step's sim launch on csrc/sim_small.h | 0: on the GEMM engine | 2..4: its other forms; same bits from all)
+ *   small_step_roles (3: the batch-32 step's softmax + backward launch split by role, outputs from a workgroup of their own |
+ *                     2: outputs from the dC workgroup of tile 0 | 1: 2 with 16-column dQ tiles | 0: unsplit; same bits from all)
  * Setting one changes the plans of every later call on every thread (workspace sizes included: query them after setting).
  * DPRHOT_E_INVALID for an unknown name. */
 int dprhot_set_option(const char* name, int value);

@@ -1,9 +1,10 @@
 """A/B of the batch-32 step's softmax + backward launch: step_small_kernel (small_step_roles = 0) against the role-split forms of
-csrc/step_small.h (1: 16-column dQ tiles, 2: 32-column dQ tiles), in ONE process, arms alternating.
+csrc/step_small.h (1: 16-column dQ tiles, 2: 32-column dQ tiles, 3: form 2 with the outputs written by a workgroup of their own), in ONE
+process, arms alternating.
 Each arm is a HIP graph of ten dprhot_inbatch_step_f32 calls (device-bound, like bench.py --driver graph10); a round times 200 replays
 of every arm in turn with device events.  Prints one line per shape: us per step, min / median / max over the rounds.
 
-  python scratch/small_step_ab.py [--rounds 7] [--arms 0,1,2] [--shapes 32x256x768,32x64x768,...]
+  python scratch/small_step_ab.py [--rounds 7] [--arms 0,1,2,3] [--shapes 32x256x768,32x64x768,...]
 """
 import argparse
 import ctypes
@@ -50,14 +51,14 @@ def build_arm(B, Nc, d, arm, dev):
         for _ in range(10):
             step(ctypes.c_void_p(side.cuda_stream))
     torch.cuda.synchronize()
-    return g, keep, (dQ, dC, ls)
+    return g, keep, (dQ, dC, ls, G, rl, lse)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--replays", type=int, default=200)
-    ap.add_argument("--arms", default="0,1,2")
+    ap.add_argument("--arms", default="0,1,2,3")
     ap.add_argument("--shapes", default=DEFAULT_SHAPES)
     a = ap.parse_args()
     dev = torch.device("cuda", 0)

@@ -1,5 +1,6 @@
 // experiment: per-workgroup wall-clock stamps (10 ns ticks) of the batch-32 step's softmax + backward launch, as it is (small_step_roles = 0:
-// step_small_kernel, slots = DPRHOT_TM 8..15) and split by role (1 / 2: step_small_kernel_roles).  Not shipped.
+// step_small_kernel, slots = DPRHOT_TM 8..15) and split by role (1 / 2: step_small_kernel_roles; 3: step_small_kernel_out, whose output
+// workgroup has a stamp row of its own, DPRHOT_TMB kind 3).  Not shipped.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 scratch/step_small_stamps.hip -o scratch/step_small_stamps
 //   scratch/step_small_stamps [Nc = 256] [d = 768] [small_step_roles = 0] [launches = 41]
 // Prints, per role: workgroup 0 (the lead), a middle one and the last to finish -- start and end since the launch's first stamp and the
@@ -30,14 +31,16 @@ int main(int argc, char** argv) {
   std::vector<int64_t> hy(B); for (int i = 0; i < B; ++i) hy[i] = i * (Nc / B); CK(hipMemcpy(y, hy.data(), B * 8, hipMemcpyHostToDevice));
   unsigned long long* dptr; CK(hipGetSymbolAddress((void**)&dptr, HIP_SYMBOL(g_dprhot_tmb)));
   std::vector<unsigned long long> t(4 * 4096 * 8);
-  const char* rname[3] = {"step_small_kernel (both products per workgroup)", "dC role", "dQ role"};
-  const int nst[3] = {8, 5, 6};
-  const char* pname[3][8] = {{"", "issue loads", "tiles->LDS (waits for Q, C)", "slab sum (waits for slabs)", "softmax + G", "barrier", "dQ MFMA + slice store + barrier", "dC MFMA + stores + dQ slice sum"},
+  const int NK = 4;
+  const char* rname[NK] = {"step_small_kernel (both products per workgroup)", "dC role", "dQ role", "output role"};
+  const int nst[NK] = {8, 5, 6, 5};
+  const char* pname[NK][8] = {{"", "issue loads", "tiles->LDS (waits for Q, C)", "slab sum (waits for slabs)", "softmax + G", "barrier", "dQ MFMA + slice store + barrier", "dC MFMA + stores + dQ slice sum"},
                              {"", "issue loads", "softmax + G (waits for slabs)", "barrier", "dC MFMA + stores", "", "", ""},
-                             {"", "issue loads (waves 0-7)", "softmax + G half (thread 0)", "barrier (C tile of waves 8-15)", "dQ MFMA + slice store + barrier", "slice sum + store", "", ""}};
+                             {"", "issue loads (waves 0-7)", "softmax + G half (thread 0)", "barrier (C tile of waves 8-15)", "dQ MFMA + slice store + barrier", "slice sum + store", "", ""},
+                             {"", "issue loads", "softmax + G / logits / row stores (waits for slabs)", "barrier", "loss sum + store", "", "", ""}};
   // [role][which workgroup: 0 = wg 0, 1 = middle, 2 = last to finish][column: 0 = start, 1.. = phases, nst = end] -> samples
-  std::vector<double> samp[3][3][10], span, spank[3];
-  int nwg[3] = {0, 0, 0};
+  std::vector<double> samp[NK][3][10], span, spank[NK];
+  int nwg[NK] = {0, 0, 0, 0};
   for (int it = 0; it < launches + 3; ++it) {
     CK(hipMemset(dptr, 0, t.size() * 8));
     int rc = dprhot_inbatch_step_f32(q, c, Qb, Cb, B, Nc, d, y, 0, nullptr, 1.f, 1.f / B, 1.f, nullptr, nullptr, loss, lse, sum, G, dq, dc, ws, wsb, nullptr);
@@ -46,11 +49,11 @@ int main(int argc, char** argv) {
     CK(hipMemcpy(t.data(), dptr, t.size() * 8, hipMemcpyDeviceToHost));
     if (it < 3) continue;
     unsigned long long g0 = ~0ull, g1 = 0;
-    for (int k = 0; k < 3; ++k)
+    for (int k = 0; k < NK; ++k)
       for (int b = 0; b < 4096; ++b) { const unsigned long long* r = &t[((size_t)k * 4096 + b) * 8]; if (r[0]) { g0 = std::min(g0, r[0]); if (r[nst[k] - 1]) g1 = std::max(g1, r[nst[k] - 1]); } }
     if (g1 == 0) { printf("no stamps: did the shape take the small step?\n"); return 1; }
     span.push_back((g1 - g0) * 0.01);
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < NK; ++k) {
       std::vector<int> ids;
       for (int b = 0; b < 4096; ++b) { const unsigned long long* r = &t[((size_t)k * 4096 + b) * 8]; if (r[0] && r[nst[k] - 1]) ids.push_back(b); }
       nwg[k] = (int)ids.size();
@@ -70,7 +73,7 @@ int main(int argc, char** argv) {
   printf("B=%d Nc=%d d=%d small_step_roles=%d, %d launches; us, medians; time zero = first stamp of the launch\n", B, Nc, d, roles, launches);
   printf("launch, first stamp -> last stamp: %.2f\n", med(span));
   const char* wname[3] = {"first workgroup ", "middle workgroup", "last to finish  "};
-  for (int k = 0; k < 3; ++k) {
+  for (int k = 0; k < NK; ++k) {
     if (!nwg[k]) continue;
     printf("%s: %d workgroups, its last one ends at %.2f\n", rname[k], nwg[k], med(spank[k]));
     for (int w = 0; w < 3; ++w) {
