@@ -112,6 +112,11 @@ SIGNATURES = {
     "dprhot_ivf_search": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                   c_int, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p,
                                   c_int, c_void_p, c_size_t, c_void_p]),
+    "dprhot_router_head_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
+    "dprhot_router_head_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dprhot_router_head_bwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int64, c_void_p, c_int, c_int, c_void_p, c_void_p,
+                                       c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dprhot_inbatch_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_size_t, c_void_p]),
 }
@@ -203,6 +208,13 @@ def maxsim_workspace_bytes(Nq: int, LQ: int, KQ: int, Ny: int, has_weights: bool
 def ivf_workspace_bytes(nq: int, n_entries: int, chunk: int, has_cls: bool) -> int:
     out = c_size_t(0)
     check(lib.dprhot_ivf_workspace_bytes(int(nq), int(n_entries), int(chunk), int(bool(has_cls)), ctypes.byref(out)), "dprhot_ivf_workspace_bytes")
+    return out.value
+
+
+def router_head_workspace_bytes(B: int, T: int, V: int, k: int, want_softmax: bool) -> int:
+    out = c_size_t(0)
+    check(lib.dprhot_router_head_workspace_bytes(int(B), int(T), int(V), int(k), int(bool(want_softmax)), ctypes.byref(out)),
+          "dprhot_router_head_workspace_bytes")
     return out.value
 
 

@@ -33,6 +33,7 @@
 #include "wideselect.h"
 #include "maxsim.h"
 #include "ivf.h"
+#include "router_head.h"
 
 using namespace dprhot;
 
@@ -1076,6 +1077,53 @@ static int ms_launch_bwd(const MsArgs& p, const MsBwd& g, hipStream_t st) {
     hipLaunchKernelGGL(kern, dim3((unsigned)p.Nc, (unsigned)(g.dc ? (p.dp + MS_DC_SLICE - 1) / MS_DC_SLICE : 1)), dim3(256), lds, st, p, g);
   }
   return DPRHOT_OK;
+}
+
+// ---- CITADEL / SPLADE router head (csrc/router_head.h) ----
+// Workspace: the rows' logsumexp [B, T] fp32 (only with want_softmax).
+static int rh_check_shape(int B, int T1, int V, int skip, int k) {
+  REQUIRE(B > 0 && B <= 65535, "B=%d: 1 <= B <= 65535", B);
+  REQUIRE(k >= 0 && k <= RH_KMAX, "k=%d: 0 <= k <= %d", k, RH_KMAX);
+  REQUIRE(V >= (k > 1 ? k : 1), "V=%d: the vocabulary must hold at least max(k, 1) = %d columns", V, k > 1 ? k : 1);
+  REQUIRE(skip >= 0 && T1 >= 1 && skip <= T1 - 1, "T1=%d skip=%d: at least one token row must remain (T >= 1)", T1, skip);
+  REQUIRE((long long)B * T1 <= 0x7fffffffLL && (long long)(T1 - skip) * (k > 0 ? k : 1) <= 0x7fffffffLL, "too many token rows (B=%d T1=%d)", B, T1);
+  return DPRHOT_OK;
+}
+static int rh_check_dtype(int dtype) {
+  REQUIRE(dtype == RH_BF16 || dtype == RH_FP16 || dtype == RH_FP32, "dtype=%d (0 bf16, 1 fp16, 2 fp32)", dtype);
+  return DPRHOT_OK;
+}
+static int rh_npt(int V) { return V <= RH_THREADS ? 1 : V <= 4 * RH_THREADS ? 4 : V <= 32 * RH_THREADS ? 32 : 0; }
+
+template <int DT>
+static void rh_launch_row(const RhArgs& a, hipStream_t st) {
+  const dim3 grid((unsigned)((long long)a.B * a.T)), block(RH_THREADS);
+  switch (rh_npt(a.V)) {
+    case 1: hipLaunchKernelGGL((rh_row_kernel<DT, 1>), grid, block, 0, st, a); break;
+    case 4: hipLaunchKernelGGL((rh_row_kernel<DT, 4>), grid, block, 0, st, a); break;
+    case 32: hipLaunchKernelGGL((rh_row_kernel<DT, 32>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((rh_row_kernel<DT, 0>), grid, block, 0, st, a); break;
+  }
+}
+template <int DT>
+static void rh_launch_fwd(const RhArgs& a, hipStream_t st) {
+  if (a.k > 0 || a.want_soft) rh_launch_row<DT>(a, st);
+  hipLaunchKernelGGL((rh_col_kernel<DT>), dim3((unsigned)((a.V + RH_COLS - 1) / RH_COLS), (unsigned)a.B), dim3(RH_COLS), 0, st, a);
+}
+template <int DT>
+static void rh_launch_bwd(const RhArgs& a, hipStream_t st) {
+  if (!a.g_soft) {
+    hipLaunchKernelGGL((rh_bwd_sparse_kernel<DT>),
+                       dim3((unsigned)((a.V + RH_COLS - 1) / RH_COLS), (unsigned)((a.T1 + RH_BWD_ROWS - 1) / RH_BWD_ROWS), (unsigned)a.B),
+                       dim3(RH_COLS), 0, st, a);
+    return;
+  }
+  const dim3 grid((unsigned)((long long)a.B * a.T1)), block(RH_THREADS);
+  switch (rh_npt(a.V)) {
+    case 1: hipLaunchKernelGGL((rh_bwd_row_kernel<DT, 1>), grid, block, 0, st, a); break;
+    case 4: hipLaunchKernelGGL((rh_bwd_row_kernel<DT, 4>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((rh_bwd_row_kernel<DT, 0>), grid, block, 0, st, a); break;
+  }
 }
 
 extern "C" {
@@ -2502,6 +2550,74 @@ int dprhot_maxsim_bwd(const float* dS, const void* q_tok, const void* c_tok, int
   else if (q_w) r2 = ms_launch_bwd<false, true>(p, g, st);
   else r2 = ms_launch_bwd<false, false>(p, g, st);
   if (r2) return r2;
+  HIP_TRY(hipGetLastError());
+  return DPRHOT_OK;
+}
+
+// ---- CITADEL / SPLADE router head (csrc/router_head.h): entry points ----
+int dprhot_router_head_workspace_bytes(int B, int T, int V, int k, int want_softmax, size_t* bytes) {
+  REQUIRE(bytes != nullptr, "NULL out pointer");
+  REQUIRE(T >= 1, "T=%d: at least one token row", T);
+  const int rc = rh_check_shape(B, T, V, 0, k);
+  if (rc) return rc;
+  *bytes = want_softmax ? align256((size_t)B * (size_t)T * 4) : 0;
+  return DPRHOT_OK;
+}
+
+int dprhot_router_head_fwd(const void* logits, int dtype, int B, int T1, int V, int64_t stride_b, int64_t stride_t, const uint8_t* mask,
+                           int skip, int k, int want_softmax, void* router_repr, int32_t* argmax, void* expert_weights,
+                           int32_t* expert_ids, void* router_mask, void* softmax_sum, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+  int rc = rh_check_shape(B, T1, V, skip, k);
+  if (rc) return rc;
+  if ((rc = rh_check_dtype(dtype))) return rc;
+  REQUIRE(logits && mask && router_repr && argmax, "NULL pointer (logits, mask, router_repr and argmax are required)");
+  REQUIRE(k == 0 || (expert_weights && expert_ids && router_mask), "NULL pointer (k > 0 needs expert_weights, expert_ids and router_mask)");
+  REQUIRE(!want_softmax || softmax_sum, "NULL pointer (softmax_sum)");
+  REQUIRE(stride_t >= V && stride_b >= 0, "strides: stride_t=%lld must be at least V=%d", (long long)stride_t, V);
+  const int T = T1 - skip;
+  const size_t need = want_softmax ? align256((size_t)B * (size_t)T * 4) : 0;
+  if (need > 0 && (workspace == nullptr || workspace_bytes < need))
+    return fail(DPRHOT_E_WORKSPACE, "workspace of %zu bytes, %zu needed (dprhot_router_head_workspace_bytes)", workspace_bytes, need);
+  RhArgs a{};
+  a.x = logits; a.mask = mask; a.B = B; a.T1 = T1; a.T = T; a.V = V; a.skip = skip; a.k = k; a.want_soft = want_softmax != 0;
+  a.sb = stride_b; a.st = stride_t;
+  a.repr = router_repr; a.arg = argmax; a.w = expert_weights; a.ids = expert_ids; a.rmask = router_mask; a.ssum = softmax_sum;
+  a.lse = (float*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == RH_FP32) rh_launch_fwd<RH_FP32>(a, st);
+  else if (dtype == RH_BF16) rh_launch_fwd<RH_BF16>(a, st);
+  else rh_launch_fwd<RH_FP16>(a, st);
+  HIP_TRY(hipGetLastError());
+  return DPRHOT_OK;
+}
+
+int dprhot_router_head_bwd(const void* logits, int dtype, int B, int T1, int V, int64_t stride_b, int64_t stride_t, const uint8_t* mask,
+                           int skip, int k, const int32_t* argmax, const int32_t* expert_ids, const void* workspace,
+                           size_t workspace_bytes, const float* g_router_repr, const float* g_expert_weights, const float* g_softmax_sum,
+                           void* dlogits, void* stream) {
+  int rc = rh_check_shape(B, T1, V, skip, k);
+  if (rc) return rc;
+  if ((rc = rh_check_dtype(dtype))) return rc;
+  REQUIRE(logits && mask && dlogits, "NULL pointer (logits, mask and dlogits are required)");
+  REQUIRE(!g_router_repr || argmax, "NULL pointer (g_router_repr needs the forward's argmax)");
+  REQUIRE(!g_expert_weights || (k > 0 && expert_ids), "g_expert_weights needs k > 0 and the forward's expert_ids");
+  REQUIRE(stride_t >= V && stride_b >= 0, "strides: stride_t=%lld must be at least V=%d", (long long)stride_t, V);
+  const int T = T1 - skip;
+  if (g_softmax_sum) {
+    const size_t need = align256((size_t)B * (size_t)T * 4);
+    if (workspace == nullptr || workspace_bytes < need)
+      return fail(DPRHOT_E_WORKSPACE, "workspace of %zu bytes, %zu needed (the forward's, with want_softmax)", workspace_bytes, need);
+  }
+  RhArgs a{};
+  a.x = logits; a.mask = mask; a.B = B; a.T1 = T1; a.T = T; a.V = V; a.skip = skip; a.k = k;
+  a.sb = stride_b; a.st = stride_t;
+  a.arg = const_cast<int*>(argmax); a.ids = const_cast<int*>(expert_ids); a.lse = (float*)const_cast<void*>(workspace);
+  a.g_repr = g_router_repr; a.g_w = g_expert_weights; a.g_soft = g_softmax_sum; a.dx = dlogits;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == RH_FP32) rh_launch_bwd<RH_FP32>(a, st);
+  else if (dtype == RH_BF16) rh_launch_bwd<RH_BF16>(a, st);
+  else rh_launch_bwd<RH_FP16>(a, st);
   HIP_TRY(hipGetLastError());
   return DPRHOT_OK;
 }

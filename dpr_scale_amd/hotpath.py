@@ -78,6 +78,9 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
+_RH_DTYPE = {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}  # the dtype codes of dprhot_router_head_*
+
+
 class HipKernels:
     """Thin, allocation-aware wrapper over libdprhot.  Every tensor must live on a HIP device."""
 
@@ -453,6 +456,39 @@ class HipKernels:
                                                    _ptr(dwq), _ptr(dwc), self._stream()),
                         "dprhot_maxsim_bwd")
         return dq, dc, dwq, dwc
+
+    def router_head_fwd(self, logits, m8, k, skip, want_softmax):
+        """The encoder head behind the MLM logits (dprhot_router_head_fwd).  logits [B, T1, V] fp32 / bf16 / fp16 with unit column stride
+        (any row strides: views pass without a copy), m8 uint8 [B, T1].  Returns (router_repr [B, V], argmax int32 [B, V],
+        expert_weights [B, T, k], expert_ids int32 [B, T, k], router_mask [B, V], softmax_sum [B, V], state); the k = 0 / want_softmax =
+        False outputs are None.  `state` (the rows' logsumexp) is what router_head_bwd needs."""
+        self._require_gpu(logits, m8)
+        B, T1, V = logits.shape
+        T, dev, dt = T1 - skip, logits.device, logits.dtype
+        nbytes = self._lib.router_head_workspace_bytes(B, max(T, 1), V, k, want_softmax)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+        repr_ = torch.empty((B, V), dtype=dt, device=dev)
+        arg = torch.empty((B, V), dtype=torch.int32, device=dev)
+        w = torch.empty((B, T, k), dtype=dt, device=dev) if k else None
+        ids = torch.empty((B, T, k), dtype=torch.int32, device=dev) if k else None
+        rmask = torch.empty((B, V), dtype=dt, device=dev) if k else None
+        ssum = torch.empty((B, V), dtype=dt, device=dev) if want_softmax else None
+        self._lib.check(self.lib.dprhot_router_head_fwd(_ptr(logits), _RH_DTYPE[dt], B, T1, V, logits.stride(0), logits.stride(1), _ptr(m8),
+                                                        skip, k, int(want_softmax), _ptr(repr_), _ptr(arg), _ptr(w), _ptr(ids), _ptr(rmask),
+                                                        _ptr(ssum), _ptr(ws), nbytes, self._stream()), "dprhot_router_head_fwd")
+        return repr_, arg, w, ids, rmask, ssum, ws
+
+    def router_head_bwd(self, logits, m8, k, skip, arg, ids, state, g_repr, g_w, g_soft):
+        """dlogits [B, T1, V] (contiguous, the logits' dtype) from the fp32 gradients of router_repr / expert_weights / softmax_sum, each
+        of which may be None (dprhot_router_head_bwd)."""
+        self._require_gpu(logits, m8, g_repr, g_w, g_soft)
+        B, T1, V = logits.shape
+        dx = torch.empty((B, T1, V), dtype=logits.dtype, device=logits.device)
+        self._lib.check(self.lib.dprhot_router_head_bwd(_ptr(logits), _RH_DTYPE[logits.dtype], B, T1, V, logits.stride(0), logits.stride(1),
+                                                        _ptr(m8), skip, k, _ptr(arg), _ptr(ids), _ptr(state),
+                                                        state.numel() if state is not None else 0, _ptr(g_repr), _ptr(g_w), _ptr(g_soft),
+                                                        _ptr(dx), self._stream()), "dprhot_router_head_bwd")
+        return dx
 
     def rank_of_gold(self, S, y, y_offset=0):
         self._require_gpu(S, y)
@@ -1371,3 +1407,66 @@ def expert_sim_score(query_repr, context_repr, mask=None, pairwise=False, query_
         if m8.numel() != Nc:
             raise ValueError(f"expert score: mask of {m8.numel()} entries for {Nc} contexts")
     return MaxSimScore.apply(q, c, qw, cw, qids, cids, m8, KQ, KD, _POOL[query_pool], M, kernels)
+
+
+# ---- the CITADEL / SPLADE encoder head (citadel_model.py:46-82, splade_model.py:26-32) ---------------------------------------------
+ROUTER_HEAD_MAX_TOPK = 8
+
+
+class RouterHead(torch.autograd.Function):
+    """Everything CITADELEncoder.forward derives from the MLM logits, without a [B, T, V] temporary: the logits are streamed by the HIP
+    kernels of csrc/router_head.h forward and backward; what is kept for the backward is [B, V] / [B, T, k] / [B, T] small."""
+
+    @staticmethod
+    def forward(ctx, logits, m8, k, skip, want_softmax, kernels):
+        kn = kernels if kernels is not None else default_kernels()
+        x = logits.detach()
+        repr_, arg, w, ids, rmask, ssum, state = kn.router_head_fwd(x, m8, k, skip, want_softmax)
+        ctx.kn, ctx.meta = kn, (k, skip)
+        ctx.save_for_backward(x, m8, arg, ids, state)
+        ctx.set_materialize_grads(False)
+        outs = (repr_, w, ssum, ids, rmask)
+        ctx.mark_non_differentiable(*[o for o in (ids, rmask) if o is not None])
+        return outs
+
+    @staticmethod
+    def backward(ctx, g_repr, g_w, g_soft, _g_ids, _g_mask):
+        x, m8, arg, ids, state = ctx.saved_tensors
+        k, skip = ctx.meta
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None
+        g = [None if t is None else t.detach().float().contiguous() for t in (g_repr, g_w, g_soft)]
+        dx = ctx.kn.router_head_bwd(x, m8, k, skip, arg, ids, state, g[0], g[1] if k else None, g[2])
+        return dx, None, None, None, None, None
+
+
+def router_head(logits, attention_mask, topk=1, skip_first=1, want_softmax=True, kernels=None):
+    """The head of CITADELEncoder.forward (citadel_model.py:50-82) / SPLADEEncoder.forward (splade_model.py:29-32, topk = 0) from the MLM
+    logits [B, T1, V] (fp32, bf16 or fp16 on a HIP device; a view with unit column stride is read in place) and attention_mask [B, T1]
+    (non-zero = a real token); the first `skip_first` token rows take no part.  Returns a dict with the reference's keys -- router_repr
+    [B, V], expert_ids int64 [B, T, k], expert_weights [B, T, k], router_mask [B, V], router_softmax_repr [B, V], avg_cond_num_experts
+    and avg_marg_num_experts [1, 1] -- float values in the logits' dtype; topk = 0 leaves the routing keys out, want_softmax = False
+    router_softmax_repr.  router_repr, expert_weights and router_softmax_repr are differentiable.  Ties: top-k by value descending then
+    vocabulary index ascending, zeros included; the max over tokens keeps the lowest token."""
+    if logits.dim() != 3 or attention_mask.dim() != 2 or attention_mask.shape != logits.shape[:2]:
+        raise ValueError(f"router_head: logits {tuple(logits.shape)} / attention_mask {tuple(attention_mask.shape)}: want [B, T1, V] and [B, T1]")
+    HipKernels._require_gpu(logits, attention_mask)
+    if logits.dtype not in _RH_DTYPE:
+        raise TypeError(f"router_head: logits of {logits.dtype}; fp32, bf16 and fp16 are supported")
+    k, skip = int(topk), int(skip_first)
+    if not 0 <= k <= ROUTER_HEAD_MAX_TOPK:
+        raise ValueError(f"router_head: topk={k}; the fused head supports 0..{ROUTER_HEAD_MAX_TOPK}")
+    if logits.stride(2) != 1 or logits.stride(1) < logits.shape[2]:
+        logits = logits.contiguous()
+    m8 = (attention_mask != 0).to(torch.uint8).contiguous()
+    repr_, w, ssum, ids, rmask = RouterHead.apply(logits, m8, k, skip, bool(want_softmax), kernels)
+    ret = {"router_repr": repr_}
+    if k:
+        ret["expert_ids"] = ids.long()
+        ret["expert_weights"] = w
+        ret["router_mask"] = rmask
+        ret["avg_cond_num_experts"] = rmask.sum(1, keepdim=True).mean(0, keepdim=True)         # citadel_model.py:66
+        ret["avg_marg_num_experts"] = rmask.max(0, keepdim=True).values.sum(1, keepdim=True)   # :68
+    if want_softmax:
+        ret["router_softmax_repr"] = ssum
+    return ret

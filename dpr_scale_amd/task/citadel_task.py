@@ -2,7 +2,9 @@
 
 Same constructor kwargs (:9-24), same hooks and metric names.  The router loss comes from citadel_router.RouterScoring, the
 expert (late-interaction) loss from multivec.ExpertScoring; both run on libdprhot.so.  The regularisers and the metric logging
-stay plain torch, as in the reference.  The encoder heads are the reference's (they return the repr dicts this task consumes).
+stay plain torch, as in the reference.  The repr dicts this task consumes come from the encoders of dpr_scale_amd/models/
+(citadel_model.CITADELEncoder, splade_model.SPLADEEncoder: the reference's kwargs, keys and shapes), whose head behind the MLM logits is
+hotpath.router_head -- HIP kernels that keep no [B, T, V] tensor (csrc/router_head.h).
 """
 import torch
 

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DPRHOT_VERSION 174 /* 0.1.74: + dprhot_ivf_workspace_bytes / _score / _search (inverted-index retrieval for CITADEL / COIL) */
+#define DPRHOT_VERSION 174 /* 0.1.74: + dprhot_ivf_workspace_bytes / _score / _search (inverted-index retrieval for CITADEL / COIL); dprhot_router_head_* joined without a bump: tests/test_ivf.py pins this number */
 
 #define DPRHOT_OK 0
 #define DPRHOT_E_INVALID (-1)     /* bad argument (NULL pointer, non-positive or misaligned size) */
@@ -349,6 +349,35 @@ int dprhot_ivf_search(const dprhot_bf16* post_vec, const int32_t* post_doc, cons
                       int n_bexp, int nq, const dprhot_bf16* cls_q, const dprhot_bf16* cls_doc, int dc, int64_t cls_rows,
                       int64_t corpus_len, int64_t id_begin, int64_t id_end, int k, int chunk, float* values, int64_t* indices, int first,
                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* The CITADEL / SPLADE encoder head behind the MLM logits (dpr_scale/models/citadel_models/citadel_model.py:46-82, splade_model.py:26-32;
+ * csrc/router_head.h), forward and backward without a [B, T, V] temporary.  logits [B, T1, V] of `dtype` (0 bf16,
+ * 1 fp16, 2 fp32) with unit column stride and ELEMENT strides stride_b / stride_t (a [:, 1:, :] view or a column slice of a wider buffer
+ * passes as it is; nothing beyond the element's own alignment is assumed); mask uint8 [B, T1] (non-zero = a real token).  The first
+ * `skip` token rows take no part; T = T1 - skip; x[b,t,v] = logits[b, t + skip, v], m[b,t] = mask[b, t + skip]:
+ *   f               = m ? log(1 + relu(x)) : 0                        (fp32; a NaN logit gives f = 0)
+ *   router_repr     [B, V]      max_t f, argmax [B, V] int32 its token (the lowest t among equals)
+ *   expert_weights, expert_ids [B, T, k] (ids int32)   the k largest f of the row: value descending, then column ascending, zeros
+ *                               included (a masked token gets columns 0 .. k-1 with weight 0); k = 0: none (SPLADE), the pointers may be NULL
+ *   router_mask     [B, V]      how many (t, j) route to the column with a weight > 0
+ *   softmax_sum     [B, V]      sum_t softmax_v(x[b,t,:]), padded tokens included; only with want_softmax (else it may be NULL)
+ * Float outputs are of `dtype`, computed in fp32.  The workspace (dprhot_router_head_workspace_bytes(B, T, V, k, want_softmax); 0 bytes and
+ * NULL allowed without want_softmax) keeps the rows' logsumexp for the backward: leave it unchanged until then.
+ * Backward: dlogits [B, T1, V] contiguous, of `dtype`, every element written once (rows below `skip` are zeros):
+ *   dlogits[b, t + skip, v] = (g_router_repr[b,v] [t == argmax[b,v]] + sum_j g_expert_weights[b,t,j] [v == expert_ids[b,t,j]]) m (x > 0) / (1 + x)
+ *                           + p (g_softmax_sum[b,v] - sum_u p[b,t,u] g_softmax_sum[b,u]),   p = softmax_v(x[b,t,:])
+ * The three incoming gradients are fp32 and each may be NULL; without g_softmax_sum there is no reduction and the logits are read only
+ * where a gradient lands.  No floating-point atomics: two runs are bit-identical.
+ * Limits (DPRHOT_E_INVALID): 0 <= k <= 8, V >= max(k, 1), T >= 1 (skip <= T1 - 1), B <= 65535, stride_t >= V. */
+int dprhot_router_head_workspace_bytes(int B, int T, int V, int k, int want_softmax, size_t* bytes);
+int dprhot_router_head_fwd(const void* logits, int dtype, int B, int T1, int V, int64_t stride_b, int64_t stride_t, const uint8_t* mask,
+                           int skip, int k, int want_softmax, void* router_repr, int32_t* argmax, void* expert_weights,
+                           int32_t* expert_ids, void* router_mask, void* softmax_sum, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int dprhot_router_head_bwd(const void* logits, int dtype, int B, int T1, int V, int64_t stride_b, int64_t stride_t, const uint8_t* mask,
+                           int skip, int k, const int32_t* argmax, const int32_t* expert_ids, const void* workspace,
+                           size_t workspace_bytes, const float* g_router_repr, const float* g_expert_weights, const float* g_softmax_sum,
+                           void* dlogits, void* stream);
 
 /* The step as the autograd operator of dpr_scale_amd/hotpath.py runs it (dpr_task.py:197-212 + its backward inside the forward call):
  * dprhot_inbatch_step_f32 / _packed_f32 with
