@@ -115,17 +115,43 @@ struct DqPartScope {
     if (e_ != hipSuccess) return fail(DPRHOT_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
-// "dynamic LDS size raised for this kernel" is a per-device fact (one code object per device): one bit per device ordinal
-struct AttrOnce {
-  unsigned long long devs = 0;
-  static int cur() {
+// Every kernel launch of this file: raise the dynamic-LDS limit where needed, launch, read the launch's error.
+// The state is per kernel: Kern is a template argument, so every instantiation of a __global__ template has its own `raised`.  It holds,
+// per device ordinal (one code object per device), the largest dynamic-LDS size raised so far -- a kernel whose LDS grows with the shape
+// (step_small.h) raises the limit again when a larger shape follows a smaller one.  Requests up to 48 KiB need no attribute and cost
+// no host call besides the launch itself (the eager driver of the batch-32 step is host-paced).
+struct LdsRaised {
+  size_t dev[64] = {};
+  size_t& cur() {
     int d = 0;
     (void)hipGetDevice(&d);
-    return d & 63;
+    return dev[d & 63];
   }
-  bool operator!() const { return !((devs >> cur()) & 1ull); }
-  void operator=(bool) { devs |= 1ull << cur(); }  // benign race: idempotent
 };
+// a failure names its kernel, "dprhot::sk_bwd_kernel (73984 bytes of dynamic LDS): invalid argument": the name is cut out of launch's own
+// __PRETTY_FUNCTION__ ("... [Kern = &dprhot::sk_bwd_kernel, Args = <...>]")
+int launch_failed(const char* pretty, size_t lds, hipError_t e) {
+  const char* s = strstr(pretty, "Kern = &");
+  s = s != nullptr ? s + 8 : pretty;
+  const char* end = strstr(s, ", Args");
+  return fail(DPRHOT_E_HIP, "%.*s (%zu bytes of dynamic LDS): %s", end != nullptr ? (int)(end - s) : (int)strlen(s), s, lds, hipGetErrorString(e));
+}
+template <auto Kern, class... Args>
+int launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
+  if (lds > 48 * 1024) {
+    static LdsRaised raised;  // benign race: idempotent
+    size_t& r = raised.cur();
+    if (r < lds) {
+      const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      if (e != hipSuccess) return launch_failed(__PRETTY_FUNCTION__, lds, e);
+      r = lds;
+    }
+  }
+  hipLaunchKernelGGL(Kern, grid, block, lds, st, args...);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return launch_failed(__PRETTY_FUNCTION__, lds, e);
+  return DPRHOT_OK;
+}
 
 #define REQUIRE(cond, ...) \
   do {                     \
@@ -270,17 +296,8 @@ int pick_tile(int M, int N, int K, int splits_hint, int want) {
 
 template <int BM, int BN, int BK, bool AK, bool BKM, bool TR, class Epi, bool AF = false, bool BF = false>
 int launch_one(const GemmArgs& a, const Epi& epi, int splits, hipStream_t st) {
-  auto kern = gemm_bf16_kernel<BM, BN, BK, 2, 2, AK, BKM, TR, Epi, AF, BF>;
-  constexpr size_t lds = gemm_lds_bytes<BM, BN, BK, AK, BKM>();
-  static AttrOnce attr_done;  // benign race: idempotent
-  if (lds > 48 * 1024 && !attr_done) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_done = true;
-  }
   dim3 grid(cdiv(a.N, BN), cdiv(a.M, BM), splits);
-  hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a, epi);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  return launch<gemm_bf16_kernel<BM, BN, BK, 2, 2, AK, BKM, TR, Epi, AF, BF>>(grid, dim3(256), gemm_lds_bytes<BM, BN, BK, AK, BKM>(), st, a, epi);
 }
 
 // persistent (one workgroup per CU walking its tiles with the K pipeline running across tile boundaries) when the
@@ -288,35 +305,19 @@ int launch_one(const GemmArgs& a, const Epi& epi, int splits, hipStream_t st) {
 // drain while its successor on the CU is already loading, a persistent one would have to wait for them
 template <class Epi, bool PERSIST>
 int launch_big(const GemmArgs& a, const Epi& epi, hipStream_t st) {
-  auto kern = gemm256_kernel<Epi, PERSIST>;
-  static AttrOnce attr_done;  // benign race: idempotent
-  if (!attr_done) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g2_lds_total));
-    attr_done = true;
-  }
   const int nbx = cdiv(a.N, G2_B), nby = cdiv(a.M, G2_B);
   const int grid = (!PERSIST || nbx * nby < kNumCU) ? nbx * nby : kNumCU;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G2_THREADS), g2_lds_total, st, a, epi, nbx, nby);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  return launch<gemm256_kernel<Epi, PERSIST>>(dim3((unsigned)grid), dim3(G2_THREADS), g2_lds_total, st, a, epi, nbx, nby);
 }
 
 // SCHED: 4 = four phases of 8 MFMAs per K step, 2 = two phases of 16 (bit-identical; the dScores pass, whose store epilogue delays
 // the first DMA waits of the next tile, is consistently ~4 % faster on the two-phase schedule: 111-114 vs 116-121 us at 8192^2 x 768)
 template <class Epi, int SCHED = 4>
 int launch_g8(const GemmArgs& a, const Epi& epi, hipStream_t st) {
-  auto kern = gemm8p_kernel<Epi, 0, SCHED>;
-  static AttrOnce attr_done;  // benign race: idempotent
-  if (!attr_done) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g8_lds_total));
-    attr_done = true;
-  }
   const int nbx = cdiv(a.N, G2_B), nby = cdiv(a.M, G2_B);
   const bool stores_tile = std::is_same<Epi, Epi8G>::value || std::is_same<Epi, Epi8Store>::value || std::is_same<Epi, Epi8StatsP>::value;
   const int grid = (nbx * nby < kNumCU || (stores_tile && opt(OPT_G8_ONE_TILE) != 0)) ? nbx * nby : kNumCU;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G2_THREADS), g8_lds_total, st, a, epi, nbx, nby);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  return launch<gemm8p_kernel<Epi, 0, SCHED>>(dim3((unsigned)grid), dim3(G2_THREADS), g8_lds_total, st, a, epi, nbx, nby);
 }
 // the inputs every gemm8p.h sim epilogue shares
 Epi8Base g8_base(const dprhot_bf16* Q, int B, int Nc, const int64_t* y, int64_t y_offset, const uint8_t* colmask, float inv_T, float* gold) {
@@ -341,15 +342,7 @@ int launch_gemm(int tile, const GemmArgs& a, const Epi& epi, int splits, hipStre
   if (tile == 0 && opt(OPT_G128_DMA) != 0 && (tr || !needs_tr) && (a.K % 64 == 0 || (!BKM && a.K >= 64 && (!AK || a.K % 8 == 0))) && a.kchunk % 64 == 0 && a.M >= 8 && a.N >= 8 &&
       (double)(AK ? a.M : a.K) * a.lda < 4.0e9 && (double)(BKM ? a.N : a.K) * a.ldb < 4.0e9) {  // (32-bit element offsets inside one K range)
     // the same tile with LDS-DMA staging (gemm128d.h): same images, same fragments, same epilogues
-    auto kern = gemm128d_kernel<AK, BKM, Epi>;
-    static AttrOnce attr_done;
-    if (!attr_done) {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g1_lds_bytes));
-      attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(cdiv(a.N, 128), cdiv(a.M, 128), splits), dim3(256), g1_lds_bytes, st, a, epi);
-    HIP_TRY(hipGetLastError());
-    return DPRHOT_OK;
+    return launch<gemm128d_kernel<AK, BKM, Epi>>(dim3(cdiv(a.N, 128), cdiv(a.M, 128), splits), dim3(256), g1_lds_bytes, st, a, epi);
   }
 #define DPRHOT_TILE_CASE(T, BM, BN, BK_)                                                       \
   case T:                                                                                      \
@@ -389,20 +382,12 @@ int launch_sim_f32(int tile, const GemmArgs& a, const EpiSim& epi, int splits, h
 template <class C1, class C2>
 int launch_pair_one(const GemmArgs& a1, const EpiScaleF32& e1, const GemmArgs& a2, const EpiScaleF32& e2, int splits2,
                     hipStream_t st) {
-  auto kern = gemm_pair_kernel<C1, C2, EpiScaleF32, EpiScaleF32>;
   constexpr size_t lds = C1::lds > C2::lds ? C1::lds : C2::lds;
-  static AttrOnce attr_done;
-  if (lds > 48 * 1024 && !attr_done) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_done = true;
-  }
   const int nbx1 = cdiv(a1.N, C1::BN), nby1 = cdiv(a1.M, C1::BM);
   const int nbx2 = cdiv(a2.N, C2::BN), nby2 = cdiv(a2.M, C2::BM);
   const long blocks = (long)nbx1 * nby1 + (long)nbx2 * nby2 * splits2;
   if (blocks > 0x7fffffffL) return fail(DPRHOT_E_UNSUPPORTED, "grid too large");
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, st, a1, e1, nbx1, nby1, a2, e2, nbx2, nby2);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  return launch<gemm_pair_kernel<C1, C2, EpiScaleF32, EpiScaleF32>>(dim3((unsigned)blocks), dim3(256), lds, st, a1, e1, nbx1, nby1, a2, e2, nbx2, nby2);
 }
 
 template <bool TR>
@@ -737,15 +722,11 @@ int launch_sim_small(bool b_f32, const GemmArgs& a, const EpiSim& epi, int split
   const int nrt = cdiv(a.M, 16), nct = cdiv(a.N, 16), total = nrt * nct * splits;
   const dim3 grid(cdiv(total, wpg)), block(64 * wpg);
   const size_t lds = sim_small_lds(form, b_f32, wpg);
-  if (form == SS_REG) {
-    if (b_f32) hipLaunchKernelGGL((sim_small_kernel<true, SS_REG>), grid, block, lds, st, a, epi, nrt, nct, total);
-    else hipLaunchKernelGGL((sim_small_kernel<false, SS_REG>), grid, block, lds, st, a, epi, nrt, nct, total);
-  } else {
-    if (b_f32) hipLaunchKernelGGL((sim_small_kernel<true, SS_PATCH>), grid, block, lds, st, a, epi, nrt, nct, total);
-    else hipLaunchKernelGGL((sim_small_kernel<false, SS_PATCH>), grid, block, lds, st, a, epi, nrt, nct, total);
-  }
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  if (form == SS_REG)
+    return b_f32 ? launch<sim_small_kernel<true, SS_REG>>(grid, block, lds, st, a, epi, nrt, nct, total)
+                 : launch<sim_small_kernel<false, SS_REG>>(grid, block, lds, st, a, epi, nrt, nct, total);
+  return b_f32 ? launch<sim_small_kernel<true, SS_PATCH>>(grid, block, lds, st, a, epi, nrt, nct, total)
+               : launch<sim_small_kernel<false, SS_PATCH>>(grid, block, lds, st, a, epi, nrt, nct, total);
 }
 
 // the loss launch of the no-logits forward -- or, inside the one-call step, a note for launch_dq
@@ -755,9 +736,15 @@ int launch_loss_sum(const float* src, int n, float scale, float* out, hipStream_
     g_loss_defer.src = src; g_loss_defer.n = n; g_loss_defer.scale = scale; g_loss_defer.out = out;
     return DPRHOT_OK;
   }
-  hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, st, src, n, scale, out);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  return launch<reduce_sum_kernel>(dim3(1), dim3(256), 0, st, src, n, scale, out);
+}
+
+// the row kernel of the one-pass forwards (128 x 128 and 256 x 256 tiles): logsumexp / loss from the strip statistics, and the fp16 numerators
+// rescaled into the bf16 dScores in place
+int launch_lse_p2g(const float* part_m, const float* part_s, int npart, int B, int Nc, const int64_t* y, int64_t y_offset, float grad_scale,
+                   float* row_lse, float* row_loss, dprhot_bf16* G, char* ws, const WsLayout& wl, hipStream_t st) {
+  return launch<g8_lse_p2g_kernel>(dim3((unsigned)B), dim3(256), 0, st, part_m, part_s, npart, reinterpret_cast<const float*>(ws + wl.gold), B, Nc, y,
+                                   y_offset, grad_scale, reinterpret_cast<float*>(ws + wl.lse), row_lse, row_loss, reinterpret_cast<float*>(ws + wl.rloss), G);
 }
 
 // dQ = scale * (slab 0 + slab 1 + ...), in slab order; inside the one-call step the same launch also forms the loss sum (launch_loss_sum)
@@ -766,13 +753,10 @@ int launch_slab_sum(const float* part, int splits, int B, int d, float h_scale, 
   const int blocks = (int)((n4 + 255) / 256 > 1024 ? 1024 : (n4 + 255) / 256);
   if (g_loss_defer.pending) {
     g_loss_defer.pending = false;
-    hipLaunchKernelGGL(splitk_reduce_loss_kernel, dim3(blocks + 1), dim3(256), 0, st, part, splits, n4, h_scale, d_scale, dQ, g_loss_defer.src,
-                       g_loss_defer.n, g_loss_defer.scale, g_loss_defer.out);
-  } else {
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, st, part, splits, n4, h_scale, d_scale, dQ);
+    return launch<splitk_reduce_loss_kernel>(dim3(blocks + 1), dim3(256), 0, st, part, splits, n4, h_scale, d_scale, dQ, g_loss_defer.src,
+                                             g_loss_defer.n, g_loss_defer.scale, g_loss_defer.out);
   }
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  return launch<splitk_reduce_kernel>(dim3(blocks), dim3(256), 0, st, part, splits, n4, h_scale, d_scale, dQ);
 }
 
 int launch_dq(const dprhot_bf16* G, const dprhot_bf16* C, int B, int Nc, int d, float h_scale, const float* d_scale, float* dQ,
@@ -796,54 +780,30 @@ int launch_dq(const dprhot_bf16* G, const dprhot_bf16* C, int B, int Nc, int d, 
 template <int NCH, int COLS, int SLOTS>
 int launch_sk_sim_c(const SkSimArgs& a, int grid, hipStream_t st) {
   const size_t lds = sk_sim_lds();
-  static AttrOnce attr_done[3];  // benign race: idempotent
   if constexpr (COLS == SK_COLS) {
     if (a.q != nullptr && opt(OPT_SK_SIM_PRIV) != 0 && grid <= kNumCU) {
       // wave-private rings, one workgroup per CU (round 5): as many chunks in flight per wave as 160 KiB of LDS hold next to the q block
       constexpr int PS = NCH <= 12 ? 6 : (NCH <= 14 ? 5 : 4);
-      auto kern = sk_simp_kernel<NCH, PS>;
-      const size_t ldsp = sk_simp_lds(NCH, PS);
-      static AttrOnce attr_p;
-      if (!attr_p) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp));
-        attr_p = true;
-      }
-      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), ldsp, st, a);
-      HIP_TRY(hipGetLastError());
-      return DPRHOT_OK;
+      return launch<sk_simp_kernel<NCH, PS>>(dim3((unsigned)grid), dim3(512), sk_simp_lds(NCH, PS), st, a);
     }
-    if (a.q != nullptr && opt(OPT_SK_SIM_W8) != 0) {
-      auto kern = sk_sim_kernel<NCH, true, COLS, SLOTS, 8>;
-      if (!attr_done[2]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_done[2] = true;
-      }
-      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, st, a);
-      HIP_TRY(hipGetLastError());
-      return DPRHOT_OK;
-    }
+    if (a.q != nullptr && opt(OPT_SK_SIM_W8) != 0) return launch<sk_sim_kernel<NCH, true, COLS, SLOTS, 8>>(dim3((unsigned)grid), dim3(512), lds, st, a);
   }
-  if (a.q != nullptr) {
-    auto kern = sk_sim_kernel<NCH, true, COLS, SLOTS>;
-    if (!attr_done[0]) {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      attr_done[0] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(SK_THREADS), lds, st, a);
-  } else {
-    auto kern = sk_sim_kernel<NCH, false, COLS, SLOTS>;
-    if (!attr_done[1]) {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      attr_done[1] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(SK_THREADS), lds, st, a);
-  }
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  if (a.q != nullptr) return launch<sk_sim_kernel<NCH, true, COLS, SLOTS>>(dim3((unsigned)grid), dim3(SK_THREADS), lds, st, a);
+  return launch<sk_sim_kernel<NCH, false, COLS, SLOTS>>(dim3((unsigned)grid), dim3(SK_THREADS), lds, st, a);
 }
 template <int NCH>
 int launch_sk_sim(const SkSimArgs& a, int grid, int scols, hipStream_t st) {
   return scols == SK_COLS ? launch_sk_sim_c<NCH, SK_COLS, SK_SLOTS>(a, grid, st) : launch_sk_sim_c<NCH, SK_SCOLS, 2 * SK_SLOTS>(a, grid, st);
+}
+
+// the backward units of skinny.h (dC tiles next to split-K dQ tiles, `units` workgroups) and the sum of the dQ slabs behind them:
+// the launches sk_step and dprhot_inbatch_bwd share
+int launch_sk_bwd(const SkBwdArgs& b, int units, hipStream_t st) {
+  return launch<sk_bwd_kernel>(dim3((unsigned)units), dim3(SK_THREADS), sk_bwd_lds(), st, b);
+}
+int launch_sk_dq_reduce(const float* part, int nslices, int B, int d, float h_scale, const float* d_scale, float* dQ, hipStream_t st) {
+  const size_t n4 = (size_t)B * d / 4;
+  return launch<sk_dq_reduce_kernel>(dim3((unsigned)((n4 + 63) / 64)), dim3(256), 0, st, part, nslices, n4, h_scale, d_scale, dQ);
 }
 
 int sk_step(const float* q, const dprhot_bf16* Cb, dprhot_bf16* Qb, int B, int Nc, int d, const int64_t* y, int64_t y_offset,
@@ -903,71 +863,39 @@ int sk_step(const float* q, const dprhot_bf16* Cb, dprhot_bf16* Qb, int B, int N
     b.reg_scale = opt(OPT_SK_DC_REGSCALE) != 0 ? 1 : 0;
     b.dq_atomic = dq_atomic ? 1 : 0;
     const size_t lds = sk_bwdf_lds();
-    static AttrOnce attr_done[4];
-    auto launch = [&](auto kern, int slot, int threads) -> int {
-      if (!attr_done[slot]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_done[slot] = true;
-      }
-      if (tail) {
-        b.tail_cnt = tail_cnt;
-        b.nfin = cdiv(B, threads / 256);
-        b.tail_fence = opt(OPT_SK_TAIL) == 2 ? 1 : 0;
-      }
-      hipLaunchKernelGGL(kern, dim3((unsigned)(ndq_pad + ndc + b.nfin)), dim3((unsigned)threads), lds, st, b);
-      return DPRHOT_OK;
-    };
-    static AttrOnce attr_pair[2];
     if (fz.pair) {
       // one kind of unit: (slice of fz.tpu statistics tiles) x (64 columns of d), one workgroup per CU
       b.ksteps = fz.tpu;
       b.nslices = fz.ns;
       const size_t ldsp = sk_bwdp_lds();
-      const unsigned gridp = (unsigned)(fz.ns * (d / SK_QN));
-      if (nts <= 64) {
-        if (!attr_pair[0]) {
-          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(sk_bwdp_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp));
-          attr_pair[0] = true;
-        }
-        hipLaunchKernelGGL(sk_bwdp_kernel<8>, dim3(gridp), dim3(512), ldsp, st, b);
-      } else {
-        if (!attr_pair[1]) {
-          HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(sk_bwdp_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp));
-          attr_pair[1] = true;
-        }
-        hipLaunchKernelGGL(sk_bwdp_kernel<16>, dim3(gridp), dim3(512), ldsp, st, b);
-      }
+      const dim3 gridp((unsigned)(fz.ns * (d / SK_QN)));
+      rc = nts <= 64 ? launch<sk_bwdp_kernel<8>>(gridp, dim3(512), ldsp, st, b) : launch<sk_bwdp_kernel<16>>(gridp, dim3(512), ldsp, st, b);
     } else {
       const bool w8 = opt(OPT_SK_W8) != 0;
-      if (dq_atomic && w8) {  // (eight-wave units only: the form production runs)
-        static AttrOnce attr_at[2];
-        auto launch_at = [&](auto kern, int slot) -> int {
-          if (!attr_at[slot]) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_at[slot] = true;
-          }
-          hipLaunchKernelGGL(kern, dim3((unsigned)(ndq_pad + ndc)), dim3(512), lds, st, b);
-          return DPRHOT_OK;
-        };
-        rc = nts <= 64 ? launch_at(sk_bwdf_kernel<8, 8, true>, 0) : launch_at(sk_bwdf_kernel<16, 8, true>, 1);
-      } else if (nts <= 64) rc = w8 ? launch(sk_bwdf_kernel<8, 8>, 2, 512) : launch(sk_bwdf_kernel<8, 4>, 0, SK_THREADS);
-      else rc = w8 ? launch(sk_bwdf_kernel<16, 8>, 3, 512) : launch(sk_bwdf_kernel<16, 4>, 1, SK_THREADS);
-      if (rc) return rc;
+      const int threads = w8 ? 512 : SK_THREADS;
+      if (tail) {
+        b.tail_cnt = tail_cnt;
+        b.nfin = cdiv(B, threads / 256);
+        b.tail_fence = opt(OPT_SK_TAIL) == 2 ? 1 : 0;
+      }
+      const dim3 grid((unsigned)(ndq_pad + ndc + b.nfin)), block((unsigned)threads);  // (b.nfin == 0 without the finishing role)
+      if (dq_atomic)  // (eight-wave units only: the form production runs)
+        rc = nts <= 64 ? launch<sk_bwdf_kernel<8, 8, true>>(grid, block, lds, st, b) : launch<sk_bwdf_kernel<16, 8, true>>(grid, block, lds, st, b);
+      else if (nts <= 64) rc = w8 ? launch<sk_bwdf_kernel<8, 8>>(grid, block, lds, st, b) : launch<sk_bwdf_kernel<8, 4>>(grid, block, lds, st, b);
+      else rc = w8 ? launch<sk_bwdf_kernel<16, 8>>(grid, block, lds, st, b) : launch<sk_bwdf_kernel<16, 4>>(grid, block, lds, st, b);
     }
-    HIP_TRY(hipGetLastError());
+    if (rc) return rc;
     if (!tail && (opt(OPT_SK_DBG) & 8)) {
       // TIMING EXPERIMENT ONLY (sk_dbg & 8): the plain slab sum in the finishing launch's place (wrong dQ) -- which launch carries the gaps?
-      const size_t n4 = (size_t)B * d / 4;
-      hipLaunchKernelGGL(sk_dq_reduce_kernel, dim3((unsigned)((n4 + 63) / 64)), dim3(256), 0, st, part, fz.nslices, n4, h_scale, d_scale, dQ);
-      HIP_TRY(hipGetLastError());
-    } else if (!tail && !dq_atomic) {
+      return launch_sk_dq_reduce(part, fz.nslices, B, d, h_scale, d_scale, dQ, st);
+    }
+    if (!tail && !dq_atomic) {
       // one workgroup per row where the row fits 256 threads (d <= 1024): the row's statistics are derived once, not once per part
       const int fthreads = d / 4 >= 256 ? 256 : cdiv(d / 4, 64) * 64;
       const int parts = cdiv(d / 4, fthreads);
       SkFinArgs f{part, fz.pair ? fz.ns : fz.nslices, fz.ksteps, nk_f, B, d, tile_lse, nts, gold, y, y_offset, Cb, grad_scale, h_scale, d_scale, dQ, parts,
                   fz.pair ? 1 : 0};
-      hipLaunchKernelGGL(sk_dq_finish_kernel, dim3((unsigned)(B * parts)), dim3((unsigned)fthreads), 0, st, f);
-      HIP_TRY(hipGetLastError());
+      return launch<sk_dq_finish_kernel>(dim3((unsigned)(B * parts)), dim3((unsigned)fthreads), 0, st, f);
     }
     return DPRHOT_OK;
   }
@@ -977,28 +905,16 @@ int sk_step(const float* q, const dprhot_bf16* Cb, dprhot_bf16* Qb, int B, int N
     int pp = parts;
     while (cdiv(Nc / 8, pp) > 4 * SK_THREADS) pp *= 2;
     SkGArgs g{S, tile_lse, gold, nts, B, Nc, y, y_offset, grad_scale, G, rl, row_lse, pp};
-    hipLaunchKernelGGL(sk_g_kernel, dim3((unsigned)(B * pp)), dim3(SK_THREADS), 0, st, g);
-    HIP_TRY(hipGetLastError());
+    if ((rc = launch<sk_g_kernel>(dim3((unsigned)(B * pp)), dim3(SK_THREADS), 0, st, g))) return rc;
   }
   {
     float* part = g_dq_part != nullptr ? g_dq_part : reinterpret_cast<float*>(ws + wl.dq_part);
     const int ndq = sk.nslices * (d / SK_QN), ndq_pad = (ndq + 7) & ~7, ndc = sk.nt * (d / SK_DN);
     SkBwdArgs b{G, Qb, Cb, B, Nc, d, h_scale, d_scale, dC_part, rl, loss_sum, g_loss_scale, g_dc_bf16 ? 1 : 0,
                 g_packed.stamp_src != nullptr ? g_packed.rows_c : 0, g_packed.n_ctx, sk.ksteps, sk.nslices, part, dQ, ndq_pad, opt(OPT_NT_STORES) ? 1 : 0};
-    const size_t lds = sk_bwd_lds();
-    static AttrOnce attr_done;
-    if (!attr_done) {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(sk_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      attr_done = true;
-    }
-    hipLaunchKernelGGL(sk_bwd_kernel, dim3((unsigned)(ndq_pad + ndc)), dim3(SK_THREADS), lds, st, b);
-    HIP_TRY(hipGetLastError());
-    if (g_dq_part == nullptr && sk.nslices > 1) {  // (else the caller's finishing launch forms dQ from the slabs: dprhot_rescale_grads;
-                                                   //  one slice: the dQ units stored the scaled sum themselves)
-      const size_t n4 = (size_t)B * d / 4;
-      hipLaunchKernelGGL(sk_dq_reduce_kernel, dim3((unsigned)((n4 + 63) / 64)), dim3(256), 0, st, part, sk.nslices, n4, h_scale, d_scale, dQ);
-      HIP_TRY(hipGetLastError());
-    }
+    if ((rc = launch_sk_bwd(b, ndq_pad + ndc, st))) return rc;
+    // (else the caller's finishing launch forms dQ from the slabs: dprhot_rescale_grads; one slice: the dQ units stored the scaled sum themselves)
+    if (g_dq_part == nullptr && sk.nslices > 1) return launch_sk_dq_reduce(part, sk.nslices, B, d, h_scale, d_scale, dQ, st);
   }
   return DPRHOT_OK;
 }
@@ -1052,29 +968,24 @@ static int ms_setup(MsArgs& p, const void* q_tok, const void* c_tok, int Nq, int
 }
 
 template <int KQT>
-static void ms_launch_fwd(const MsArgs& p, unsigned blocks, hipStream_t st) {
-  if (p.qid && p.qw) hipLaunchKernelGGL((ms_fwd_kernel<KQT, true, true>), dim3(blocks), dim3(256), 0, st, p);
-  else if (p.qid) hipLaunchKernelGGL((ms_fwd_kernel<KQT, true, false>), dim3(blocks), dim3(256), 0, st, p);
-  else if (p.qw) hipLaunchKernelGGL((ms_fwd_kernel<KQT, false, true>), dim3(blocks), dim3(256), 0, st, p);
-  else hipLaunchKernelGGL((ms_fwd_kernel<KQT, false, false>), dim3(blocks), dim3(256), 0, st, p);
+static int ms_launch_fwd(const MsArgs& p, unsigned blocks, hipStream_t st) {
+  if (p.qid && p.qw) return launch<ms_fwd_kernel<KQT, true, true>>(dim3(blocks), dim3(256), 0, st, p);
+  if (p.qid) return launch<ms_fwd_kernel<KQT, true, false>>(dim3(blocks), dim3(256), 0, st, p);
+  if (p.qw) return launch<ms_fwd_kernel<KQT, false, true>>(dim3(blocks), dim3(256), 0, st, p);
+  return launch<ms_fwd_kernel<KQT, false, false>>(dim3(blocks), dim3(256), 0, st, p);
 }
 
 template <bool IDS, bool W>
 static int ms_launch_bwd(const MsArgs& p, const MsBwd& g, hipStream_t st) {
   const int R = p.Nq * p.LQ;
-  if (g.dq || g.dwq)
-    hipLaunchKernelGGL((ms_dq_kernel<IDS, W>), dim3((unsigned)((R + 3) / 4), (unsigned)(g.dq ? (p.dp + MS_DQ_CHUNK - 1) / MS_DQ_CHUNK : 1)),
-                       dim3(256), 0, st, p, g);
+  if (g.dq || g.dwq) {
+    const dim3 grid((unsigned)((R + 3) / 4), (unsigned)(g.dq ? (p.dp + MS_DQ_CHUNK - 1) / MS_DQ_CHUNK : 1));
+    if (int rc = launch<ms_dq_kernel<IDS, W>>(grid, dim3(256), 0, st, p, g)) return rc;
+  }
   if (g.dc || g.dwc) {
-    const size_t lds = ((size_t)p.LD * MS_DC_SLICE + (size_t)p.LD * p.KD) * 4;
-    auto kern = ms_dc_kernel<IDS, W>;
-    static AttrOnce attr_done;
-    if (!attr_done) {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)(((size_t)DPRHOT_MAXSIM_MAX_LEN * (MS_DC_SLICE + MS_KMAX)) * 4)));
-      attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)p.Nc, (unsigned)(g.dc ? (p.dp + MS_DC_SLICE - 1) / MS_DC_SLICE : 1)), dim3(256), lds, st, p, g);
+    const size_t lds = ((size_t)p.LD * MS_DC_SLICE + (size_t)p.LD * p.KD) * 4;  // (grows with LD and KD: the helper raises the limit as it does)
+    const dim3 grid((unsigned)p.Nc, (unsigned)(g.dc ? (p.dp + MS_DC_SLICE - 1) / MS_DC_SLICE : 1));
+    return launch<ms_dc_kernel<IDS, W>>(grid, dim3(256), lds, st, p, g);
   }
   return DPRHOT_OK;
 }
@@ -1096,33 +1007,32 @@ static int rh_check_dtype(int dtype) {
 static int rh_npt(int V) { return V <= RH_THREADS ? 1 : V <= 4 * RH_THREADS ? 4 : V <= 32 * RH_THREADS ? 32 : 0; }
 
 template <int DT>
-static void rh_launch_row(const RhArgs& a, hipStream_t st) {
+static int rh_launch_row(const RhArgs& a, hipStream_t st) {
   const dim3 grid((unsigned)((long long)a.B * a.T)), block(RH_THREADS);
   switch (rh_npt(a.V)) {
-    case 1: hipLaunchKernelGGL((rh_row_kernel<DT, 1>), grid, block, 0, st, a); break;
-    case 4: hipLaunchKernelGGL((rh_row_kernel<DT, 4>), grid, block, 0, st, a); break;
-    case 32: hipLaunchKernelGGL((rh_row_kernel<DT, 32>), grid, block, 0, st, a); break;
-    default: hipLaunchKernelGGL((rh_row_kernel<DT, 0>), grid, block, 0, st, a); break;
+    case 1: return launch<rh_row_kernel<DT, 1>>(grid, block, 0, st, a);
+    case 4: return launch<rh_row_kernel<DT, 4>>(grid, block, 0, st, a);
+    case 32: return launch<rh_row_kernel<DT, 32>>(grid, block, 0, st, a);
+    default: return launch<rh_row_kernel<DT, 0>>(grid, block, 0, st, a);
   }
 }
 template <int DT>
-static void rh_launch_fwd(const RhArgs& a, hipStream_t st) {
-  if (a.k > 0 || a.want_soft) rh_launch_row<DT>(a, st);
-  hipLaunchKernelGGL((rh_col_kernel<DT>), dim3((unsigned)((a.V + RH_COLS - 1) / RH_COLS), (unsigned)a.B), dim3(RH_COLS), 0, st, a);
+static int rh_launch_fwd(const RhArgs& a, hipStream_t st) {
+  if (a.k > 0 || a.want_soft)
+    if (int rc = rh_launch_row<DT>(a, st)) return rc;
+  return launch<rh_col_kernel<DT>>(dim3((unsigned)((a.V + RH_COLS - 1) / RH_COLS), (unsigned)a.B), dim3(RH_COLS), 0, st, a);
 }
 template <int DT>
-static void rh_launch_bwd(const RhArgs& a, hipStream_t st) {
+static int rh_launch_bwd(const RhArgs& a, hipStream_t st) {
   if (!a.g_soft) {
-    hipLaunchKernelGGL((rh_bwd_sparse_kernel<DT>),
-                       dim3((unsigned)((a.V + RH_COLS - 1) / RH_COLS), (unsigned)((a.T1 + RH_BWD_ROWS - 1) / RH_BWD_ROWS), (unsigned)a.B),
-                       dim3(RH_COLS), 0, st, a);
-    return;
+    const dim3 grid((unsigned)((a.V + RH_COLS - 1) / RH_COLS), (unsigned)((a.T1 + RH_BWD_ROWS - 1) / RH_BWD_ROWS), (unsigned)a.B);
+    return launch<rh_bwd_sparse_kernel<DT>>(grid, dim3(RH_COLS), 0, st, a);
   }
   const dim3 grid((unsigned)((long long)a.B * a.T1)), block(RH_THREADS);
   switch (rh_npt(a.V)) {
-    case 1: hipLaunchKernelGGL((rh_bwd_row_kernel<DT, 1>), grid, block, 0, st, a); break;
-    case 4: hipLaunchKernelGGL((rh_bwd_row_kernel<DT, 4>), grid, block, 0, st, a); break;
-    default: hipLaunchKernelGGL((rh_bwd_row_kernel<DT, 0>), grid, block, 0, st, a); break;
+    case 1: return launch<rh_bwd_row_kernel<DT, 1>>(grid, block, 0, st, a);
+    case 4: return launch<rh_bwd_row_kernel<DT, 4>>(grid, block, 0, st, a);
+    default: return launch<rh_bwd_row_kernel<DT, 0>>(grid, block, 0, st, a);
   }
 }
 
@@ -1168,9 +1078,7 @@ int dprhot_cast_bf16(const float* src, dprhot_bf16* dst, size_t n, void* stream)
   if (n == 0) return DPRHOT_OK;
   const size_t n4 = n / 4, tiles = (n4 + 256 * CAST_UT - 1) / (256 * CAST_UT);
   REQUIRE(tiles < (1ull << 31), "n=%zu", n);
-  hipLaunchKernelGGL(cast_bf16_kernel, dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, src, dst, n4);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  return launch<cast_bf16_kernel>(dim3((unsigned)tiles), dim3(256), 0, (hipStream_t)stream, src, dst, n4);
 }
 
 int dprhot_prep(const float* q, size_t nq, dprhot_bf16* Qb, const float* c, size_t nc, dprhot_bf16* Cdst, void* stream) {
@@ -1180,9 +1088,7 @@ int dprhot_prep(const float* q, size_t nq, dprhot_bf16* Qb, const float* c, size
   const size_t n8 = (nq + nc) / 8;
   if (n8 == 0) return DPRHOT_OK;
   const int blocks = (int)((n8 + 255) / 256 > 2048 ? 2048 : (n8 + 255) / 256);
-  hipLaunchKernelGGL(cast2_bf16_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, q, Qb, nq / 8, c, Cdst, nc / 8);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  return launch<cast2_bf16_kernel>(dim3(blocks), dim3(256), 0, (hipStream_t)stream, q, Qb, nq / 8, c, Cdst, nc / 8);
 }
 
 int dprhot_packed_rows(int n_ctx, int d, int* h_rows) {
@@ -1204,9 +1110,7 @@ int dprhot_pack_ctx(const float* c, const uint8_t* mask, int n_ctx, int d, dprho
   dprhot_packed_rows(n_ctx, d, &rows_c);
   const size_t n8 = (size_t)rows_c * d / 8;
   const int blocks = (int)((n8 + 255) / 256 > 2048 ? 2048 : (n8 + 255) / 256);
-  hipLaunchKernelGGL(pack_ctx_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, c, mask, n_ctx, d, rows_c, send);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  return launch<pack_ctx_kernel>(dim3(blocks), dim3(256), 0, (hipStream_t)stream, c, mask, n_ctx, d, rows_c, send);
 }
 
 int dprhot_unpack_mask(const dprhot_bf16* gathered, int W, int n_ctx, int d, uint8_t* colmask, void* stream) {
@@ -1215,10 +1119,8 @@ int dprhot_unpack_mask(const dprhot_bf16* gathered, int W, int n_ctx, int d, uin
   int rows_c = 0;
   dprhot_packed_rows(n_ctx, d, &rows_c);
   const int total = W * rows_c;
-  hipLaunchKernelGGL(unpack_mask_kernel, dim3(cdiv(total, 256) > 1024 ? 1024 : cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream,
-                     gathered, W, n_ctx, d, rows_c, colmask);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  return launch<unpack_mask_kernel>(dim3(cdiv(total, 256) > 1024 ? 1024 : cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, gathered, W, n_ctx,
+                                    d, rows_c, colmask);
 }
 
 int dprhot_sim_fwd(const dprhot_bf16* Q, int B, const dprhot_bf16* C, int Nc, int d, const uint8_t* colmask, float inv_T,
@@ -1250,20 +1152,13 @@ int dprhot_softmax_ce_fwd_bwd(const float* S, int B, int Nc, const int64_t* y, i
   REQUIRE(aligned16(S) && (G == nullptr || aligned16(G)), "pointers must be 16-byte aligned");
   REQUIRE(row_win_start == nullptr || win_len > 0, "win_len must be > 0 with row_win_start");
   SoftmaxArgs p{S, B, Nc, y, y_offset, grad_scale, row_win_start, win_len, row_loss, row_lse, G};
-  if (Nc <= 4096) {
-    hipLaunchKernelGGL(softmax_ce_kernel<64>, dim3(cdiv(B, 4)), dim3(256), 0, (hipStream_t)stream, p);
-  } else {
-    hipLaunchKernelGGL(softmax_ce_kernel<256>, dim3(B), dim3(256), 0, (hipStream_t)stream, p);
-  }
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  if (Nc <= 4096) return launch<softmax_ce_kernel<64>>(dim3(cdiv(B, 4)), dim3(256), 0, (hipStream_t)stream, p);
+  return launch<softmax_ce_kernel<256>>(dim3(B), dim3(256), 0, (hipStream_t)stream, p);
 }
 
 int dprhot_reduce_sum(const float* x, int n, float scale, float* out, void* stream) {
   REQUIRE(x && out && n > 0, "bad argument");
-  hipLaunchKernelGGL(reduce_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, x, n, scale, out);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  return launch<reduce_sum_kernel>(dim3(1), dim3(256), 0, (hipStream_t)stream, x, n, scale, out);
 }
 
 int dprhot_dq(const dprhot_bf16* G, const dprhot_bf16* C, int B, int Nc, int d, float h_scale, const float* d_scale, float* dQ,
@@ -1297,43 +1192,26 @@ int dprhot_rank_of_gold(const float* S, int rows, int cols, const int64_t* y, in
   REQUIRE(rows > 0 && cols > 0, "bad shape rows=%d cols=%d", rows, cols);
   if (cols % 4 != 0) return fail(DPRHOT_E_UNSUPPORTED, "cols=%d must be a multiple of 4", cols);
   REQUIRE(aligned16(S), "S must be 16-byte aligned");
-  hipLaunchKernelGGL(rank_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, S, rows, cols, y, y_offset, rank);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  return launch<rank_kernel>(dim3(rows), dim3(256), 0, (hipStream_t)stream, S, rows, cols, y, y_offset, rank);
 }
 
 int dprhot_pairwise_fwd(const float* q, const float* c, const uint8_t* mask, int B, int M, int d, float* S, void* stream) {
   REQUIRE(q && c && S, "NULL pointer");
   REQUIRE(B > 0 && M > 0 && d > 0, "bad shape B=%d M=%d d=%d", B, M, d);
   REQUIRE((long)B * M <= 0x7fffffffL, "too many pairs");
-  hipLaunchKernelGGL(pairwise_fwd_kernel, dim3((unsigned)(B * M)), dim3(256), 0, (hipStream_t)stream, q, c, mask, B, M, d, S);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  return launch<pairwise_fwd_kernel>(dim3((unsigned)(B * M)), dim3(256), 0, (hipStream_t)stream, q, c, mask, B, M, d, S);
 }
 
 int dprhot_pairwise_bwd(const float* g, const float* q, const float* c, int B, int M, int d, float* dq, float* dc, void* stream) {
   REQUIRE(g && q && c, "NULL pointer");
   REQUIRE(B > 0 && M > 0 && d > 0 && B <= 65535, "bad shape B=%d M=%d d=%d", B, M, d);
-  hipLaunchKernelGGL(pairwise_bwd_kernel, dim3((unsigned)cdiv(d, 512), (unsigned)B), dim3(256), 0, (hipStream_t)stream, g, q, c, B, M, d, dq, dc);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  return launch<pairwise_bwd_kernel>(dim3((unsigned)cdiv(d, 512), (unsigned)B), dim3(256), 0, (hipStream_t)stream, g, q, c, B, M, d, dq, dc);
 }
 
 static int launch_topk(const TopkArgs& p, int rows, hipStream_t st) {
-  if (p.k <= TK_KSMALL) {
-    hipLaunchKernelGGL((topk_stream_kernel<1024, TK_KSMALL, 4>), dim3(rows), dim3(256), tk_lds_bytes(1024), st, p);
-  } else if (p.k <= TK_KMAX) {
-    hipLaunchKernelGGL((topk_stream_kernel<4096, TK_KMAX, 8>), dim3(rows), dim3(256), tk_lds_bytes(4096), st, p);
-  } else {  // 1024 < k <= 4096: 8192 slots
-    auto kern = topk_stream_kernel<8192, TK_KWIDE, 8>;
-    static AttrOnce attr_done;
-    if (!attr_done) {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tk_lds_bytes(8192)));
-      attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(rows), dim3(256), tk_lds_bytes(8192), st, p);
-  }
-  return DPRHOT_OK;
+  if (p.k <= TK_KSMALL) return launch<topk_stream_kernel<1024, TK_KSMALL, 4>>(dim3(rows), dim3(256), tk_lds_bytes(1024), st, p);
+  if (p.k <= TK_KMAX) return launch<topk_stream_kernel<4096, TK_KMAX, 8>>(dim3(rows), dim3(256), tk_lds_bytes(4096), st, p);
+  return launch<topk_stream_kernel<8192, TK_KWIDE, 8>>(dim3(rows), dim3(256), tk_lds_bytes(8192), st, p);  // 1024 < k <= 4096: 8192 slots
 }
 
 int dprhot_topk_update(const float* S, int rows, int cols, int64_t ld, int64_t col_offset, int k, float* values,
@@ -1343,9 +1221,7 @@ int dprhot_topk_update(const float* S, int rows, int cols, int64_t ld, int64_t c
           (long long)ld, k);
   REQUIRE(col_offset >= 0, "negative col_offset");
   TopkArgs p{S, rows, cols, (long long)ld, (long long)col_offset, k, values, indices, first ? 1 : 0, nullptr, nullptr};
-  if (int rc = launch_topk(p, rows, (hipStream_t)stream)) return rc;
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  return launch_topk(p, rows, (hipStream_t)stream);
 }
 
 int dprhot_topk(const float* S, int rows, int cols, int k, float* values, int64_t* indices, void* stream) {
@@ -1385,34 +1261,26 @@ int dprhot_topk_update_wide(const float* S, int rows, int cols, int64_t ld, int6
   float* Bv = reinterpret_cast<float*>(ws + off); off += align256((size_t)rows * k * 4);
   int64_t* Bi = reinterpret_cast<int64_t*>(ws + off);
   WselArgs a{S, rows, cols, (long long)ld, (long long)col_offset, k, values, indices, first, rec, Av, Ai};
-  hipLaunchKernelGGL(wsel_select_kernel, dim3((unsigned)rows), dim3(WSEL_THREADS), 0, st, a);
-  hipLaunchKernelGGL(wsel_collect_kernel, dim3((unsigned)rows), dim3(WSEL_THREADS), 0, st, a);
+  if (int rc = launch<wsel_select_kernel>(dim3((unsigned)rows), dim3(WSEL_THREADS), 0, st, a)) return rc;
+  if (int rc = launch<wsel_collect_kernel>(dim3((unsigned)rows), dim3(WSEL_THREADS), 0, st, a)) return rc;
   const int nblk = cdiv(k, WSEL_BLOCK);
-  const size_t lds = (size_t)WSEL_BLOCK * 12;
-  static AttrOnce attr_done;
-  if (!attr_done) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(wsel_sort_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_done = true;
-  }
-  hipLaunchKernelGGL(wsel_sort_kernel, dim3((unsigned)rows, (unsigned)nblk), dim3(WSEL_THREADS), lds, st, Av, Ai, k);
+  if (int rc = launch<wsel_sort_kernel>(dim3((unsigned)rows, (unsigned)nblk), dim3(WSEL_THREADS), (size_t)WSEL_BLOCK * 12, st, Av, Ai, k)) return rc;
   int passes = 0;
   for (long long L = WSEL_BLOCK; L < k; L <<= 1) ++passes;
   const dim3 mgrid((unsigned)cdiv(k, WSEL_THREADS), (unsigned)rows);
   const float* sv = Av;
   const int64_t* si = Ai;
-  if (passes == 0) {  // one block: the sorted block IS the new state (a merge pass against an empty partner run copies it)
-    hipLaunchKernelGGL(wsel_merge_kernel, mgrid, dim3(WSEL_THREADS), 0, st, sv, si, values, indices, k, WSEL_BLOCK, rec);
-  }
+  if (passes == 0)  // one block: the sorted block IS the new state (a merge pass against an empty partner run copies it)
+    return launch<wsel_merge_kernel>(mgrid, dim3(WSEL_THREADS), 0, st, sv, si, values, indices, k, WSEL_BLOCK, rec);
   long long L = WSEL_BLOCK;
   for (int j = 0; j < passes; ++j, L <<= 1) {
     const bool last = j == passes - 1;
     float* dv = last ? values : ((j & 1) == 0 ? Bv : Av);
     int64_t* di = last ? indices : ((j & 1) == 0 ? Bi : Ai);
-    hipLaunchKernelGGL(wsel_merge_kernel, mgrid, dim3(WSEL_THREADS), 0, st, sv, si, dv, di, k, (int)L, last ? rec : nullptr);
+    if (int rc = launch<wsel_merge_kernel>(mgrid, dim3(WSEL_THREADS), 0, st, sv, si, dv, di, k, (int)L, last ? rec : nullptr)) return rc;
     sv = dv;
     si = di;
   }
-  HIP_TRY(hipGetLastError());
   return DPRHOT_OK;
 }
 
@@ -1472,8 +1340,7 @@ int dprhot_search(const dprhot_bf16* Q, int nq, const dprhot_bf16* C, int64_t n_
         if (int rc = launch_g8(a8, e8, st)) return rc;
       }
       TopkArgs p8{S, nq, cols, (long long)cols, (long long)(id_offset + j0), k, values, indices, 0, cand_j, cnt};
-      launch_topk(p8, nq, st);
-      HIP_TRY(hipGetLastError());
+      if (int rc = launch_topk(p8, nq, st)) return rc;
       continue;
     }
     const int tile = (force_tile() < 0 && big_ok(nq, cols, d)) ? kBigTile : pick_tile(nq, cols, d, 1, 2 * kNumCU);
@@ -1481,8 +1348,7 @@ int dprhot_search(const dprhot_bf16* Q, int nq, const dprhot_bf16* C, int64_t n_
     EpiFilter epi{values, indices, k, nq, cols, (long long)(id_offset + j0), cnt, S, cand_j};
     if (int rc = launch_gemm<true, true>(tile, a, epi, 1, st)) return rc;
     TopkArgs p{S, nq, cols, (long long)cols, (long long)(id_offset + j0), k, values, indices, 0, cand_j, cnt};
-    launch_topk(p, nq, st);
-    HIP_TRY(hipGetLastError());
+    if (int rc = launch_topk(p, nq, st)) return rc;
   }
   return DPRHOT_OK;
 }
@@ -1558,14 +1424,7 @@ int dprhot_sim_stats_f32(const float* q, const float* c, dprhot_bf16* Qb, dprhot
       // vocabulary-wide fp32 operands: LDS-DMA ring of fp32 tiles, bf16 rounding on the fragment read (wide.h)
       WideSimArgs wa{q, c, Qb, Cb, B, Nc, d, colmask, inv_T, reinterpret_cast<float*>(ws + wl.logits), (size_t)B * Nc, fp.kchunk,
                      reinterpret_cast<unsigned long long*>(ws + wl.header), 2, opt(OPT_WIDE_NOCOPY), cdiv(Nc, WD_B), cdiv(B, WD_B)};
-      static AttrOnce attr_done;
-      if (!attr_done) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(wide_sim_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)wd_lds_bytes));
-        attr_done = true;
-      }
-      hipLaunchKernelGGL(wide_sim_kernel, dim3((unsigned)(wa.nbx * wa.nby * fp.splits)), dim3(WD_THREADS), wd_lds_bytes, (hipStream_t)stream, wa);
-      HIP_TRY(hipGetLastError());
-      return DPRHOT_OK;
+      return launch<wide_sim_kernel>(dim3((unsigned)(wa.nbx * wa.nby * fp.splits)), dim3(WD_THREADS), wd_lds_bytes, (hipStream_t)stream, wa);
     }
     EpiSim epi{reinterpret_cast<float*>(ws + wl.logits), colmask, B, Nc, inv_T, nullptr, nullptr, nullptr, 0, nullptr,
                reinterpret_cast<unsigned long long*>(ws + wl.header), 2, (size_t)B * Nc};
@@ -1598,10 +1457,10 @@ int dprhot_softmax_finish(const float* S_in, int B, int Nc, int d, const int64_t
     // into G here -- dprhot_dscores recomputes them
     if (G != nullptr) return fail(DPRHOT_E_UNSUPPORTED, "softmax_finish: no logits at B=%d Nc=%d d=%d (no-logits forward): G comes from dprhot_dscores", B, Nc, d);
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(g8_lse_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, reinterpret_cast<const float*>(ws + wl.part_m),
-                       reinterpret_cast<const float*>(ws + wl.part_s), cdiv(Nc, G2_B) * 4, reinterpret_cast<const float*>(ws + wl.gold), B,
-                       reinterpret_cast<float*>(ws + wl.lse), row_lse, row_loss, reinterpret_cast<float*>(ws + wl.rloss));
-    HIP_TRY(hipGetLastError());
+    if (int rc = launch<g8_lse_kernel>(dim3(cdiv(B, 4)), dim3(256), 0, st, reinterpret_cast<const float*>(ws + wl.part_m),
+                                       reinterpret_cast<const float*>(ws + wl.part_s), cdiv(Nc, G2_B) * 4, reinterpret_cast<const float*>(ws + wl.gold), B,
+                                       reinterpret_cast<float*>(ws + wl.lse), row_lse, row_loss, reinterpret_cast<float*>(ws + wl.rloss)))
+      return rc;
     return launch_loss_sum(reinterpret_cast<const float*>(ws + wl.rloss), B, g_loss_scale, loss_sum, st);
   }
   const FwdPlan fp = fwd_plan(B, Nc, d);  // same plan as dprhot_sim_stats -> same intermediate layout
@@ -1610,10 +1469,8 @@ int dprhot_softmax_finish(const float* S_in, int B, int Nc, int d, const int64_t
     GShortArgs g{reinterpret_cast<const float*>(ws + wl.logits), fp.splits, (size_t)B * Nc, B, Nc, y, y_offset, grad_scale,
                  const_cast<float*>(S_in), row_loss, row_lse, G, reinterpret_cast<unsigned long long*>(ws + wl.header), loss_sum, fp.tpr, g_loss_scale};
     if (fp.blocks > 65535) return fail(DPRHOT_E_UNSUPPORTED, "softmax_finish: B=%d rows need %d workgroups (max 65535)", B, fp.blocks);
-    if (fp.cpt == 1) hipLaunchKernelGGL(gfinal_short_kernel<1>, dim3(fp.blocks), dim3(fp.threads), 0, (hipStream_t)stream, g);
-    else hipLaunchKernelGGL(gfinal_short_kernel<2>, dim3(fp.blocks), dim3(fp.threads), 0, (hipStream_t)stream, g);
-    HIP_TRY(hipGetLastError());
-    return DPRHOT_OK;
+    if (fp.cpt == 1) return launch<gfinal_short_kernel<1>>(dim3(fp.blocks), dim3(fp.threads), 0, (hipStream_t)stream, g);
+    return launch<gfinal_short_kernel<2>>(dim3(fp.blocks), dim3(fp.threads), 0, (hipStream_t)stream, g);
   }
   const float* S = S_in ? S_in : reinterpret_cast<const float*>(ws + wl.logits);
   const int nt = fp.nt;
@@ -1627,10 +1484,8 @@ int dprhot_softmax_finish(const float* S_in, int B, int Nc, int d, const int64_t
   if (cdiv(B, rpb) > 65535)  // grid.y limit, and the arrival ticket of the loss accumulation is 16 bits wide
     return fail(DPRHOT_E_UNSUPPORTED, "softmax_finish: B=%d rows need %d row blocks (max 65535)", B, cdiv(B, rpb));
   dim3 grid(xblocks, cdiv(B, rpb));
-  if (thin) hipLaunchKernelGGL(gfinal_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, g);
-  else hipLaunchKernelGGL(gfinal_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, g);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  if (thin) return launch<gfinal_kernel<1>>(grid, dim3(256), 0, (hipStream_t)stream, g);
+  return launch<gfinal_kernel<8>>(grid, dim3(256), 0, (hipStream_t)stream, g);
 }
 
 // dScores of the no-logits forward: G = (softmax(S) - onehot) * grad_scale with S recomputed tile by tile (the same GEMM as
@@ -1683,13 +1538,11 @@ int dprhot_sim_rank(const dprhot_bf16* Q, int B, const dprhot_bf16* C, int Nc, i
   static_cast<Epi8Base&>(epi) = g8_base(Q, B, Nc, y, y_offset, colmask, inv_T, nullptr);
   epi.gold_val = gold;
   epi.count = count;
-  hipLaunchKernelGGL(g8_gold_kernel, dim3(cdiv(B, 32)), dim3(64), 0, st, Q, C, B, Nc, d, y, y_offset, epi.sim, inv_T, gold);
+  if (int rc = launch<g8_gold_kernel>(dim3(cdiv(B, 32)), dim3(64), 0, st, Q, C, B, Nc, d, y, y_offset, epi.sim, inv_T, gold)) return rc;
   HIP_TRY(hipMemsetAsync(count, 0, (size_t)B * sizeof(int), st));
   GemmArgs a8{Q, C, B, Nc, d, d, d, d};
   if (int rc = launch_g8(a8, epi, st)) return rc;
-  hipLaunchKernelGGL(g8_rank_finish_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, count, B, rank);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  return launch<g8_rank_finish_kernel>(dim3(cdiv(B, 256)), dim3(256), 0, st, count, B, rank);
 }
 
 // compute_rank_metrics AND the cross-entropy of the same scores (dpr_task.py:224-227, :296-299) in one call: at no-logits shapes ONE
@@ -1721,14 +1574,14 @@ int dprhot_sim_rank_loss(const dprhot_bf16* Q, int B, const dprhot_bf16* C, int 
   epi.part_m = reinterpret_cast<float*>(ws + wl.part_m);
   epi.part_s = reinterpret_cast<float*>(ws + wl.part_s);
   epi.npart = cdiv(Nc, G2_B) * 4;
-  hipLaunchKernelGGL(g8_gold_kernel, dim3(cdiv(B, 32)), dim3(64), 0, st, Q, C, B, Nc, d, y, y_offset, epi.sim, inv_T, gold);
+  if (int rc = launch<g8_gold_kernel>(dim3(cdiv(B, 32)), dim3(64), 0, st, Q, C, B, Nc, d, y, y_offset, epi.sim, inv_T, gold)) return rc;
   HIP_TRY(hipMemsetAsync(count, 0, (size_t)B * sizeof(int), st));
   GemmArgs a8{Q, C, B, Nc, d, d, d, d};
   if (int rc = launch_g8(a8, epi, st)) return rc;
-  hipLaunchKernelGGL(g8_rank_finish_kernel, dim3(cdiv(B, 256)), dim3(256), 0, st, count, B, rank);
-  hipLaunchKernelGGL(g8_lse_kernel, dim3(cdiv(B, 4)), dim3(256), 0, st, epi.part_m, epi.part_s, epi.npart, gold, B,
-                     reinterpret_cast<float*>(ws + wl.lse), row_lse, row_loss, reinterpret_cast<float*>(ws + wl.rloss));
-  HIP_TRY(hipGetLastError());
+  if (int rc = launch<g8_rank_finish_kernel>(dim3(cdiv(B, 256)), dim3(256), 0, st, count, B, rank)) return rc;
+  if (int rc = launch<g8_lse_kernel>(dim3(cdiv(B, 4)), dim3(256), 0, st, epi.part_m, epi.part_s, epi.npart, gold, B, reinterpret_cast<float*>(ws + wl.lse),
+                                     row_lse, row_loss, reinterpret_cast<float*>(ws + wl.rloss)))
+    return rc;
   return launch_loss_sum(reinterpret_cast<const float*>(ws + wl.rloss), B, g_loss_scale, loss_sum, st);
 }
 
@@ -1753,17 +1606,8 @@ int dprhot_inbatch_fwd(const dprhot_bf16* Q, int B, const dprhot_bf16* C, int Nc
     epi.P = G;
     epi.npart = cdiv(Nc, 64);
     GemmArgs a{Q, C, B, Nc, d, d, d, d};
-    auto kern = gemm128d_kernel<true, true, EpiSimP, false>;
-    static AttrOnce attr_done;
-    if (!attr_done) {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g1_lds_bytes));
-      attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(cdiv(Nc, 128), cdiv(B, 128), 1), dim3(256), g1_lds_bytes, st, a, epi);
-    hipLaunchKernelGGL(g8_lse_p2g_kernel, dim3((unsigned)B), dim3(256), 0, st, epi.part_m, epi.part_s, epi.npart,
-                       reinterpret_cast<const float*>(ws + wl.gold), B, Nc, y, y_offset, grad_scale, reinterpret_cast<float*>(ws + wl.lse), row_lse, row_loss,
-                       reinterpret_cast<float*>(ws + wl.rloss), G);
-    HIP_TRY(hipGetLastError());
+    if (int rc = launch<gemm128d_kernel<true, true, EpiSimP, false>>(dim3(cdiv(Nc, 128), cdiv(B, 128), 1), dim3(256), g1_lds_bytes, st, a, epi)) return rc;
+    if (int rc = launch_lse_p2g(epi.part_m, epi.part_s, epi.npart, B, Nc, y, y_offset, grad_scale, row_lse, row_loss, G, ws, wl, st)) return rc;
     return launch_loss_sum(reinterpret_cast<const float*>(ws + wl.rloss), B, g_loss_scale, loss_sum, st);
   }
   if (S_out == nullptr && G != nullptr && nl_ok(B, Nc, d) && opt(OPT_NL_P16) != 0) {
@@ -1791,10 +1635,7 @@ int dprhot_inbatch_fwd(const dprhot_bf16* Q, int B, const dprhot_bf16* C, int Nc
       es.P = G;
       if (int rc = launch_g8<Epi8StatsPS, 2>(a8, es, st)) return rc;
     } else if (int rc = launch_g8<Epi8StatsP, 2>(a8, epi, st)) return rc;  // (two-phase schedule, as every storing epilogue; the four-phase instantiation spilled two registers)
-    hipLaunchKernelGGL(g8_lse_p2g_kernel, dim3((unsigned)B), dim3(256), 0, st, epi.part_m, epi.part_s, epi.npart,
-                       reinterpret_cast<const float*>(ws + wl.gold), B, Nc, y, y_offset, grad_scale, reinterpret_cast<float*>(ws + wl.lse), row_lse, row_loss,
-                       reinterpret_cast<float*>(ws + wl.rloss), G);
-    HIP_TRY(hipGetLastError());
+    if (int rc = launch_lse_p2g(epi.part_m, epi.part_s, epi.npart, B, Nc, y, y_offset, grad_scale, row_lse, row_loss, G, ws, wl, st)) return rc;
     return launch_loss_sum(reinterpret_cast<const float*>(ws + wl.rloss), B, g_loss_scale, loss_sum, st);
   }
   if (S_out == nullptr && nl_ok(B, Nc, d)) {
@@ -1863,19 +1704,8 @@ int dprhot_inbatch_bwd(const dprhot_bf16* G, const dprhot_bf16* Q, const dprhot_
       const int ndq = sk.nslices * (d / SK_QN), ndq_pad = (ndq + 7) & ~7, ndc = sk.nt * (d / SK_DN);
       SkBwdArgs b{G, Q, C, B, Nc, d, h_scale, d_scale, dC_part, nullptr, nullptr, 1.0f, 0, 0, 0, sk.ksteps, sk.nslices, part, dQ, ndq_pad,
                   opt(OPT_NT_STORES) ? 1 : 0};
-      const size_t lds = sk_bwd_lds();
-      static AttrOnce attr_done;
-      if (!attr_done) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(sk_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_done = true;
-      }
-      hipLaunchKernelGGL(sk_bwd_kernel, dim3((unsigned)(ndq_pad + ndc)), dim3(SK_THREADS), lds, st, b);
-      HIP_TRY(hipGetLastError());
-      if (sk.nslices > 1) {
-        const size_t n4 = (size_t)B * d / 4;
-        hipLaunchKernelGGL(sk_dq_reduce_kernel, dim3((unsigned)((n4 + 63) / 64)), dim3(256), 0, st, part, sk.nslices, n4, h_scale, d_scale, dQ);
-        HIP_TRY(hipGetLastError());
-      }
+      if (int rc = launch_sk_bwd(b, ndq_pad + ndc, st)) return rc;
+      if (sk.nslices > 1) return launch_sk_dq_reduce(part, sk.nslices, B, d, h_scale, d_scale, dQ, st);
       return DPRHOT_OK;
     }
   }
@@ -1889,15 +1719,7 @@ int dprhot_inbatch_bwd(const dprhot_bf16* G, const dprhot_bf16* Q, const dprhot_
     const int ksteps = cdiv(Nc, 64);
     const int ndq = d / SK_QN, ndq_pad = (ndq + 7) & ~7, ndc = cdiv(Nc, SK_COLS) * cdiv(d, SK_DN);
     SkBwdArgs b{G, Q, C, B, Nc, d, h_scale, d_scale, dC_part, nullptr, nullptr, 1.0f, 0, 0, 0, ksteps, 1, nullptr, dQ, ndq_pad, opt(OPT_NT_STORES) ? 1 : 0};
-    const size_t lds = sk_bwd_lds();
-    static AttrOnce attr_done;
-    if (!attr_done) {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(sk_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      attr_done = true;
-    }
-    hipLaunchKernelGGL(sk_bwd_kernel, dim3((unsigned)(ndq_pad + ndc)), dim3(SK_THREADS), lds, st, b);
-    HIP_TRY(hipGetLastError());
-    return DPRHOT_OK;
+    return launch_sk_bwd(b, ndq_pad + ndc, st);
   }
   const WsLayout wl = ws_layout(B, Nc, d);
   if (pair128_use(B, Nc, d)) {
@@ -1912,17 +1734,11 @@ int dprhot_inbatch_bwd(const dprhot_bf16* G, const dprhot_bf16* Q, const dprhot_
     GemmArgs a2{G, C, B, d, Nc, Nc, d, pp.kchunk};
     const EpiScaleF32 e2 = pp.splits == 1 ? EpiScaleF32{dQ, B, d, h_scale, d_scale}
                                           : EpiScaleF32{reinterpret_cast<float*>(ws + wl.dq_part), B, d, 1.0f, nullptr};
-    auto kern = gemm128d_pair_kernel<EpiScaleF32>;
-    static AttrOnce attr_done;
-    if (!attr_done) {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g1_lds_bytes));
-      attr_done = true;
-    }
     const int nbx1 = cdiv(d, 128), nby1 = cdiv(Nc, 128), nbx2 = cdiv(d, 128), nby2 = cdiv(B, 128);
     const long grid = (long)nbx1 * nby1 + (long)nbx2 * nby2 * pp.splits;
     if (grid > 0x7fffffffL) return fail(DPRHOT_E_UNSUPPORTED, "grid too large");
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), g1_lds_bytes, st, a1, e1, nbx1, nby1, a2, e2, nbx2, nby2, pp.splits);
-    HIP_TRY(hipGetLastError());
+    if (int rc = launch<gemm128d_pair_kernel<EpiScaleF32>>(dim3((unsigned)grid), dim3(256), g1_lds_bytes, st, a1, e1, nbx1, nby1, a2, e2, nbx2, nby2, pp.splits))
+      return rc;
     if (pp.splits > 1) return launch_slab_sum(reinterpret_cast<const float*>(ws + wl.dq_part), pp.splits, B, d, h_scale, d_scale, dQ, st);
     return DPRHOT_OK;
   }
@@ -1937,12 +1753,6 @@ int dprhot_inbatch_bwd(const dprhot_bf16* G, const dprhot_bf16* Q, const dprhot_
   EpiScaleF32 e2 = p.splits == 1 ? EpiScaleF32{dQ, B, d, h_scale, d_scale}
                                  : EpiScaleF32{reinterpret_cast<float*>(ws + wl.dq_part), B, d, 1.0f, nullptr};
   if (p.big) {
-    auto kern = gemm256_bwd_kernel<EpiScaleF32>;
-    static AttrOnce attr_done;  // benign race: idempotent
-    if (!attr_done) {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g2_lds_total));
-      attr_done = true;
-    }
     // Few query rows against a long context axis (512 <= B <= 2048, Nc >= 32 B: e.g. 8192 global queries x 8 contexts seen from one
     // of 8 ranks): the dC tiles of the pair launch are only K = B deep -- 8 to 32 K steps between a pipeline fill and a 256 KiB store
     // -- next to dQ units several times as long (the K slices of dQ stop at 16), and the launch loses to dC on the 128 x 128 engine in a
@@ -1956,40 +1766,24 @@ int dprhot_inbatch_bwd(const dprhot_bf16* G, const dprhot_bf16* Q, const dprhot_
     //  multi-rank layout's column counts are multiples of 64, rarely of 128)
     const bool ok8 = !no8 && B % 64 == 0 && Nc % 64 == 0 && p.kchunk % 128 == 0 && (double)B * Nc < 2.0e9 && (double)Nc * d < 2.0e9;
     a1.kchunk = B;  // dC: one K range (B % 64 == 0)
+    // the same epilogues for the phase-interleaved kernel (gemm8pb.h)
+    const Epi8Scale s1{e1.out, e1.M, e1.N, e1.h_scale, e1.d_scale, e1.stamp_src, e1.stamp_period, e1.stamp_row};
+    const Epi8Scale s2{e2.out, e2.M, e2.N, e2.h_scale, e2.d_scale, e2.stamp_src, e2.stamp_period, e2.stamp_row};
     if (long_axis && ok8 && (opt(OPT_DC_ALONE_8P) == 2 || (opt(OPT_DC_ALONE_8P) == 1 && ((size_t)Nc * 2) % ((size_t)128 << 10) == 0))) {
       // (A/B, round 6) the dC tiles alone on the phase-interleaved kernel: no dQ units four times as long next to them
-      auto k8 = gemm8p_bwd_kernel<Epi8Scale>;
-      static AttrOnce attr8a_done;
-      if (!attr8a_done) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k8), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g8_lds_total));
-        attr8a_done = true;
-      }
-      const Epi8Scale s1{e1.out, e1.M, e1.N, e1.h_scale, e1.d_scale, e1.stamp_src, e1.stamp_period, e1.stamp_row};
-      const Epi8Scale s2{e2.out, e2.M, e2.N, e2.h_scale, e2.d_scale, e2.stamp_src, e2.stamp_period, e2.stamp_row};
       const int nbx1a = cdiv(d, G2_B), nby1a = cdiv(Nc, G2_B);
-      hipLaunchKernelGGL(k8, dim3((unsigned)(nbx1a * nby1a)), dim3(G2_THREADS), g8_lds_total, st, a1, s1, nbx1a, nby1a, a2, s2, cdiv(d, G2_B), 0, p.splits);
-      HIP_TRY(hipGetLastError());
+      if (int rc = launch<gemm8p_bwd_kernel<Epi8Scale>>(dim3((unsigned)(nbx1a * nby1a)), dim3(G2_THREADS), g8_lds_total, st, a1, s1, nbx1a, nby1a, a2, s2,
+                                                        cdiv(d, G2_B), 0, p.splits))
+        return rc;
     } else if (long_axis) {
       if (int rc = dprhot_dc(G, Q, B, Nc, d, h_scale, d_scale, dC_part, stream)) return rc;
     }
     const int nbx1 = cdiv(d, G2_B), nby1 = long_axis ? 0 : cdiv(Nc, G2_B), nbx2 = cdiv(d, G2_B), nby2 = cdiv(B, G2_B);
     const int grid = nbx1 * nby1 + nbx2 * nby2 * p.splits;
-    if (ok8) {
-      // the phase-interleaved schedule (gemm8pb.h): an even number of K steps per unit, byte offsets in 32 bits
-      auto k8 = gemm8p_bwd_kernel<Epi8Scale>;
-      static AttrOnce attr8_done;
-      if (!attr8_done) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(k8), hipFuncAttributeMaxDynamicSharedMemorySize, (int)g8_lds_total));
-        attr8_done = true;
-      }
-      const Epi8Scale s1{e1.out, e1.M, e1.N, e1.h_scale, e1.d_scale, e1.stamp_src, e1.stamp_period, e1.stamp_row};
-      const Epi8Scale s2{e2.out, e2.M, e2.N, e2.h_scale, e2.d_scale, e2.stamp_src, e2.stamp_period, e2.stamp_row};
-      hipLaunchKernelGGL(k8, dim3((unsigned)grid), dim3(G2_THREADS), g8_lds_total, st, a1, s1, nbx1, nby1, a2, s2, nbx2, nby2, p.splits);
-      HIP_TRY(hipGetLastError());
-      return launch_dq(G, C, B, Nc, d, h_scale, d_scale, dQ, ws, wl, st, /*gemm_too=*/false);
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G2_THREADS), g2_lds_total, st, a1, e1, nbx1, nby1, a2, e2, nbx2, nby2, p.splits);
-    HIP_TRY(hipGetLastError());
+    // ok8: the phase-interleaved schedule (gemm8pb.h): an even number of K steps per unit, byte offsets in 32 bits
+    const int rc = ok8 ? launch<gemm8p_bwd_kernel<Epi8Scale>>(dim3((unsigned)grid), dim3(G2_THREADS), g8_lds_total, st, a1, s1, nbx1, nby1, a2, s2, nbx2, nby2, p.splits)
+                       : launch<gemm256_bwd_kernel<EpiScaleF32>>(dim3((unsigned)grid), dim3(G2_THREADS), g2_lds_total, st, a1, e1, nbx1, nby1, a2, e2, nbx2, nby2, p.splits);
+    if (rc) return rc;
     return launch_dq(G, C, B, Nc, d, h_scale, d_scale, dQ, ws, wl, st, /*gemm_too=*/false);
   }
   const int t1 = dc_tile(B, Nc, d);
@@ -2092,23 +1886,10 @@ int dprhot_inbatch_step_f32(const float* q, const float* c, dprhot_bf16* Qb, dpr
   const int ncp = (Nc + 31) / 32 * 32;
   const dim3 grid(d / tw), block(1024);
   hipStream_t st = (hipStream_t)stream;
-#define DPRHOT_SS_LAUNCH_N(CPT, NS, NRB)                                                                                      \
-  do {                                                                                                                         \
-    auto kern = step_small_kernel<CPT, tw, NS, NRB>;                                                                             \
-    static size_t attr_dev[64] = {}; /* per device; benign race: idempotent */                                                 \
-    size_t& attr = attr_dev[lds > 48 * 1024 ? AttrOnce::cur() : 0];                                                            \
-    if (lds > 48 * 1024 && attr < lds) {                                                                                       \
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-      attr = lds;                                                                                                              \
-    }                                                                                                                          \
-    hipLaunchKernelGGL(kern, grid, block, lds, st, a);                                                                         \
-  } while (0)
-#define DPRHOT_SS_LAUNCH(CPT, NS)                      \
-  do {                                                 \
-    if (B <= SS_ROWS) DPRHOT_SS_LAUNCH_N(CPT, NS, 1);  \
-    else DPRHOT_SS_LAUNCH_N(CPT, NS, 2);               \
-  } while (0)
   if (lds > 160 * 1024 || fp.splits > 4) return fail(DPRHOT_E_UNSUPPORTED, "small step: Nc=%d needs %zu bytes of LDS", Nc, lds);
+  // (the LDS of all these kernels grows with Nc: launch() raises the limit again when a larger shape follows a smaller one)
+#define DPRHOT_BY_SLABS(LAUNCH, CPT) \
+  (fp.splits <= 1 ? LAUNCH(CPT, 1) : fp.splits == 2 ? LAUNCH(CPT, 2) : fp.splits == 3 ? LAUNCH(CPT, 3) : LAUNCH(CPT, 4))
   // the role-split forms (step_small_kernel_roles, step_small_kernel_out): one row block, the multi-slab plans up to 768 columns
   if (const int roles = opt(OPT_SMALL_STEP_ROLES); roles != 0 && B <= SS_ROWS && ncp <= 768) {
     const int qtw = roles >= 2 && d % 32 == 0 ? 32 : 16;
@@ -2117,66 +1898,26 @@ int dprhot_inbatch_step_f32(const float* q, const float* c, dprhot_bf16* Qb, dpr
     const bool outwg = roles == 3 && g_packed.stamp_src == nullptr;
     const size_t rlds = step_roles_lds(Nc, qtw);  // (the maximum over the roles, the output role included)
     const dim3 rgrid(d / 16 + 2 * (d / qtw) + (outwg ? 1 : 0));
-#define DPRHOT_SR_LAUNCH_K(KERN)                                                                                               \
-  do {                                                                                                                         \
-    auto kern = KERN;                                                                                                          \
-    static size_t attr_dev[64] = {}; /* per device; benign race: idempotent */                                                 \
-    size_t& attr = attr_dev[rlds > 48 * 1024 ? AttrOnce::cur() : 0];                                                           \
-    if (rlds > 48 * 1024 && attr < rlds) {                                                                                     \
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds)); \
-      attr = rlds;                                                                                                             \
-    }                                                                                                                          \
-    hipLaunchKernelGGL(kern, rgrid, block, rlds, st, a);                                                                       \
-  } while (0)
-#define DPRHOT_SR_LAUNCH_Q(CPT, NS, QTW)                                              \
-  do {                                                                                \
-    if (outwg) DPRHOT_SR_LAUNCH_K((step_small_kernel_out<CPT, NS, QTW>));             \
-    else DPRHOT_SR_LAUNCH_K((step_small_kernel_roles<CPT, NS, QTW>));                 \
-  } while (0)
-#define DPRHOT_SR_LAUNCH(CPT, NS)                        \
-  do {                                                   \
-    if (qtw == 16) DPRHOT_SR_LAUNCH_Q(CPT, NS, 16);      \
-    else DPRHOT_SR_LAUNCH_Q(CPT, NS, 32);                \
-  } while (0)
-#define DPRHOT_SR_LAUNCH_S(CPT)                          \
-  do {                                                   \
-    if (fp.splits <= 1) DPRHOT_SR_LAUNCH(CPT, 1);        \
-    else if (fp.splits == 2) DPRHOT_SR_LAUNCH(CPT, 2);   \
-    else if (fp.splits == 3) DPRHOT_SR_LAUNCH(CPT, 3);   \
-    else DPRHOT_SR_LAUNCH(CPT, 4);                       \
-  } while (0)
-    if (ncp <= 256) DPRHOT_SR_LAUNCH_S(1);
-    else if (ncp <= 512) DPRHOT_SR_LAUNCH_S(2);
-    else DPRHOT_SR_LAUNCH_S(3);
-#undef DPRHOT_SR_LAUNCH_S
+#define DPRHOT_SR_LAUNCH_K(KERN, CPT, NS, QTW) launch<KERN<CPT, NS, QTW>>(rgrid, block, rlds, st, a)
+#define DPRHOT_SR_LAUNCH_Q(CPT, NS, QTW) \
+  (outwg ? DPRHOT_SR_LAUNCH_K(step_small_kernel_out, CPT, NS, QTW) : DPRHOT_SR_LAUNCH_K(step_small_kernel_roles, CPT, NS, QTW))
+#define DPRHOT_SR_LAUNCH(CPT, NS) (qtw == 16 ? DPRHOT_SR_LAUNCH_Q(CPT, NS, 16) : DPRHOT_SR_LAUNCH_Q(CPT, NS, 32))
+    if (ncp <= 256) return DPRHOT_BY_SLABS(DPRHOT_SR_LAUNCH, 1);
+    if (ncp <= 512) return DPRHOT_BY_SLABS(DPRHOT_SR_LAUNCH, 2);
+    return DPRHOT_BY_SLABS(DPRHOT_SR_LAUNCH, 3);
 #undef DPRHOT_SR_LAUNCH
 #undef DPRHOT_SR_LAUNCH_Q
 #undef DPRHOT_SR_LAUNCH_K
-    HIP_TRY(hipGetLastError());
-    return DPRHOT_OK;
   }
-  if (ncp <= 256) {
-    if (fp.splits <= 1) DPRHOT_SS_LAUNCH(1, 1);
-    else if (fp.splits == 2) DPRHOT_SS_LAUNCH(1, 2);
-    else if (fp.splits == 3) DPRHOT_SS_LAUNCH(1, 3);
-    else DPRHOT_SS_LAUNCH(1, 4);
-  } else if (ncp <= 512) {
-    if (fp.splits <= 1) DPRHOT_SS_LAUNCH(2, 1);
-    else if (fp.splits == 2) DPRHOT_SS_LAUNCH(2, 2);
-    else if (fp.splits == 3) DPRHOT_SS_LAUNCH(2, 3);
-    else DPRHOT_SS_LAUNCH(2, 4);
-  } else if (ncp <= 768) {
-    if (fp.splits <= 1) DPRHOT_SS_LAUNCH(3, 1);
-    else if (fp.splits == 2) DPRHOT_SS_LAUNCH(3, 2);
-    else if (fp.splits == 3) DPRHOT_SS_LAUNCH(3, 3);
-    else DPRHOT_SS_LAUNCH(3, 4);
-  } else {
-    DPRHOT_SS_LAUNCH_N(5, 1, 1);  // (B <= 32 only: small_step_ok; above 768 columns the sim launch writes one slab: fwd_plan)
-  }
-#undef DPRHOT_SS_LAUNCH_N
+#define DPRHOT_SS_LAUNCH_N(CPT, NS, NRB) launch<step_small_kernel<CPT, tw, NS, NRB>>(grid, block, lds, st, a)
+#define DPRHOT_SS_LAUNCH(CPT, NS) (B <= SS_ROWS ? DPRHOT_SS_LAUNCH_N(CPT, NS, 1) : DPRHOT_SS_LAUNCH_N(CPT, NS, 2))
+  if (ncp <= 256) return DPRHOT_BY_SLABS(DPRHOT_SS_LAUNCH, 1);
+  if (ncp <= 512) return DPRHOT_BY_SLABS(DPRHOT_SS_LAUNCH, 2);
+  if (ncp <= 768) return DPRHOT_BY_SLABS(DPRHOT_SS_LAUNCH, 3);
+  return DPRHOT_SS_LAUNCH_N(5, 1, 1);  // (B <= 32 only: small_step_ok; above 768 columns the sim launch writes one slab: fwd_plan)
 #undef DPRHOT_SS_LAUNCH
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+#undef DPRHOT_SS_LAUNCH_N
+#undef DPRHOT_BY_SLABS
 }
 
 // World size > 1, everything after the all-gather in ONE call: the column mask is read from the packed buffer (no
@@ -2286,11 +2027,8 @@ int dprhot_rescale_grads(float* dQ, size_t n_dq, const float* dq_part, int nslab
   }
   const dim3 grid(nb), block(256);
   if (dc_kind == GC_FP32)
-    hipLaunchKernelGGL(rescale_grads_kernel<GC_FP32>, grid, block, 0, (hipStream_t)stream, dQ, n_dq / 8, dq_part, nslabs, nqb, dC, n_dc / 8, go, used, out2);
-  else
-    hipLaunchKernelGGL(rescale_grads_kernel<GC_BF16>, grid, block, 0, (hipStream_t)stream, dQ, n_dq / 8, dq_part, nslabs, nqb, dC, n_dc / 8, go, used, out2);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+    return launch<rescale_grads_kernel<GC_FP32>>(grid, block, 0, (hipStream_t)stream, dQ, n_dq / 8, dq_part, nslabs, nqb, dC, n_dc / 8, go, used, out2);
+  return launch<rescale_grads_kernel<GC_BF16>>(grid, block, 0, (hipStream_t)stream, dQ, n_dq / 8, dq_part, nslabs, nqb, dC, n_dc / 8, go, used, out2);
 }
 
 int dprhot_grad_pack(const float* bucket, size_t n, float scale, int wire, void* send, size_t n_padded, void* stream) {
@@ -2302,11 +2040,9 @@ int dprhot_grad_pack(const float* bucket, size_t n, float scale, int wire, void*
   REQUIRE(tiles < (1ull << 31), "n_padded=%zu", n_padded);
   const dim3 grid((unsigned)tiles), block(256);  // one workgroup per contiguous tile (gradcomm.h)
   hipStream_t st = (hipStream_t)stream;
-  if (wire == GC_BF16) hipLaunchKernelGGL(grad_pack_kernel<GC_BF16>, grid, block, 0, st, bucket, n, scale, send, n_padded);
-  else if (wire == GC_FP16) hipLaunchKernelGGL(grad_pack_kernel<GC_FP16>, grid, block, 0, st, bucket, n, scale, send, n_padded);
-  else hipLaunchKernelGGL(grad_pack_kernel<GC_FP32>, grid, block, 0, st, bucket, n, scale, send, n_padded);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  if (wire == GC_BF16) return launch<grad_pack_kernel<GC_BF16>>(grid, block, 0, st, bucket, n, scale, send, n_padded);
+  if (wire == GC_FP16) return launch<grad_pack_kernel<GC_FP16>>(grid, block, 0, st, bucket, n, scale, send, n_padded);
+  return launch<grad_pack_kernel<GC_FP32>>(grid, block, 0, st, bucket, n, scale, send, n_padded);
 }
 
 int dprhot_grad_sum_shards(const void* recv, int W, size_t shard, int wire, int out_kind, void* out, void* stream) {
@@ -2317,15 +2053,11 @@ int dprhot_grad_sum_shards(const void* recv, int W, size_t shard, int wire, int 
   REQUIRE(aligned16(recv) && aligned16(out), "pointers must be 16-byte aligned");
   const dim3 grid(gc_blocks(shard / 8)), block(256);
   hipStream_t st = (hipStream_t)stream;
-#define DPRHOT_GC_SUM(WK, OK) hipLaunchKernelGGL((grad_sum_shards_kernel<WK, OK>), grid, block, 0, st, recv, W, shard, out)
-  if (wire == GC_BF16 && out_kind == GC_BF16) DPRHOT_GC_SUM(GC_BF16, GC_BF16);
-  else if (wire == GC_BF16) DPRHOT_GC_SUM(GC_BF16, GC_FP32);
-  else if (wire == GC_FP16 && out_kind == GC_FP16) DPRHOT_GC_SUM(GC_FP16, GC_FP16);
-  else if (wire == GC_FP16) DPRHOT_GC_SUM(GC_FP16, GC_FP32);
-  else DPRHOT_GC_SUM(GC_FP32, GC_FP32);
-#undef DPRHOT_GC_SUM
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  if (wire == GC_BF16 && out_kind == GC_BF16) return launch<grad_sum_shards_kernel<GC_BF16, GC_BF16>>(grid, block, 0, st, recv, W, shard, out);
+  if (wire == GC_BF16) return launch<grad_sum_shards_kernel<GC_BF16, GC_FP32>>(grid, block, 0, st, recv, W, shard, out);
+  if (wire == GC_FP16 && out_kind == GC_FP16) return launch<grad_sum_shards_kernel<GC_FP16, GC_FP16>>(grid, block, 0, st, recv, W, shard, out);
+  if (wire == GC_FP16) return launch<grad_sum_shards_kernel<GC_FP16, GC_FP32>>(grid, block, 0, st, recv, W, shard, out);
+  return launch<grad_sum_shards_kernel<GC_FP32, GC_FP32>>(grid, block, 0, st, recv, W, shard, out);
 }
 
 int dprhot_grad_unpack(const void* full, int kind, float* bucket, size_t n, void* stream) {
@@ -2336,11 +2068,9 @@ int dprhot_grad_unpack(const void* full, int kind, float* bucket, size_t n, void
   REQUIRE(tiles < (1ull << 31), "n=%zu", n);
   const dim3 grid((unsigned)(tiles > 0 ? tiles : 1)), block(256);  // one workgroup per contiguous tile (gradcomm.h)
   hipStream_t st = (hipStream_t)stream;
-  if (kind == GC_BF16) hipLaunchKernelGGL(grad_unpack_kernel<GC_BF16>, grid, block, 0, st, full, bucket, n);
-  else if (kind == GC_FP16) hipLaunchKernelGGL(grad_unpack_kernel<GC_FP16>, grid, block, 0, st, full, bucket, n);
-  else hipLaunchKernelGGL(grad_unpack_kernel<GC_FP32>, grid, block, 0, st, full, bucket, n);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  if (kind == GC_BF16) return launch<grad_unpack_kernel<GC_BF16>>(grid, block, 0, st, full, bucket, n);
+  if (kind == GC_FP16) return launch<grad_unpack_kernel<GC_FP16>>(grid, block, 0, st, full, bucket, n);
+  return launch<grad_unpack_kernel<GC_FP32>>(grid, block, 0, st, full, bucket, n);
 }
 
 }  // extern "C"
@@ -2523,14 +2253,10 @@ int dprhot_maxsim_fwd(const void* q_tok, const void* c_tok, int Nq, int LQ, int 
   hipStream_t st = (hipStream_t)stream;
   const long ntiles = M > 0 ? (long)Nq * ((LQ + MS_BM - 1) / MS_BM) : ((long)Nq * LQ + MS_BM - 1) / MS_BM;
   const unsigned blocks = (unsigned)(ntiles * p.Ny);
-  if (KQ == 1) ms_launch_fwd<1>(p, blocks, st);
-  else if (KQ == 2) ms_launch_fwd<2>(p, blocks, st);
-  else if (KQ <= 4) ms_launch_fwd<4>(p, blocks, st);
-  else ms_launch_fwd<8>(p, blocks, st);
-  HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(ms_pool_kernel, dim3((unsigned)(((long)Nq * p.Ny + 3) / 4)), dim3(256), 0, st, p);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  const int r1 = KQ == 1 ? ms_launch_fwd<1>(p, blocks, st) : KQ == 2 ? ms_launch_fwd<2>(p, blocks, st)
+               : KQ <= 4 ? ms_launch_fwd<4>(p, blocks, st) : ms_launch_fwd<8>(p, blocks, st);
+  if (r1) return r1;
+  return launch<ms_pool_kernel>(dim3((unsigned)(((long)Nq * p.Ny + 3) / 4)), dim3(256), 0, st, p);
 }
 
 int dprhot_maxsim_bwd(const float* dS, const void* q_tok, const void* c_tok, int Nq, int LQ, int Nc, int LD, int dp, const int* q_ids,
@@ -2544,14 +2270,10 @@ int dprhot_maxsim_bwd(const float* dS, const void* q_tok, const void* c_tok, int
   MsBwd g{dS, dq, dc, q_w ? dwq : nullptr, q_w ? dwc : nullptr};
   if (!(dq || dc || g.dwq || g.dwc)) return DPRHOT_OK;
   hipStream_t st = (hipStream_t)stream;
-  int r2;
-  if (q_ids && q_w) r2 = ms_launch_bwd<true, true>(p, g, st);
-  else if (q_ids) r2 = ms_launch_bwd<true, false>(p, g, st);
-  else if (q_w) r2 = ms_launch_bwd<false, true>(p, g, st);
-  else r2 = ms_launch_bwd<false, false>(p, g, st);
-  if (r2) return r2;
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  if (q_ids && q_w) return ms_launch_bwd<true, true>(p, g, st);
+  if (q_ids) return ms_launch_bwd<true, false>(p, g, st);
+  if (q_w) return ms_launch_bwd<false, true>(p, g, st);
+  return ms_launch_bwd<false, false>(p, g, st);
 }
 
 // ---- CITADEL / SPLADE router head (csrc/router_head.h): entry points ----
@@ -2585,11 +2307,9 @@ int dprhot_router_head_fwd(const void* logits, int dtype, int B, int T1, int V, 
   a.repr = router_repr; a.arg = argmax; a.w = expert_weights; a.ids = expert_ids; a.rmask = router_mask; a.ssum = softmax_sum;
   a.lse = (float*)workspace;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == RH_FP32) rh_launch_fwd<RH_FP32>(a, st);
-  else if (dtype == RH_BF16) rh_launch_fwd<RH_BF16>(a, st);
-  else rh_launch_fwd<RH_FP16>(a, st);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  if (dtype == RH_FP32) return rh_launch_fwd<RH_FP32>(a, st);
+  if (dtype == RH_BF16) return rh_launch_fwd<RH_BF16>(a, st);
+  return rh_launch_fwd<RH_FP16>(a, st);
 }
 
 int dprhot_router_head_bwd(const void* logits, int dtype, int B, int T1, int V, int64_t stride_b, int64_t stride_t, const uint8_t* mask,
@@ -2615,11 +2335,9 @@ int dprhot_router_head_bwd(const void* logits, int dtype, int B, int T1, int V, 
   a.arg = const_cast<int*>(argmax); a.ids = const_cast<int*>(expert_ids); a.lse = (float*)const_cast<void*>(workspace);
   a.g_repr = g_router_repr; a.g_w = g_expert_weights; a.g_soft = g_softmax_sum; a.dx = dlogits;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == RH_FP32) rh_launch_bwd<RH_FP32>(a, st);
-  else if (dtype == RH_BF16) rh_launch_bwd<RH_BF16>(a, st);
-  else rh_launch_bwd<RH_FP16>(a, st);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  if (dtype == RH_FP32) return rh_launch_bwd<RH_FP32>(a, st);
+  if (dtype == RH_BF16) return rh_launch_bwd<RH_BF16>(a, st);
+  return rh_launch_bwd<RH_FP16>(a, st);
 }
 
 // ---- inverted-index retrieval (csrc/ivf.h) ----
@@ -2668,9 +2386,7 @@ int dprhot_ivf_score(const dprhot_bf16* post_vec, const int32_t* post_doc, const
   IvfArgs a{reinterpret_cast<const uint16_t*>(post_vec), post_doc, reinterpret_cast<const long long*>(exp_off), n_experts, dp,
             reinterpret_cast<const uint16_t*>(ent_vec), ent_q, bexp, bexp_off, n_bexp, nq, (long long)doc_begin, cols, S, (long long)ld};
   const unsigned blocks = (unsigned)cdiv(cdiv(cols, IVF_T), IVF_WAVES);
-  hipLaunchKernelGGL(ivf_score_kernel, dim3(blocks), dim3(64 * IVF_WAVES), 0, (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return DPRHOT_OK;
+  return launch<ivf_score_kernel>(dim3(blocks), dim3(64 * IVF_WAVES), 0, (hipStream_t)stream, a);
 }
 
 int dprhot_ivf_search(const dprhot_bf16* post_vec, const int32_t* post_doc, const int64_t* exp_off, int64_t n_postings, int n_experts, int dp,
