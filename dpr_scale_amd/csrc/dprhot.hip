@@ -1886,8 +1886,12 @@ int dprhot_inbatch_step_f32(const float* q, const float* c, dprhot_bf16* Qb, dpr
   const int ncp = (Nc + 31) / 32 * 32;
   const dim3 grid(d / tw), block(1024);
   hipStream_t st = (hipStream_t)stream;
-  if (lds > 160 * 1024 || fp.splits > 4) return fail(DPRHOT_E_UNSUPPORTED, "small step: Nc=%d needs %zu bytes of LDS", Nc, lds);
+  if (lds > 160 * 1024) return fail(DPRHOT_E_UNSUPPORTED, "small step: Nc=%d needs %zu bytes of LDS", Nc, lds);
   // (the LDS of all these kernels grows with Nc: launch() raises the limit again when a larger shape follows a smaller one)
+  // DPRHOT_BY_SLABS instantiates NS == max(fp.splits, 1): the role-split kernels read exactly NS slabs and add them all, with no
+  // run-time look at the slab count (step_small.h: ss_load_slabs), so a plan outside 0 .. 4 must never reach the macro
+  if (fp.splits < 0 || fp.splits > 4)
+    return fail(DPRHOT_E_UNSUPPORTED, "small step: the plan has %d slabs, the launch reads max(splits, 1) <= 4", fp.splits);
 #define DPRHOT_BY_SLABS(LAUNCH, CPT) \
   (fp.splits <= 1 ? LAUNCH(CPT, 1) : fp.splits == 2 ? LAUNCH(CPT, 2) : fp.splits == 3 ? LAUNCH(CPT, 3) : LAUNCH(CPT, 4))
   // the role-split forms (step_small_kernel_roles, step_small_kernel_out): one row block, the multi-slab plans up to 768 columns

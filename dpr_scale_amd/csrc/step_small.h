@@ -404,8 +404,10 @@ __global__ __launch_bounds__(1024) void step_small_kernel(StepSmallArgs p) {
 //                                                   step_small_kernel -- and it ended the launch 0.36 us behind the other 47.
 //                                                   step_small_kernel_out (form 3): one output workgroup of the same grid that has
 //                                                   no product to do; every dC workgroup is a plain one.
-// Every value is formed by the instruction sequence of step_small_kernel -- the softmax below is its text -- so the outputs are the
-// same bits (tests/test_small_step_roles.py, tests/test_small_step_out.py).
+// Every value is formed by the arithmetic instructions of step_small_kernel in their order -- the softmax below is its text without
+// the selects, compares, address arithmetic and LDS lane exchanges that change no value -- so the outputs are the same bits, and
+// step_small_kernel, which is left exactly as it was, is the reference they are compared with (tests/test_small_step_roles.py,
+// tests/test_small_step_out.py, tests/test_small_step_lean.py).
 inline size_t step_roles_lds(int Nc, int QTW) {
   const int ncp = (Nc + 31) / 32 * 32, gs = ncp + 8;
   const size_t dc = (size_t)SS_ROWS * gs * 2 + (size_t)SS_ROWS * 24 * 2 + SS_MAXB * sizeof(float);
@@ -419,72 +421,104 @@ inline size_t step_roles_lds(int Nc, int QTW) {
 // exponential per score, G (bf16) into row `lrow` of the LDS image.  Returns the row loss (lane tr == 0 uses it).
 // G_IMAGE = false (the output role: nobody reads its image) drops the LDS store of G and nothing else: the values are formed all
 // the same for the global store.
-template <int CPT, int NS, bool G_IMAGE = true>
+// Every workgroup of the launch repeats this text on four SIMDs, so its VALU instructions ARE the launch's critical path.  It forms
+// every value with the arithmetic instructions of step_small_kernel, in their order, and spends nothing else ("the lean
+// row softmax"):
+//   NS is the number of slabs, by contract with the launcher (NS == max(splits, 1)): no run-time `z < p.splits` select at the add.
+//   FULL (B == 32 and Nc == 256 * CPT, compile-time): every row and every chunk is there -- no -inf select, no guard, no zero fill.
+//   A dead row takes one select on the subtrahend (exp(-inf - 0) = +0, what the select on the result gave), not one per score.
+//   The gold column is the element dg = yi - c0 of the thread's chunk, a compare against a constant per element.
+//   The two 16-lane halves of a row meet through v_permlane16_swap, not through LDS (ss_pair16).
+
+// x of lanes l and l ^ 16, side by side in every lane.  v_permlane16_swap with D = S = x exchanges the odd 16-lane rows of D with the
+// even rows of S: afterwards r[0] = x[l & ~16] and r[1] = x[l | 16] in EVERY lane l.  Here a query row is 32 lanes (tr = tid & 31:
+// lanes 0-31 of a wave are row 2w, lanes 32-63 row 2w + 1), so lanes tr and tr ^ 16 -- the two DPP rows of ONE query row -- meet, and
+// the two query rows of the wave never mix.  Lanes 0-15 / 32-47 combine (own, other) as __shfl_xor(x, 16) had them, lanes 16-31 /
+// 48-63 (other, own): max and a two-term sum are commutative, so all 32 lanes of the row hold the bits they held before.  (The one
+// non-commutative case of v_max_f32 is max(+0, -0): the sign of a zero row maximum reaches no output -- exp(+-0) = 1, and
+// lse = m + log(sum) with sum >= 1 has log(sum) >= +0, which absorbs it.)
+__device__ __forceinline__ void ss_pair16(float x, float& even, float& odd) {
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+  even = __uint_as_float(r[0]);
+  odd = __uint_as_float(r[1]);
+}
+
+template <int CPT, int NS, bool FULL, bool G_IMAGE = true>
 __device__ __forceinline__ float ss_row_softmax(const StepSmallArgs& p, float4 (&sa)[CPT][NS], float4 (&sb)[CPT][NS], int row, bool active,
                                                 int64_t yraw, int tr, bool lead, uint16_t* Gs_row, int ncp) {
-  const int Nc = p.Nc, cpr = Nc >> 3;
+  const int Nc = FULL ? 256 * CPT : p.Nc, cpr = Nc >> 3;
   float v[CPT][8];
 #pragma unroll
   for (int k = 0; k < CPT; ++k) {
     float4 a = sa[k][0], b = sb[k][0];
 #pragma unroll
-    for (int z = 1; z < NS; ++z) {
-      const bool on = z < p.splits;
-      a.x += on ? sa[k][z].x : 0.f; a.y += on ? sa[k][z].y : 0.f; a.z += on ? sa[k][z].z : 0.f; a.w += on ? sa[k][z].w : 0.f;
-      b.x += on ? sb[k][z].x : 0.f; b.y += on ? sb[k][z].y : 0.f; b.z += on ? sb[k][z].z : 0.f; b.w += on ? sb[k][z].w : 0.f;
+    for (int z = 1; z < NS; ++z) {  // slab order 0, 1, 2, 3
+      a.x += sa[k][z].x; a.y += sa[k][z].y; a.z += sa[k][z].z; a.w += sa[k][z].w;
+      b.x += sb[k][z].x; b.y += sb[k][z].y; b.z += sb[k][z].z; b.w += sb[k][z].w;
     }
-    const bool ok = active && (tr + k * 32) < cpr;
-    v[k][0] = ok ? a.x : -INFINITY; v[k][1] = ok ? a.y : -INFINITY; v[k][2] = ok ? a.z : -INFINITY; v[k][3] = ok ? a.w : -INFINITY;
-    v[k][4] = ok ? b.x : -INFINITY; v[k][5] = ok ? b.y : -INFINITY; v[k][6] = ok ? b.z : -INFINITY; v[k][7] = ok ? b.w : -INFINITY;
+    if constexpr (FULL) {
+      v[k][0] = a.x; v[k][1] = a.y; v[k][2] = a.z; v[k][3] = a.w;
+      v[k][4] = b.x; v[k][5] = b.y; v[k][6] = b.z; v[k][7] = b.w;
+    } else {
+      const bool ok = active && (tr + k * 32) < cpr;
+      v[k][0] = ok ? a.x : -INFINITY; v[k][1] = ok ? a.y : -INFINITY; v[k][2] = ok ? a.z : -INFINITY; v[k][3] = ok ? a.w : -INFINITY;
+      v[k][4] = ok ? b.x : -INFINITY; v[k][5] = ok ? b.y : -INFINITY; v[k][6] = ok ? b.z : -INFINITY; v[k][7] = ok ? b.w : -INFINITY;
+    }
   }
-  const int yi = active ? (int)(yraw + p.y_offset) : -1;
+  const int yi = FULL || active ? (int)(yraw + p.y_offset) : -1;
   float m = -INFINITY;
 #pragma unroll
   for (int k = 0; k < CPT; ++k)
 #pragma unroll
     for (int e = 0; e < 8; ++e) m = fmaxf(m, v[k][e]);
   m = dprhot_row16_max(m);
-  m = fmaxf(m, __shfl_xor(m, 16));
+  float even, odd;
+  ss_pair16(m, even, odd);
+  m = fmaxf(even, odd);
   float sm = 0.f, gold = 0.f;  // exactly one lane of the row holds the gold column
+  unsigned dg[CPT];            // ... as element dg of its chunk k (dg < 8 there, and nowhere else; yi = -1 matches nothing)
 #pragma unroll
   for (int k = 0; k < CPT; ++k) {
-    const int c0 = (tr + k * 32) * 8;
+    dg[k] = (unsigned)yi - (unsigned)((tr + k * 32) * 8);
 #pragma unroll
     for (int e = 0; e < 8; ++e)
-      if (yi == c0 + e) gold = v[k][e];
+      if (dg[k] == (unsigned)e) gold = v[k][e];
   }
   float ex[CPT][8];
   const bool dead = m == -INFINITY;  // a row with every column masked (the reference yields NaN there as well)
+  const float m0 = dead ? 0.f : m;   // every score of a dead row is -inf: exp(-inf - 0) = +0
 #pragma unroll
   for (int k = 0; k < CPT; ++k)
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      ex[k][e] = dead ? 0.f : __expf(v[k][e] - m);
+      ex[k][e] = __expf(v[k][e] - m0);
       sm += ex[k][e];
     }
   sm = dprhot_row16_sum(sm);
   gold = dprhot_row16_sum(gold);
-  sm += __shfl_xor(sm, 16);
-  gold += __shfl_xor(gold, 16);
+  ss_pair16(sm, even, odd);
+  sm = even + odd;
+  ss_pair16(gold, even, odd);
+  gold = even + odd;
   const float lse = m + logf(sm);
   const float inv_sm = 1.0f / sm;  // sm = 0 (dead row): inf * 0 = NaN, like exp(v - lse) with lse = NaN
-  const float l = active ? lse - gold : 0.f;
-  if (tr == 0 && lead && active) {
+  const float l = FULL || active ? lse - gold : 0.f;
+  if (tr == 0 && lead && (FULL || active)) {
     if (p.row_lse) p.row_lse[row] = lse;
     if (p.row_loss) p.row_loss[row] = l;
   }
 #pragma unroll
   for (int k = 0; k < CPT; ++k) {
     const int chunk = tr + k * 32;
-    if (chunk * 8 < ncp) {
+    if (FULL || chunk * 8 < ncp) {
       uint4 gv = make_uint4(0u, 0u, 0u, 0u);
-      if (active && chunk < cpr) {
+      if (FULL || (active && chunk < cpr)) {
         const int c0 = chunk * 8;
         float gg[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
           float pr = ex[k][e] * inv_sm;
-          if (c0 + e == yi) pr -= 1.0f;
+          if (dg[k] == (unsigned)e) pr -= 1.0f;
           gg[e] = pr * p.grad_scale;
         }
         gv = make_uint4(pk_bf16(gg[0], gg[1]), pk_bf16(gg[2], gg[3]), pk_bf16(gg[4], gg[5]), pk_bf16(gg[6], gg[7]));
@@ -503,18 +537,18 @@ __device__ __forceinline__ float ss_row_softmax(const StepSmallArgs& p, float4 (
   return l;
 }
 
-// the thread's chunks of every slab, issued back to back on valid addresses (absent slabs re-read slab 0: step_small_kernel)
-template <int CPT, int NS>
+// the thread's chunks of all NS slabs, issued back to back: slab z is one base plus z uniform strides
+template <int CPT, int NS, bool FULL>
 __device__ __forceinline__ void ss_load_slabs(const StepSmallArgs& p, float4 (&sa)[CPT][NS], float4 (&sb)[CPT][NS], int row, bool active, int tr) {
-  const int Nc = p.Nc, cpr = Nc >> 3;
+  const int Nc = FULL ? 256 * CPT : p.Nc, cpr = Nc >> 3;
 #pragma unroll
   for (int k = 0; k < CPT; ++k) {
     const int chunk = tr + k * 32;
-    const bool ok = active && chunk < cpr;
+    const bool ok = FULL || (active && chunk < cpr);  // (an absent chunk re-reads the first one and is dropped by the softmax)
     const float* src = p.slabs + (ok ? (size_t)row * Nc + (size_t)chunk * 8 : (size_t)0);
 #pragma unroll
     for (int z = 0; z < NS; ++z) {
-      const float* sz = src + (z < p.splits ? (size_t)z * p.slab_stride : (size_t)0);
+      const float* sz = src + (size_t)z * p.slab_stride;
       sa[k][z] = *reinterpret_cast<const float4*>(sz);
       sb[k][z] = *reinterpret_cast<const float4*>(sz + 4);
     }
@@ -526,11 +560,12 @@ __device__ __forceinline__ void ss_load_slabs(const StepSmallArgs& p, float4 (&s
 // dC role: dC_part[0:Nc, n0:n0+16] = G^T x Q[:, n0:n0+16] for column tile `tile`.  LEAD: the workgroup of tile 0 also writes the
 // loss / logsumexp / G / logits and, in the stamping launch of the packed step, the loss into its column 0 of dC (forms 1, 2);
 // false: no workgroup of this role does (form 3).
-template <int CPT, int NS, bool LEAD>
+// FULL (every role): B == 32 and Nc == 256 * CPT, known at compile time -- see ss_row_softmax.
+template <int CPT, int NS, bool LEAD, bool FULL>
 __device__ __forceinline__ void ss_role_dc(const StepSmallArgs& p, uint16_t* Gs, int tile) {  // Gs: [32][gs]  G, row-major
   constexpr int TW = 16, TS = TW + 8, TC = TW / 8;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int Nc = p.Nc;
+  const int Nc = FULL ? 256 * CPT : p.Nc, B = FULL ? SS_ROWS : p.B;
   const int ncp = (Nc + 31) / 32 * 32, gs = ncp + 8;
   const int lrow = tid >> 5, tr = tid & 31;
   const float dsc = p.d_scale ? *p.d_scale : 1.0f;
@@ -542,15 +577,15 @@ __device__ __forceinline__ void ss_role_dc(const StepSmallArgs& p, uint16_t* Gs,
   float* const s_rl = reinterpret_cast<float*>(Qs + SS_ROWS * TS);  // [32] row losses
   DPRHOT_TMB(1, 0);
   const int row = lrow;
-  const bool active = row < p.B;
+  const bool active = FULL || row < B;
   const int64_t yraw = active ? p.y[row] : (int64_t)-1;
   uint4 qreg = make_uint4(0u, 0u, 0u, 0u);
   if (active && tr < TC) qreg = *reinterpret_cast<const uint4*>(p.Qb + (size_t)row * p.d + n0 + tr * 8);
   float4 sa[CPT][NS], sb[CPT][NS];
-  ss_load_slabs<CPT, NS>(p, sa, sb, row, active, tr);
+  ss_load_slabs<CPT, NS, FULL>(p, sa, sb, row, active, tr);
   DPRHOT_TMB(1, 1);
   if (tr < TC) *reinterpret_cast<uint4*>(Qs + lrow * TS + tr * 8) = qreg;
-  const float l = ss_row_softmax<CPT, NS>(p, sa, sb, row, active, yraw, tr, lead, Gs + lrow * gs, ncp);
+  const float l = ss_row_softmax<CPT, NS, FULL>(p, sa, sb, row, active, yraw, tr, lead, Gs + lrow * gs, ncp);
   if constexpr (LEAD) {
     if (tr == 0) s_rl[lrow] = l;
   }
@@ -561,7 +596,7 @@ __device__ __forceinline__ void ss_role_dc(const StepSmallArgs& p, uint16_t* Gs,
   if (lead) {                                     // workgroup-uniform
     if (tid == 0) {
       double tot = 0.0;
-      for (int r = 0; r < p.B; ++r) tot += (double)s_rl[r];
+      for (int r = 0; r < B; ++r) tot += (double)s_rl[r];
       p.loss_sum[0] = (float)tot * p.loss_scale;
       s_rl[0] = (float)tot * p.loss_scale;  // (row losses are no longer needed) for the stamp below
     }
@@ -593,30 +628,30 @@ __device__ __forceinline__ void ss_role_dc(const StepSmallArgs& p, uint16_t* Gs,
 }
 
 // dQ role: dQ[r0:r0+16, n0:n0+QTW] = G[r0:r0+16, :] x C[:, n0:n0+QTW] for column tile qt and 16-row half `half`
-template <int CPT, int NS, int QTW>
+template <int CPT, int NS, int QTW, bool FULL>
 __device__ __forceinline__ void ss_role_dq(const StepSmallArgs& p, uint16_t* Gs, int qt, int half) {  // Gs: [16][gs]  G, row-major
   constexpr int QTS = QTW + 8, QTC = QTW / 8, NF = QTW / 16;
   constexpr int CUQ = (256 * CPT * QTC + 511) / 512;  // C-tile chunks per thread of waves 8-15
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int Nc = p.Nc;
+  const int Nc = FULL ? 256 * CPT : p.Nc, B = FULL ? SS_ROWS : p.B;
   const int ncp = (Nc + 31) / 32 * 32, gs = ncp + 8;
   const int lrow = tid >> 5, tr = tid & 31;
   const float dsc = p.d_scale ? *p.d_scale : 1.0f;
   const float sc = p.h_scale * dsc;
   const int i = lane & 15, g = lane >> 4;
   const int n0 = qt * QTW, r0 = half * 16;
-  if (r0 >= p.B) return;  // (fewer rows than one half: nothing of dQ is this block's to write)
+  if (r0 >= B) return;  // (fewer rows than one half: nothing of dQ is this block's to write)
   uint16_t* const Cs = Gs + 16 * gs;                             // [ncp][QTS]  C[:, n0:n0+QTW]
   float* const red = reinterpret_cast<float*>(Cs + ncp * QTS);   // [8][16][QTW] dQ partial sums
   DPRHOT_TMB(2, 0);
   if (tid < 512) {  // waves 0-7: the softmax of the half's 16 rows
     const int row = r0 + lrow;
-    const bool active = row < p.B;
+    const bool active = FULL || row < B;
     const int64_t yraw = active ? p.y[row] : (int64_t)-1;
     float4 sa[CPT][NS], sb[CPT][NS];
-    ss_load_slabs<CPT, NS>(p, sa, sb, row, active, tr);
+    ss_load_slabs<CPT, NS, FULL>(p, sa, sb, row, active, tr);
     DPRHOT_TMB(2, 1);
-    (void)ss_row_softmax<CPT, NS>(p, sa, sb, row, active, yraw, tr, false, Gs + lrow * gs, ncp);
+    (void)ss_row_softmax<CPT, NS, FULL>(p, sa, sb, row, active, yraw, tr, false, Gs + lrow * gs, ncp);
   } else {  // waves 8-15: the C tile
     const int t2 = tid - 512;
     uint4 creg[CUQ];
@@ -657,7 +692,7 @@ __device__ __forceinline__ void ss_role_dq(const StepSmallArgs& p, uint16_t* Gs,
   DPRHOT_TMB(2, 4);
   if (tid < 16 * QTW) {  // add the 8 K slices in order
     const int e = tid, r = e / QTW, ccol = e - r * QTW;
-    if (r0 + r < p.B) {
+    if (r0 + r < B) {
       float s = red[e];
 #pragma unroll
       for (int k = 1; k < 8; ++k) s += red[k * 16 * QTW + e];
@@ -670,19 +705,20 @@ __device__ __forceinline__ void ss_role_dq(const StepSmallArgs& p, uint16_t* Gs,
 // output role (form 3): what the lead did besides its dC tile, and nothing else -- the full softmax with its stores of G, the logits,
 // logsumexp and row loss (ss_row_softmax with lead = true: the same bits), then the loss.  No Q tile, no C tile, no product, and no
 // G image in LDS.
-template <int CPT, int NS>
+template <int CPT, int NS, bool FULL>
 __device__ __forceinline__ void ss_role_out(const StepSmallArgs& p, float* s_rl) {  // s_rl: [32] row losses
   const int tid = threadIdx.x, lane = tid & 63;
-  const int ncp = (p.Nc + 31) / 32 * 32;
+  const int Nc = FULL ? 256 * CPT : p.Nc, B = FULL ? SS_ROWS : p.B;
+  const int ncp = (Nc + 31) / 32 * 32;
   const int lrow = tid >> 5, tr = tid & 31;
   DPRHOT_TMB(3, 0);
   const int row = lrow;
-  const bool active = row < p.B;
+  const bool active = FULL || row < B;
   const int64_t yraw = active ? p.y[row] : (int64_t)-1;
   float4 sa[CPT][NS], sb[CPT][NS];
-  ss_load_slabs<CPT, NS>(p, sa, sb, row, active, tr);
+  ss_load_slabs<CPT, NS, FULL>(p, sa, sb, row, active, tr);
   DPRHOT_TMB(3, 1);
-  const float l = ss_row_softmax<CPT, NS, false>(p, sa, sb, row, active, yraw, tr, true, nullptr, ncp);
+  const float l = ss_row_softmax<CPT, NS, FULL, false>(p, sa, sb, row, active, yraw, tr, true, nullptr, ncp);
   if (tr == 0) s_rl[lrow] = l;
   DPRHOT_TMB(3, 2);
   __syncthreads();
@@ -699,7 +735,7 @@ __device__ __forceinline__ void ss_role_out(const StepSmallArgs& p, float* s_rl)
 #pragma unroll
     for (int r = 0; r < SS_ROWS; ++r) {
       const double xr = __hiloint2double(__builtin_amdgcn_readlane(mhi, r), __builtin_amdgcn_readlane(mlo, r));
-      x[r] = r < p.B ? xr : 0.0;
+      x[r] = r < B ? xr : 0.0;
     }
     double tot = 0.0;
 #pragma unroll
@@ -711,14 +747,13 @@ __device__ __forceinline__ void ss_role_out(const StepSmallArgs& p, float* s_rl)
 
 // CPT, NS: as in step_small_kernel (CPT <= 3).  QTW: columns of d per dQ workgroup (16 or 32; d % QTW == 0).
 // Grid: d / 16 dC blocks, then 2 * d / QTW dQ blocks.
-template <int CPT, int NS, int QTW>
-__global__ __launch_bounds__(1024) void step_small_kernel_roles(StepSmallArgs p) {
-  extern __shared__ __attribute__((aligned(16))) uint16_t ss_smem[];
+template <int CPT, int NS, int QTW, bool FULL>
+__device__ __forceinline__ void ss_roles_block(const StepSmallArgs& p, uint16_t* smem) {
   const int ndc = p.d / 16;  // dC blocks
   if ((int)blockIdx.x < ndc) {
     // the XCD-aware tile mapping of step_small_kernel (linear ids are dealt round-robin to the 8 XCDs)
     const int tile = (ndc % 8 == 0) ? ((int)blockIdx.x % 8) * (ndc / 8) + (int)blockIdx.x / 8 : (int)blockIdx.x;
-    ss_role_dc<CPT, NS, true>(p, ss_smem, tile);
+    ss_role_dc<CPT, NS, true, FULL>(p, smem, tile);
     return;
   }
   const int u = (int)blockIdx.x - ndc, nqt = p.d / QTW;
@@ -732,7 +767,15 @@ __global__ __launch_bounds__(1024) void step_small_kernel_roles(StepSmallArgs p)
     qt = u % nqt;
     half = u / nqt;
   }
-  ss_role_dq<CPT, NS, QTW>(p, ss_smem, qt, half);
+  ss_role_dq<CPT, NS, QTW, FULL>(p, smem, qt, half);
+}
+// FULL is chosen HERE, from the arguments the role bodies index with, by one workgroup-uniform scalar branch: a kernel cannot be
+// launched with a flag that its B and Nc do not bear out, and the launcher keeps one instantiation per (CPT, NS, QTW).
+template <int CPT, int NS, int QTW>
+__global__ __launch_bounds__(1024) void step_small_kernel_roles(StepSmallArgs p) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t ss_smem[];
+  if (p.B == SS_ROWS && p.Nc == 256 * CPT) ss_roles_block<CPT, NS, QTW, true>(p, ss_smem);
+  else ss_roles_block<CPT, NS, QTW, false>(p, ss_smem);
 }
 
 // Form 3.  Grid: ONE output block, then d / 16 dC blocks, then 2 * d / QTW dQ blocks.
@@ -744,18 +787,17 @@ __global__ __launch_bounds__(1024) void step_small_kernel_roles(StepSmallArgs p)
 // Block index b -> XCD is b % 8, so the tile mappings below are computed from the physical index b, not from b - 1: the blocks of
 // XCD x are b = x + 8 k (x = 0: 8 + 8 k), k = (b - 1) / 8 counts them, and XCD x owns the same contiguous run of column tiles in
 // both roles -- the neighbouring tiles of one 128-byte line of Q / C rows still meet in one L2.
-template <int CPT, int NS, int QTW>
-__global__ __launch_bounds__(1024) void step_small_kernel_out(StepSmallArgs p) {
-  extern __shared__ __attribute__((aligned(16))) uint16_t ss_smem[];
+template <int CPT, int NS, int QTW, bool FULL>
+__device__ __forceinline__ void ss_out_block(const StepSmallArgs& p, uint16_t* smem) {
   const int b = (int)blockIdx.x;
   if (b == 0) {
-    ss_role_out<CPT, NS>(p, reinterpret_cast<float*>(ss_smem));
+    ss_role_out<CPT, NS, FULL>(p, reinterpret_cast<float*>(smem));
     return;
   }
   const int ndc = p.d / 16, nqt = p.d / QTW;
   if (b <= ndc) {
     const int tile = (ndc % 8 == 0) ? (b % 8) * (ndc / 8) + (b - 1) / 8 : b - 1;
-    ss_role_dc<CPT, NS, false>(p, ss_smem, tile);
+    ss_role_dc<CPT, NS, false, FULL>(p, smem, tile);
     return;
   }
   const int u = b - 1 - ndc;
@@ -768,7 +810,13 @@ __global__ __launch_bounds__(1024) void step_small_kernel_out(StepSmallArgs p) {
     qt = u % nqt;
     half = u / nqt;
   }
-  ss_role_dq<CPT, NS, QTW>(p, ss_smem, qt, half);
+  ss_role_dq<CPT, NS, QTW, FULL>(p, smem, qt, half);
+}
+template <int CPT, int NS, int QTW>
+__global__ __launch_bounds__(1024) void step_small_kernel_out(StepSmallArgs p) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t ss_smem[];
+  if (p.B == SS_ROWS && p.Nc == 256 * CPT) ss_out_block<CPT, NS, QTW, true>(p, ss_smem);  // (FULL: see step_small_kernel_roles)
+  else ss_out_block<CPT, NS, QTW, false>(p, ss_smem);
 }
 
 }  // namespace dprhot
