@@ -33,6 +33,7 @@
 #include "wideselect.h"
 #include "maxsim.h"
 #include "ivf.h"
+#include "ivf_pack.h"
 #include "router_head.h"
 
 using namespace dprhot;
@@ -2443,6 +2444,45 @@ int dprhot_ivf_search(const dprhot_bf16* post_vec, const int32_t* post_doc, cons
     }
   }
   return DPRHOT_OK;
+}
+
+// ---- postings and query batches from encoder outputs (csrc/ivf_pack.h) ----
+int dprhot_ivf_compact(const int32_t* expert_ids, const float* weights, const uint8_t* att, const int32_t* row_ids, int B, int L, int K,
+                       int test_weight, float min_weight, int32_t* seq_off, int32_t* out_expert, int32_t* out_row, int32_t* out_slot,
+                       float* out_weight, int64_t capacity, void* stream) {
+  REQUIRE(K >= 1 && K <= 8, "K=%d out of range (1 .. 8)", K);
+  REQUIRE(L >= 1, "L=%d: at least one token", L);
+  REQUIRE(B >= 1 && B <= 65535, "B=%d out of range (1 .. 65535)", B);
+  REQUIRE((long long)B * L * K < (1ll << 31), "B L K = %lld must stay below 2^31", (long long)B * L * K);
+  REQUIRE(expert_ids && att && row_ids, "NULL pointer (expert_ids, att and row_ids are required)");
+  REQUIRE(seq_off && out_expert && out_row && out_slot && out_weight, "NULL pointer (outputs)");
+  REQUIRE(capacity >= 0, "capacity=%lld", (long long)capacity);
+  IvfCompactArgs a{expert_ids, weights, att, row_ids, B, L, K, test_weight != 0, min_weight, seq_off, out_expert, out_row, out_slot,
+                   out_weight, (long long)capacity};
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)cdiv(B, IVFP_WAVES)), block(64 * IVFP_WAVES);
+  if (int rc = launch<ivf_count_kernel>(grid, block, 0, st, a)) return rc;
+  if (int rc = launch<ivf_scan_kernel>(dim3(1), dim3(256), 0, st, seq_off, B)) return rc;
+  return launch<ivf_emit_kernel>(grid, block, 0, st, a);
+}
+
+int dprhot_ivf_gather(const float* repr, int64_t repr_ld, int64_t n_rows, const float* weights, const int32_t* slot, const int64_t* perm,
+                      int64_t n, int d, int K, int prod_round, int entry_round, int out_kind, void* out, int64_t out_ld, void* stream) {
+  REQUIRE(d >= 1 && out_ld >= d && repr_ld >= d, "bad shape d=%d out_ld=%lld repr_ld=%lld", d, (long long)out_ld, (long long)repr_ld);
+  REQUIRE(K >= 1 && K <= 8, "K=%d out of range (1 .. 8)", K);
+  REQUIRE(n >= 0 && n < (1ll << 31), "n=%lld out of range (0 .. 2^31 - 1)", (long long)n);
+  REQUIRE(n_rows >= 1, "n_rows=%lld", (long long)n_rows);
+  REQUIRE(prod_round == IVFP_FP32 || prod_round == IVFP_BF16 || prod_round == IVFP_FP16, "unknown prod_round %d", prod_round);
+  REQUIRE(entry_round == 0 || entry_round == 1, "unknown entry_round %d", entry_round);
+  REQUIRE(out_kind == IVFP_FP32 || out_kind == IVFP_BF16, "unknown out_kind %d", out_kind);
+  if (n == 0) return DPRHOT_OK;
+  REQUIRE(repr && slot && out, "NULL pointer (repr, slot and out are required)");
+  const long long blocks = (n * out_ld + 255) / 256;
+  REQUIRE(blocks <= 0x7fffffffLL, "n=%lld rows of %lld columns: too many elements for one launch", (long long)n, (long long)out_ld);
+  IvfGatherArgs a{repr, (long long)repr_ld, (long long)n_rows, weights, slot, reinterpret_cast<const long long*>(perm), (long long)n, d, K,
+                  prod_round, entry_round, out, (long long)out_ld};
+  if (out_kind == IVFP_BF16) return launch<ivf_gather_kernel<IVFP_BF16>>(dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  return launch<ivf_gather_kernel<IVFP_FP32>>(dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
 }
 
 }  // extern "C"

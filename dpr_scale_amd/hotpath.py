@@ -79,6 +79,7 @@ def _ptr(t):
 
 
 _RH_DTYPE = {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}  # the dtype codes of dprhot_router_head_*
+_IVF_ROUND = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # DPRHOT_IVF_FP32 / _BF16 / _FP16 of dprhot_ivf_gather
 
 
 class HipKernels:
@@ -593,6 +594,57 @@ class HipKernels:
                                                    0 if index.cls is None else index.cls.shape[0], index.corpus_len, int(id_begin),
                                                    int(id_end), values.shape[1], int(chunk), _ptr(values), _ptr(indices),
                                                    int(bool(first)), _ptr(ws), ws.numel(), self._stream()), "dprhot_ivf_search")
+
+    # -- postings and query batches from encoder outputs (csrc/ivf_pack.h; dpr_scale_amd/ivf.py drives them) ----
+    def ivf_compact(self, expert_ids, weights, att, row_ids, test_weight, min_weight=0.0, capacity=None):
+        """The kept slots of a repr dict in (b, t, k) order (dprhot_ivf_compact).  expert_ids [B, L, K] of any integer type, weights
+        [B, L, K] or None (all 1), att [B, L] (> 0 = a real token), row_ids [B].  Returns (n, largest count of one sequence, seq_off
+        int32 [B + 1], expert, row, slot int32 [m], weight fp32 [m]) with m = min(n, capacity); capacity defaults to the worst case
+        B L K.  n and the largest count come to the host in ONE transfer (the call's only synchronisation)."""
+        self._require_gpu(expert_ids, weights, att, row_ids)
+        B, L, K = expert_ids.shape
+        dev = expert_ids.device
+        ids = expert_ids.detach().to(torch.int32).contiguous()
+        w = None if weights is None else weights.detach().to(torch.float32).contiguous()
+        a8 = (att.detach() > 0).to(torch.uint8).contiguous()
+        rows = row_ids.detach().to(torch.int32).contiguous()
+        assert a8.shape == (B, L) and rows.shape == (B,) and (w is None or w.shape == ids.shape)
+        cap = B * L * K if capacity is None else int(capacity)
+        seq_off = torch.empty(B + 1, dtype=torch.int32, device=dev)
+        expert, row, slot = (torch.empty(max(cap, 1), dtype=torch.int32, device=dev) for _ in range(3))  # (never a NULL pointer)
+        weight = torch.empty(max(cap, 1), dtype=torch.float32, device=dev)
+        self._lib.check(self.lib.dprhot_ivf_compact(_ptr(ids), _ptr(w), _ptr(a8), _ptr(rows), B, L, K, int(bool(test_weight)),
+                                                    float(min_weight), _ptr(seq_off), _ptr(expert), _ptr(row), _ptr(slot), _ptr(weight),
+                                                    cap, self._stream()), "dprhot_ivf_compact")
+        n, most = torch.stack([seq_off[B], (seq_off[1:] - seq_off[:-1]).max()]).tolist()
+        m = min(n, cap)
+        return n, most, seq_off, expert[:m], row[:m], slot[:m], weight[:m]
+
+    def ivf_gather(self, expert_repr, weights, slot, perm, K, entry_fp16, out_dtype, out_ld=None):
+        """out [n, out_ld] (fp32 or bf16): row i = weight * token row of record perm[i] (record i without perm), rounded as torch rounds
+        in the host loops -- the product to P, then to fp16 when entry_fp16, then to out_dtype (dprhot_ivf_gather).  P is the dtype of
+        `one weight * one token row`, torch.result_type of a 0-dim weight and the row: the row's dtype, and torch casts the weight to
+        it before it multiplies.  expert_repr [..., d] and weights [..., K] come in their own dtypes; the widening of P to fp32 done
+        here is exact."""
+        self._require_gpu(expert_repr, weights, slot, perm)
+        d = int(expert_repr.shape[-1])
+        prod = expert_repr.dtype if weights is None else torch.result_type(weights.new_zeros(()), expert_repr)
+        if prod not in _IVF_ROUND or out_dtype not in (torch.float32, _BF16):
+            raise TypeError(f"ivf_gather: product of {prod}, output of {out_dtype}; fp32, bf16 and fp16 products, fp32 and bf16 outputs")
+        x = expert_repr.detach().reshape(-1, d).to(torch.float32)
+        if x.stride(1) != 1 or x.stride(0) < d:
+            x = x.contiguous()
+        w = None if weights is None else weights.detach().to(prod).to(torch.float32).contiguous()
+        assert w is None or w.numel() == x.shape[0] * K
+        n = int(slot.shape[0])
+        out_ld = d if out_ld is None else int(out_ld)
+        out = torch.empty((n, out_ld), dtype=out_dtype, device=x.device)
+        assert slot.dtype == torch.int32 and slot.is_contiguous() and (perm is None or (perm.dtype == torch.int64 and perm.is_contiguous()
+                                                                                        and perm.shape[0] == n))
+        self._lib.check(self.lib.dprhot_ivf_gather(_ptr(x), x.stride(0), x.shape[0], _ptr(w), _ptr(slot), _ptr(perm), n, d, int(K),
+                                                   _IVF_ROUND[prod], int(bool(entry_fp16)), _IVF_ROUND[out_dtype], _ptr(out), out_ld,
+                                                   self._stream()), "dprhot_ivf_gather")
+        return out
 
 
 _DEFAULT = None

@@ -13,6 +13,11 @@ Precision: operands are rounded to bf16 once (round to nearest even) when the in
 exact in fp32 and accumulation is fp32 (csrc/ivf.h, DESIGN.md section 10).  Scoring and top-k run in libdprhot.so (dprhot_ivf_search);
 there is no torch fallback.
 
+Building both sides on the device ("Building postings and query batches"): `pack_queries_device` makes the
+packed query batch and `IndexBuilder` the postings -- the on-disk tree above or an IVFIndex -- straight from the encoders' repr tensors,
+with the kept slots listed and the weighted vectors written by libdprhot.so (dprhot_ivf_compact / dprhot_ivf_gather) in the order and
+with the roundings of the host loops they replace.
+
 Not supported (NotImplementedError / out of scope): product quantisation, `portion` < 1, hnsw, expert parallelism across GPUs, ColBERT.
 """
 import collections
@@ -32,7 +37,7 @@ KNARROW = 4096                # largest k of dprhot_topk_update; beyond it the H
 def _pad_cols(x, mult):
     pad = (-x.shape[1]) % mult
     if pad:
-        x = torch.cat([x, torch.zeros((x.shape[0], pad), dtype=x.dtype)], 1)
+        x = torch.cat([x, torch.zeros((x.shape[0], pad), dtype=x.dtype, device=x.device)], 1)
     return x
 
 
@@ -252,3 +257,206 @@ def load_index(ctx_embeddings_dir, corpus_len, device=None, chunk=None, kernels=
     device = torch.device(device) if device is not None else torch.device("cuda", 0)
     experts, docs, vecs, cls = read_postings(ctx_embeddings_dir, int(corpus_len))
     return IVFIndex(experts, docs, vecs, cls, corpus_len, device, chunk=chunk, kernels=kernels)
+
+
+# ---- both sides from the encoders' repr tensors, on the device ----------------------------------------------------------------------
+
+def query_dicts(queries_repr, n):
+    """The query side of the reference's retrieval step (citadel_retrieval_task.py:104-125) on the host: per query a dict
+    {expert_id: [weighted vector, ...]} and the same for the weights (fp32 for COIL, fp16 and zero weights dropped for CITADEL)."""
+    coil = queries_repr["expert_ids"].dim() == 2
+    # one transfer instead of one per token: the per-token work below is host work on small tensors
+    reprs, ids, wts, att = (queries_repr[k].cpu() for k in ("expert_repr", "expert_ids", "expert_weights", "attention_mask"))
+    batch_embeddings, batch_weights = [], []
+    for b in range(n):
+        embeddings, weights = collections.defaultdict(list), collections.defaultdict(list)
+        for x, e, w, a in zip(reprs[b], ids[b], wts[b], att[b]):
+            if a > 0:
+                if coil:  # fp32 entries (:116-117)
+                    embeddings[e.item()].append((w * x).to(torch.float32))
+                    weights[e.item()].append(w.to(torch.float32))
+                else:  # CITADEL: fp16 entries, zero weights dropped (:119-122)
+                    for ek, wk in zip(e, w):
+                        if wk > 0:
+                            embeddings[ek.item()].append((wk * x).to(torch.float16))
+                            weights[ek.item()].append(wk.to(torch.float16))
+        batch_embeddings.append(embeddings)
+        batch_weights.append(weights)
+    return batch_embeddings, batch_weights
+
+
+def _default_kernels(kernels):
+    if kernels is None:
+        from . import hotpath
+
+        kernels = hotpath.default_kernels()
+    return kernels
+
+
+def _slots(repr_, n=None):
+    """(expert_repr [n, L, d], expert_ids [n, L, K], expert_weights [n, L, K], attention_mask [n, L], coil) of a repr dict."""
+    x, ids, w, att = (repr_[k].detach() for k in ("expert_repr", "expert_ids", "expert_weights", "attention_mask"))
+    if n is not None:
+        x, ids, w, att = x[:n], ids[:n], w[:n], att[:n]
+    coil = ids.dim() == 2
+    if coil:
+        ids, w = ids.unsqueeze(-1), w.unsqueeze(-1)
+    if ids.dim() != 3 or w.shape != ids.shape or x.shape[:2] != ids.shape[:2] or att.shape != ids.shape[:2]:
+        raise ValueError(f"repr dict: expert_repr {tuple(x.shape)}, expert_ids {tuple(ids.shape)}, expert_weights {tuple(w.shape)}, "
+                         f"attention_mask {tuple(att.shape)} do not belong together")
+    return x, ids, w, att, coil
+
+
+def query_entries(queries_repr, n=None, kernels=None):
+    """The entries of a query batch as the reference's query writer lists them (citadel_eval_task.py:153-170), on the device of the
+    repr tensors and in emission order (query, token, slot): (expert int32 [E], query row int32 [E], weight fp32 [E], vec fp32 [E, d])
+    with vec = weight * expert_repr in expert_repr's dtype, widened.  COIL keeps every attended token, CITADEL every attended
+    slot of weight > 0."""
+    kn = _default_kernels(kernels)
+    x, ids, w, att, coil = _slots(queries_repr, n)
+    rows = torch.arange(ids.shape[0], dtype=torch.int32, device=ids.device)
+    _, _, _, expert, row, slot, weight = kn.ivf_compact(ids, w, att, rows, not coil, 0.0)
+    return expert, row, weight, kn.ivf_gather(x, w, slot, None, ids.shape[2], False, torch.float32, None)
+
+
+def pack_queries_device(queries_repr, batch_cls, n=None, kernels=None):
+    """What pack_queries(batch_cls, *query_dicts(queries_repr, n)).to(device) returns, tensor for tensor, built on the device of the
+    repr tensors: the kept slots come from dprhot_ivf_compact in (query, token, slot) order, a stable sort by expert makes that
+    (expert, query, listed order), and dprhot_ivf_gather writes the bf16 entries through the host path's roundings (product in the
+    token rows' dtype; CITADEL: then fp16; then bf16)."""
+    kn = _default_kernels(kernels)
+    x, ids, w, att, coil = _slots(queries_repr, n)
+    nq, d, dev = int(ids.shape[0]), int(x.shape[-1]), x.device
+    if nq == 0:
+        raise ValueError("empty query batch")
+    rows = torch.arange(nq, dtype=torch.int32, device=dev)
+    E, most, seq_off, expert, row, slot, _ = kn.ivf_compact(ids, w, att, rows, not coil, 0.0)
+    if most > MAX_ENTRIES_PER_QUERY:
+        q = int(torch.nonzero(seq_off[1:] - seq_off[:-1] > MAX_ENTRIES_PER_QUERY)[0])
+        raise ValueError(f"query {q} has {int(seq_off[q + 1] - seq_off[q])} entries; at most {MAX_ENTRIES_PER_QUERY} are supported")
+    dp = (d + 31) // 32 * 32
+    if E:
+        key, order = torch.sort(expert.long(), stable=True)  # stable: (query, token, slot) survives inside an expert
+        ent_vec = kn.ivf_gather(x, w, slot, order.contiguous(), ids.shape[2], not coil, _BF16, dp)
+        ent_q = row[order].contiguous()
+        bexp, counts = torch.unique_consecutive(key, return_counts=True)
+        boff = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(counts, 0)]).to(torch.int32)
+        bexp = bexp.to(torch.int32)
+    else:
+        ent_vec = torch.zeros((0, dp), dtype=_BF16, device=dev)
+        ent_q = torch.zeros(0, dtype=torch.int32, device=dev)
+        bexp, boff = torch.zeros(0, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+    cls = None
+    if torch.is_tensor(batch_cls) and batch_cls.numel() > 0:
+        if batch_cls.shape[0] != nq:
+            raise ValueError("batch_cls and batch_embeddings differ in length")
+        cls = _pad_cols(batch_cls.detach().to(dev, torch.float32), 8).to(_BF16).contiguous()
+    return QueryBatch(nq, ent_vec, ent_q, bexp, boff, cls)
+
+
+def postings_from_repr(contexts_repr, corpus_ids, weight_threshold=0.0, kernels=None):
+    """The postings of one context batch as the reference's index writer lists them (citadel_eval_task.py:51-69), on the device of the
+    repr tensors and in emission order (passage, token, slot): (expert int32 [P], doc int32 [P], weight fp32 [P], slot int32 [P],
+    vec fp32 [P, d]) with vec = weight * expert_repr in expert_repr's dtype, widened.  COIL (2-D ids) keeps weights > 0,
+    CITADEL weights > weight_threshold (strictly)."""
+    kn = _default_kernels(kernels)
+    x, ids, w, att, coil = _slots(contexts_repr)
+    docs = torch.as_tensor(corpus_ids).to(x.device)
+    thr = 0.0 if coil else float(weight_threshold)
+    if w.is_floating_point():  # torch compares a tensor with a Python number in the tensor's dtype
+        thr = float(torch.tensor(thr, dtype=torch.float64).to(w.dtype))
+    _, _, _, expert, doc, slot, weight = kn.ivf_compact(ids, w, att, docs, True, thr)
+    vec = kn.ivf_gather(x, w, slot, None, ids.shape[2], False, torch.float32, None)
+    return expert, doc, weight, slot, vec
+
+
+class IndexBuilder:
+    """Collects the postings of context batches on the device and turns them into the reference's on-disk index (`write`) or straight
+    into an IVFIndex (`finish`), which equals load_index of the tree `write` produces.  `corpus_len` is needed by `finish` only."""
+
+    def __init__(self, corpus_len, device=None, kernels=None):
+        self.corpus_len = None if corpus_len is None else int(corpus_len)
+        self.device = None if device is None else torch.device(device)
+        self.kn = kernels
+        self.parts, self.cls_parts = [], []
+
+    def add(self, contexts_repr, corpus_ids, weight_threshold=0.0, context_ids=None):
+        """One context batch.  `context_ids` [B, L] (CITADEL only: the writer's add_context_id): every attended slot is kept whatever
+        its weight and the third column of the files is the slot's token id instead of its vector."""
+        self.kn = _default_kernels(self.kn)
+        if context_ids is not None and contexts_repr["expert_ids"].dim() == 3:
+            x, ids, w, att, _ = _slots(contexts_repr)
+            docs = torch.as_tensor(corpus_ids).to(x.device)
+            _, _, _, expert, doc, slot, weight = self.kn.ivf_compact(ids, w, att, docs, False, 0.0)
+            tok = context_ids.detach().to(x.device)[:, : ids.shape[1]].reshape(-1)
+            vec = tok[(slot // ids.shape[2]).long()].to(torch.float32)
+        else:
+            expert, doc, weight, slot, vec = postings_from_repr(contexts_repr, corpus_ids, weight_threshold, self.kn)
+        self.parts.append((expert, doc, weight, vec))
+        if "cls_repr" in contexts_repr:
+            self.cls_parts.append(contexts_repr["cls_repr"].detach().to(torch.float32))
+        return int(expert.shape[0])
+
+    def _cat(self):
+        if not self.parts:
+            raise ValueError("no context batch was added")
+        return tuple(torch.cat([p[i] for p in self.parts], 0) for i in range(4))
+
+    def by_expert(self):
+        """Host tensors of everything added, stably sorted by expert: (expert ids [V'], their posting counts [V'], doc int64 [P],
+        weight fp32 [P], vec fp32 [P, d]) -- what `write` cuts into files."""
+        expert, doc, weight, vec = self._cat()
+        key, order = torch.sort(expert.long(), stable=True)
+        ids, counts = torch.unique_consecutive(key, return_counts=True)
+        return ids.cpu(), counts.cpu(), doc[order].long().cpu(), weight[order].cpu(), vec[order].cpu()
+
+    def write(self, ctx_embeddings_dir, rank=0):
+        """expert_{rank:04}/{id}.pkl = (ids int64, weights fp32, reprs fp32) in emission order per expert, cls_{rank:04}.pkl fp32 [docs,
+        dc] when the batches carried cls_repr: the files of citadel_eval_task.py:75-117, pickle protocol 4."""
+        ids, counts, doc, weight, vec = self.by_expert()
+        if self.cls_parts:
+            with open(os.path.join(ctx_embeddings_dir, f"cls_{rank:04}.pkl"), "wb") as f:
+                pickle.dump(torch.cat(self.cls_parts, 0).cpu(), f, protocol=4)
+        out_dir = os.path.join(ctx_embeddings_dir, f"expert_{rank:04}")
+        os.makedirs(out_dir, exist_ok=True)
+        lo = 0
+        for e, c in zip(ids.tolist(), counts.tolist()):
+            with open(os.path.join(out_dir, f"{e}.pkl"), "wb") as f:  # clones: a pickled view would carry the whole storage
+                pickle.dump((doc[lo:lo + c].clone(), weight[lo:lo + c].clone(), vec[lo:lo + c].clone()), f, protocol=4)
+            lo += c
+        return ctx_embeddings_dir
+
+    def finish(self, chunk=None):
+        """The IVFIndex of everything added: postings stably sorted by (expert, doc), vectors rounded to bf16 and padded to a multiple
+        of 32 columns by dprhot_ivf_gather, CLS rows with their zero tail."""
+        if self.corpus_len is None or not 0 < self.corpus_len < 2 ** 31:
+            raise ValueError(f"corpus_len={self.corpus_len} out of range (1 .. 2^31 - 1)")
+        expert, doc, _, vec = self._cat()
+        if vec.dim() != 2:
+            raise ValueError("postings that carry token ids (add_context_id) make no index")
+        P, d = int(vec.shape[0]), int(vec.shape[1])
+        if P == 0:
+            raise ValueError("no posting was added")
+        lo_hi = torch.stack([doc.min(), doc.max(), expert.min(), expert.max()]).tolist()
+        if lo_hi[0] < 0 or lo_hi[1] >= self.corpus_len or lo_hi[2] < 0:
+            raise ValueError("doc ids must lie in [0, corpus_len) and expert ids must be non-negative")
+        if lo_hi[3] >= 2 ** 31 - 1:
+            raise ValueError("expert ids must fit int32")
+        dev = vec.device
+        order = torch.sort(expert.long() * self.corpus_len + doc.long(), stable=True).indices.contiguous()
+        counts = torch.bincount(expert.long(), minlength=lo_hi[3] + 1)
+        exp_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(counts, 0)]).contiguous()
+        slot = torch.arange(P, dtype=torch.int32, device=dev)
+        post_vec = self.kn.ivf_gather(vec, None, slot, order, 1, False, _BF16, (d + 31) // 32 * 32)
+        post_doc = doc[order].to(torch.int32).contiguous()
+        cls_rows = None
+        if self.cls_parts:
+            cls = torch.cat(self.cls_parts, 0)
+            if cls.shape[0] != self.corpus_len:
+                raise ValueError(f"{cls.shape[0]} CLS rows for {self.corpus_len} passages")
+            c = _pad_cols(cls, 8).to(_BF16)
+            cls_rows = torch.cat([c, torch.zeros((8, c.shape[1]), dtype=_BF16, device=dev)], 0).contiguous()
+        out = [post_doc, post_vec, exp_off, cls_rows]
+        if self.device is not None and self.device != dev:
+            out = [None if t is None else t.to(self.device) for t in out]
+        return IVFIndex.from_packed(*out, self.corpus_len, d, chunk=chunk, kernels=self.kn)

@@ -2,7 +2,8 @@
 
 Same constructor kwargs (:15-30), `_eval_step` (:84-140), `test_epoch_end` (:145-177), `merge_trec_results` (:179-201) and
 `merge_qa_results` (:204-231).  The reference builds `self.index` from dpr_scale/index/inverted_vector_index.py, which it does not
-ship; here the index is dpr_scale_amd.ivf.load_index (one device-resident inverted index, scored by libdprhot.so).
+ship; here the index is dpr_scale_amd.ivf.load_index (one device-resident inverted index, scored by libdprhot.so).  Query batches whose
+repr tensors are on the index's device are packed there (ivf.pack_queries_device; `device_pack = False` keeps the host loop).
 
 Scope: `quantizer="pq"`, `cuda=False`, `portion` below 1.0 and `hnsw_index` raise NotImplementedError; `expert_parallel` (the
 reference's split of experts across GPUs) is accepted and ignored: the index lives on one device.
@@ -47,6 +48,8 @@ class PassageTable:
 
 
 class CITADELRetrievalTask(MultiVecRetrieverTask):
+    device_pack = True  # pack query batches on the device when the encoder outputs and the index live there (False: the host loop)
+
     def __init__(
         self,
         ctx_embeddings_dir,
@@ -107,25 +110,16 @@ class CITADELRetrievalTask(MultiVecRetrieverTask):
         questions = batch["question"] if "question" in batch else []
         queries_repr = {k: v.detach() for k, v in self(query_ids).items()}
         batch_cls = queries_repr["cls_repr"] if "cls_repr" in queries_repr else []
-        coil = queries_repr["expert_ids"].dim() == 2
         n = len(topic_ids) if len(topic_ids) > 0 else len(query_ids["input_ids"])
-        # one transfer instead of one per token: the per-token work below is host work on small tensors
-        reprs, ids, wts, att = (queries_repr[k].cpu() for k in ("expert_repr", "expert_ids", "expert_weights", "attention_mask"))
-        batch_embeddings, batch_weights = [], []
-        for b in range(n):
-            embeddings, weights = collections.defaultdict(list), collections.defaultdict(list)
-            for x, e, w, a in zip(reprs[b], ids[b], wts[b], att[b]):
-                if a > 0:
-                    if coil:  # fp32 entries (:116-117)
-                        embeddings[e.item()].append((w * x).to(torch.float32))
-                        weights[e.item()].append(w.to(torch.float32))
-                    else:  # CITADEL: fp16 entries, zero weights dropped (:119-122)
-                        for ek, wk in zip(e, w):
-                            if wk > 0:
-                                embeddings[ek.item()].append((wk * x).to(torch.float16))
-                                weights[ek.item()].append(wk.to(torch.float16))
-            batch_embeddings.append(embeddings)
-            batch_weights.append(weights)
+        if self.device_pack and queries_repr["expert_repr"].is_cuda and self.index.device.type == "cuda":
+            # the batch is packed where the encoder left it (ivf.pack_queries_device): same tensors as the host path below, bit for bit
+            qb = ivf.pack_queries_device(queries_repr, batch_cls, n, kernels=self.index._kernels())
+            self.latency["encode_time"] += time.perf_counter() - tic
+            tic = time.perf_counter()
+            batch_top_scores, batch_top_ids = self.index.search_packed(qb, self.topk)
+            self.index.latency["search_time"] += time.perf_counter() - tic
+            return batch_top_scores.cpu().tolist(), batch_top_ids.cpu().tolist(), topic_ids, questions, answers
+        batch_embeddings, batch_weights = ivf.query_dicts(queries_repr, n)
         self.latency["encode_time"] += time.perf_counter() - tic
         batch_top_scores, batch_top_ids = self.index.search(batch_cls, batch_embeddings, batch_weights, self.topk)
         return batch_top_scores.cpu().tolist(), batch_top_ids.cpu().tolist(), topic_ids, questions, answers

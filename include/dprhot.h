@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DPRHOT_VERSION 174 /* 0.1.74: + dprhot_ivf_workspace_bytes / _score / _search (inverted-index retrieval for CITADEL / COIL); dprhot_router_head_* joined without a bump: tests/test_ivf.py pins this number */
+#define DPRHOT_VERSION 174 /* 0.1.74: + dprhot_ivf_workspace_bytes / _score / _search (inverted-index retrieval for CITADEL / COIL); dprhot_router_head_* and dprhot_ivf_compact / _gather joined without a bump: tests/test_ivf.py pins this number */
 
 #define DPRHOT_OK 0
 #define DPRHOT_E_INVALID (-1)     /* bad argument (NULL pointer, non-positive or misaligned size) */
@@ -349,6 +349,35 @@ int dprhot_ivf_search(const dprhot_bf16* post_vec, const int32_t* post_doc, cons
                       int n_bexp, int nq, const dprhot_bf16* cls_q, const dprhot_bf16* cls_doc, int dc, int64_t cls_rows,
                       int64_t corpus_len, int64_t id_begin, int64_t id_end, int k, int chunk, float* values, int64_t* indices, int first,
                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* From encoder outputs to index postings and query batches (csrc/ivf_pack.h, DESIGN.md section 10, "Building postings and query
+ * batches"): the per-token loops of the reference's citadel_eval_task.py:43-70 and citadel_retrieval_task.py:104-125 as two operations.
+ * dprhot_ivf_compact lists the kept slots of a repr dict.  expert_ids int32 [B, L, K], weights fp32 [B, L, K] or NULL (every weight 1),
+ * att uint8 [B, L], row_ids int32 [B] (the corpus id or the query row of a sequence).  Slot (b, t, k) is kept when att[b, t] > 0 and
+ * (test_weight == 0 or weight > min_weight; a NaN weight is never kept).  seq_off int32 [B + 1]: seq_off[b] = kept slots of the
+ * sequences before b, seq_off[B] = their total n.  Record r is the r-th kept slot in (b, t, k) order: out_expert[r] its expert id,
+ * out_row[r] = row_ids[b], out_slot[r] = (b L + t) K + k, out_weight[r] its weight.  Records at or beyond `capacity` (the length of
+ * the four record arrays) are not written and the call still returns OK: the caller reads seq_off[B].  One wave per sequence, ranks by
+ * ballot: no atomics, every element has one owner, two runs are bit-identical.
+ * Limits (DPRHOT_E_INVALID): 1 <= K <= 8, L >= 1, 1 <= B <= 65535, B L K < 2^31.
+ * dprhot_ivf_gather writes the weighted vectors of n records: output row i takes record r = perm[i] (r = i when perm is NULL), token
+ * row slot[r] / K of repr fp32 [n_rows, d] (row stride repr_ld elements) and weight weights[slot[r]] (1 when NULL):
+ *   v = round_prod(w * x)  ->  entry_round == DPRHOT_IVF_ENTRY_FP16: v = fp16(v)  ->  out fp32: v;  out bf16: bf16(v)
+ * every rounding to nearest even, the product one plain fp32 multiply; round_prod rounds to prod_round (fp32: nothing); out_kind is
+ * DPRHOT_IVF_FP32 or DPRHOT_IVF_BF16.  This is what
+ * torch computes on the host for a weight and a row of the dtype prod_round names (their widening to fp32 is exact).  Columns d .. out_ld - 1 are
+ * written as zeros; a record outside [0, n) or a slot outside the n_rows K slots gives a row of zeros.  n == 0 launches nothing.
+ * Limits (DPRHOT_E_INVALID): d >= 1, out_ld >= d, repr_ld >= d, 1 <= K <= 8, 0 <= n < 2^31, n_rows >= 1. */
+#define DPRHOT_IVF_FP32 0
+#define DPRHOT_IVF_BF16 1
+#define DPRHOT_IVF_FP16 2
+#define DPRHOT_IVF_ENTRY_NONE 0
+#define DPRHOT_IVF_ENTRY_FP16 1
+int dprhot_ivf_compact(const int32_t* expert_ids, const float* weights, const uint8_t* att, const int32_t* row_ids, int B, int L, int K,
+                       int test_weight, float min_weight, int32_t* seq_off, int32_t* out_expert, int32_t* out_row, int32_t* out_slot,
+                       float* out_weight, int64_t capacity, void* stream);
+int dprhot_ivf_gather(const float* repr, int64_t repr_ld, int64_t n_rows, const float* weights, const int32_t* slot, const int64_t* perm,
+                      int64_t n, int d, int K, int prod_round, int entry_round, int out_kind, void* out, int64_t out_ld, void* stream);
 
 /* The CITADEL / SPLADE encoder head behind the MLM logits (dpr_scale/models/citadel_models/citadel_model.py:46-82, splade_model.py:26-32;
  * csrc/router_head.h), forward and backward without a [B, T, V] temporary.  logits [B, T1, V] of `dtype` (0 bf16,
