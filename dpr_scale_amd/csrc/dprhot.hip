@@ -976,6 +976,17 @@ static int ms_launch_fwd(const MsArgs& p, unsigned blocks, hipStream_t st) {
   return launch<ms_fwd_kernel<KQT, false, false>>(dim3(blocks), dim3(256), 0, st, p);
 }
 
+static_assert(MS_SC_SLOTS == DPRHOT_MAXSIM_MAX_LEN * MS_KMAX, "ms_score_kernel's LDS table holds every row slot of one query");
+
+template <int KQT>
+static int ms_launch_score(const MsArgs& p, hipStream_t st) {
+  const dim3 grid((unsigned)p.Nc), block(256);
+  if (p.qid && p.qw) return launch<ms_score_kernel<KQT, true, true>>(grid, block, 0, st, p);
+  if (p.qid) return launch<ms_score_kernel<KQT, true, false>>(grid, block, 0, st, p);
+  if (p.qw) return launch<ms_score_kernel<KQT, false, true>>(grid, block, 0, st, p);
+  return launch<ms_score_kernel<KQT, false, false>>(grid, block, 0, st, p);
+}
+
 template <bool IDS, bool W>
 static int ms_launch_bwd(const MsArgs& p, const MsBwd& g, hipStream_t st) {
   const int R = p.Nq * p.LQ;
@@ -2262,6 +2273,30 @@ int dprhot_maxsim_fwd(const void* q_tok, const void* c_tok, int Nq, int LQ, int 
                : KQ <= 4 ? ms_launch_fwd<4>(p, blocks, st) : ms_launch_fwd<8>(p, blocks, st);
   if (r1) return r1;
   return launch<ms_pool_kernel>(dim3((unsigned)(((long)Nq * p.Ny + 3) / 4)), dim3(256), 0, st, p);
+}
+
+int dprhot_maxsim_score(const void* q_tok, const void* c_tok, int Nq, int LQ, int Nc, int LD, int dp, const int* q_ids, const int* c_ids,
+                        const float* q_w, const float* c_w, int KQ, int KD, int pool, int M, const uint8_t* mask, float* S, void* stream) {
+  REQUIRE(Nq >= 0 && Nc >= 0 && LQ > 0 && LD > 0, "bad shape Nq=%d LQ=%d Nc=%d LD=%d", Nq, LQ, Nc, LD);
+  REQUIRE(LQ <= DPRHOT_MAXSIM_MAX_LEN && LD <= DPRHOT_MAXSIM_MAX_LEN, "LQ=%d LD=%d: token counts are limited to %d", LQ, LD,
+          DPRHOT_MAXSIM_MAX_LEN);
+  REQUIRE(dp >= 32 && dp % 32 == 0, "dp=%d must be a positive multiple of 32 (zero-pad the features)", dp);
+  REQUIRE(KQ >= 1 && KQ <= MS_KMAX && KD >= 1 && KD <= MS_KMAX, "KQ=%d KD=%d: expert slots per token are limited to 1..%d", KQ, KD,
+          MS_KMAX);
+  REQUIRE((q_ids == nullptr) == (c_ids == nullptr), "expert ids are required on both sides or on neither");
+  REQUIRE((q_w == nullptr) == (c_w == nullptr), "expert weights are required on both sides or on neither");
+  REQUIRE(q_ids || (KQ == 1 && KD == 1), "KQ=%d KD=%d without expert ids (ColBERT has one slot per token)", KQ, KD);
+  REQUIRE(pool == DPRHOT_POOL_SUM || pool == DPRHOT_POOL_MAX, "pool=%d (0 sum, 1 max)", pool);
+  REQUIRE(M >= 1 && (long)Nq * M == (long)Nc, "pairwise: M=%d must be at least 1 and Nc=%d equal Nq * M = %d * %d", M, Nc, Nq, M);
+  if (Nc == 0) return DPRHOT_OK;
+  REQUIRE(q_tok && c_tok && S, "NULL pointer (q_tok, c_tok and S are required)");
+  REQUIRE(((uintptr_t)q_tok & 15) == 0 && ((uintptr_t)c_tok & 15) == 0, "token rows must be 16-byte aligned");
+  REQUIRE((long)Nq * LQ * KQ <= 0x7fffffffL && (long)Nc * LD * KD <= 0x7fffffffL, "too many token slots");
+  const MsArgs p{(const uint16_t*)q_tok, (const uint16_t*)c_tok, q_ids, c_ids, q_w, c_w, mask, Nq, LQ, Nc, LD, dp, KQ, KD, M, M, pool,
+                 nullptr, nullptr, nullptr, nullptr, S};
+  hipStream_t st = (hipStream_t)stream;
+  return KQ == 1 ? ms_launch_score<1>(p, st) : KQ == 2 ? ms_launch_score<2>(p, st)
+       : KQ <= 4 ? ms_launch_score<4>(p, st) : ms_launch_score<8>(p, st);
 }
 
 int dprhot_maxsim_bwd(const float* dS, const void* q_tok, const void* c_tok, int Nq, int LQ, int Nc, int LD, int dp, const int* q_ids,

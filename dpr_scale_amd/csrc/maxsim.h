@@ -11,6 +11,7 @@
 //   ms_fwd_kernel   the token GEMM on v_mfma_f32_16x16x32_bf16, a running (max, argmax) per row slot in the epilogue; writes the
 //                   [Ny, Nq*LQ*KQ] value / argmax tables (and the raw dot product at the argmax when weights are present)
 //   ms_pool_kernel  one wave per (q, y): sum or max over the query's row slots, -inf at masked contexts
+//   ms_score_kernel forward only, pairwise: both of the above in one launch, no tables (one workgroup per (q, y); see its comment)
 //   ms_dq_kernel    backward, one wave per row: gathers the selected context rows in a fixed (kq, y) order; dW_q
 //   ms_dc_kernel    backward, one workgroup per (context, 64-feature slice): wave w owns context tokens j = w (mod 4) and adds the
 //                   selected query rows into an LDS accumulator in increasing row-slot order; dW_c
@@ -213,6 +214,149 @@ __global__ __launch_bounds__(256) void ms_pool_kernel(MsArgs p) {
     p.S[pair] = (p.mask && p.mask[ctx]) ? -INFINITY : acc;
     if (p.pool) p.parg[pair] = q * n + (ai == MS_NONE ? 0 : ai);
   }
+}
+
+// Score only (inference: reranking aligned pairs): ms_fwd_kernel + ms_pool_kernel in pairwise mode as ONE launch with no tables.
+// One workgroup per (q, y), blockIdx.x = ctx = q * M + y.  The query's rows go in tiles of 16 * nrf tokens, nrf = 1 (LQ <= 16),
+// 2 (LQ <= 32) or 4 MFMA row fragments; wave w works on fragment w % nrf and column group w / nrf, and the 4 / nrf column groups take
+// alternate 64-token chunks of the passage -- so four waves stay busy at a rerank query's 32 tokens.  ms_better is a total order, so
+// its maximum does not depend on how the columns are split.  Each wave leaves its row slots' (max, argmax) in LDS, one plane per
+// column group (argmax planes exist only where there is more than one group: they settle equal values, +0 against -0, as the
+// tables' lowest-index rule does).  After one barrier wave 0 merges the planes and pools the n = LQ * KQ slots in ms_pool_kernel's
+// order -- lane l takes slots l, l + 64, ... in increasing order, then the xor tree 32 .. 1 -- so the fp32 sum is the same to the bit.
+constexpr int MS_SC_SLOTS = 512 * MS_KMAX;     // LQ <= 512 (DPRHOT_MAXSIM_MAX_LEN): 4096 row slots, the 16 KiB value table
+constexpr int MS_SC_SPLIT = 32 * MS_KMAX * 2;  // LQ <= 32: at most 4 planes x 16 tokens x 8 = 2 planes x 32 tokens x 8 slots
+
+template <int KQT, bool IDS, bool W>
+__global__ __launch_bounds__(256) void ms_score_kernel(MsArgs p) {
+  __shared__ float tab[MS_SC_SLOTS];
+  __shared__ int tix[MS_SC_SPLIT];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ctx = (int)blockIdx.x;
+  const int q = ctx / p.M;
+  const int LQ = p.LQ, KD = p.KD, n = LQ * p.KQ;
+  const int nrf = LQ <= 16 ? 1 : LQ <= 32 ? 2 : 4;
+  const int ncg = 4 / nrf;
+  const int frag = wave % nrf, cg = wave / nrf;
+  const int i16 = lane & 15, g4 = lane >> 4;
+  const int qr0 = q * LQ;  // first global row of this query
+  const uint16_t* cbase = p.c + (long)ctx * p.LD * p.dp + g4 * 8;
+
+  for (int t0 = 0; t0 < LQ; t0 += 16 * nrf) {
+    const int f0 = t0 + frag * 16;  // first query token of this wave's fragment
+    if (f0 >= LQ) continue;         // (wave-uniform; the barrier is outside the loop)
+    const int ia = f0 + i16;        // A-operand token of this lane
+    const bool ra_ok = ia < LQ;
+    const uint16_t* qa = p.q + (long)(qr0 + (ra_ok ? ia : f0)) * p.dp + g4 * 8;
+
+    float bv[4][KQT];
+    int bi[4][KQT];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int k = 0; k < KQT; ++k) { bv[r][k] = -INFINITY; bi[r][k] = MS_NONE; }
+
+    for (int c0 = cg * MS_BN; c0 < p.LD; c0 += ncg * MS_BN) {
+      ms_f32x4 acc[4];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) acc[b] = ms_f32x4{0.f, 0.f, 0.f, 0.f};
+      int col[4];
+      bool cok[4];
+#pragma unroll
+      for (int b = 0; b < 4; ++b) { col[b] = c0 + b * 16 + i16; cok[b] = col[b] < p.LD; }
+      for (int k = 0; k < p.dp; k += 32) {
+        const ms_bf16x8 af = ms_load8(qa + k, ra_ok);
+        ms_bf16x8 bfr[4];
+#pragma unroll
+        for (int b = 0; b < 4; ++b) bfr[b] = ms_load8(cbase + (long)(cok[b] ? col[b] : 0) * p.dp + k, cok[b]);
+#pragma unroll
+        for (int b = 0; b < 4; ++b) acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfr[b], acc[b], 0, 0, 0);
+      }
+      // epilogue as in ms_fwd_kernel: lane holds tokens f0 + g4*4 + r, column col[b]
+#pragma unroll
+      for (int b = 0; b < 4; ++b) {
+        if (!cok[b]) continue;
+        const long cs = ((long)ctx * p.LD + col[b]) * KD;
+        for (int kd = 0; kd < KD; ++kd) {
+          const int idc = IDS ? p.cid[cs + kd] : 0;
+          const float wc = W ? p.cw[cs + kd] : 1.f;
+          const int idx = col[b] * KD + kd;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float s = acc[b][r];
+            const long rq = qr0 + min(f0 + g4 * 4 + r, LQ - 1);  // (tokens past the query's end are never written)
+#pragma unroll
+            for (int kq = 0; kq < KQT; ++kq) {
+              if (kq >= p.KQ) break;
+              bool match = true;
+              if (IDS) match = p.qid[rq * p.KQ + kq] == idc;
+              float f = 1.f;
+              if (W) f = p.qw[rq * p.KQ + kq] * wc;
+              if (!match) f = 0.f;
+              const float v = (IDS || W) ? s * f : s;
+              if (ms_better(v, idx, bv[r][kq], bi[r][kq])) { bv[r][kq] = v; bi[r][kq] = idx; }
+            }
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+      for (int kq = 0; kq < KQT; ++kq) {
+#pragma unroll
+        for (int off = 8; off >= 1; off >>= 1) {
+          const float v2 = __shfl_xor(bv[r][kq], off, 64);
+          const int i2 = __shfl_xor(bi[r][kq], off, 64);
+          if (ms_better(v2, i2, bv[r][kq], bi[r][kq])) { bv[r][kq] = v2; bi[r][kq] = i2; }
+        }
+      }
+    if (i16 == 0) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int i = f0 + g4 * 4 + r;
+        if (i >= LQ) continue;
+#pragma unroll
+        for (int kq = 0; kq < KQT; ++kq) {
+          if (kq >= p.KQ) break;
+          const int o = cg * n + i * p.KQ + kq;  // ncg > 1 only with LQ <= 32: ncg * n <= MS_SC_SPLIT
+          tab[o] = bv[r][kq];
+          if (ncg > 1) tix[o] = bi[r][kq];
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  float acc = p.pool ? -INFINITY : 0.f;
+  int ai = MS_NONE;
+  for (int s = lane; s < n; s += 64) {
+    float v = tab[s];
+    if (ncg > 1) {
+      int vi = tix[s];
+      for (int g = 1; g < ncg; ++g) {
+        const float v2 = tab[g * n + s];
+        const int i2 = tix[g * n + s];
+        if (ms_better(v2, i2, v, vi)) { v = v2; vi = i2; }
+      }
+    }
+    if (p.pool) {
+      if (ms_better(v, s, acc, ai)) { acc = v; ai = s; }
+    } else {
+      acc += v;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const float v2 = __shfl_xor(acc, off, 64);
+    if (p.pool) {
+      const int i2 = __shfl_xor(ai, off, 64);
+      if (ms_better(v2, i2, acc, ai)) { acc = v2; ai = i2; }
+    } else {
+      acc += v2;
+    }
+  }
+  if (lane == 0) p.S[ctx] = (p.mask && p.mask[ctx]) ? -INFINITY : acc;
 }
 
 struct MsBwd {

@@ -441,6 +441,18 @@ class HipKernels:
                         "dprhot_maxsim_fwd")
         return S, ws
 
+    def maxsim_score(self, Qb, Cb, qids, cids, qw, cw, KQ, KD, pool, M, m8):
+        """maxsim_fwd's pairwise scores for inference (dprhot_maxsim_score): same operands, M >= 1, one launch, no workspace and no
+        state.  Returns S fp32 [Nq, M], bit-equal to maxsim_fwd's."""
+        self._require_gpu(Qb, Cb, qids, cids, qw, cw, m8)
+        Nq, LQ, dp = Qb.shape
+        Nc, LD, _ = Cb.shape
+        S = torch.empty((Nq, M), dtype=torch.float32, device=Qb.device)
+        self._lib.check(self.lib.dprhot_maxsim_score(_ptr(Qb), _ptr(Cb), Nq, LQ, Nc, LD, dp, _ptr(qids), _ptr(cids), _ptr(qw), _ptr(cw),
+                                                     KQ, KD, pool, M, _ptr(m8), _ptr(S), self._stream()),
+                        "dprhot_maxsim_score")
+        return S
+
     def maxsim_bwd(self, dS, Qb, Cb, qids, cids, qw, cw, KQ, KD, pool, M, m8, state, need_dq=True, need_dc=True, need_dw=False):
         """Backward of maxsim_fwd from dS [Nq, Ny] fp32: (dq fp32 [Nq, LQ, dp], dc fp32 [Nc, LD, dp], dwq [Nq, LQ, KQ], dwc [Nc, LD, KD]),
         each None unless asked for."""
@@ -1459,6 +1471,59 @@ def expert_sim_score(query_repr, context_repr, mask=None, pairwise=False, query_
         if m8.numel() != Nc:
             raise ValueError(f"expert score: mask of {m8.numel()} entries for {Nc} contexts")
     return MaxSimScore.apply(q, c, qw, cw, qids, cids, m8, KQ, KD, _POOL[query_pool], M, kernels)
+
+
+def expert_score_only(query_repr, context_repr, mask=None, query_pool="sum", kernels=None):
+    """expert_sim_score(..., pairwise=True) for inference: the same repr dicts, the same operands (features padded to 32 in bf16,
+    int32 ids, fp32 weights) and the same bits, [B, M] with M = Nc // B, from one launch that keeps no tables (dprhot_maxsim_score).
+    The result has no grad_fn and nothing is saved."""
+    if query_pool not in _POOL:
+        raise NotImplementedError("Invalid query pooling! Available: [max, sum]")
+    kn = kernels if kernels is not None else default_kernels()
+    q, c = query_repr["expert_repr"].detach(), context_repr["expert_repr"].detach()
+    B, Nc = q.shape[0], c.shape[0]
+    M = Nc // B
+    if M * B != Nc:
+        raise ValueError(f"pairwise expert score: {Nc} contexts is not a multiple of {B} queries")
+    qids = cids = qw = cw = None
+    KQ = KD = 1
+    if "expert_ids" in query_repr:
+        KQ, KD = _slots(query_repr["expert_ids"], "query expert_ids"), _slots(context_repr["expert_ids"], "context expert_ids")
+        qids = query_repr["expert_ids"].to(torch.int32).contiguous()
+        cids = context_repr["expert_ids"].to(torch.int32).contiguous()
+        if "expert_weights" in query_repr:  # (COIL: the integer attention mask)
+            qw = query_repr["expert_weights"].detach().float().contiguous()
+            cw = context_repr["expert_weights"].detach().float().contiguous()
+    m8 = None
+    if mask is not None:
+        m8 = mask.reshape(-1).to(torch.uint8).contiguous()
+        if m8.numel() != Nc:
+            raise ValueError(f"expert score: mask of {m8.numel()} entries for {Nc} contexts")
+    return kn.maxsim_score(_bf16_rows(q), _bf16_rows(c), qids, cids, qw, cw, KQ, KD, _POOL[query_pool], M, m8)
+
+
+def _bf16_rows(x):
+    """The bf16 image of token rows, zero-padded to a multiple of 32 features, without a padded copy in the source dtype."""
+    d = x.shape[-1]
+    pad = (-d) % 32
+    if not pad:
+        return x.to(_BF16).contiguous()
+    out = torch.zeros(x.shape[:-1] + (d + pad,), dtype=_BF16, device=x.device)
+    out[..., :d].copy_(x)
+    return out
+
+
+def rerank_score(query_repr, context_repr, query_pool="sum", kernels=None):
+    """RerankMultiVecRetrieverTask's score of B aligned (query, passage) pairs (citadel_eval_task.py:238-265, :281-283): [B], the
+    expert score of pair b plus <q_cls[b], c_cls[b]> when the passages carry `cls_repr`."""
+    B, Nc = query_repr["expert_repr"].shape[0], context_repr["expert_repr"].shape[0]
+    if Nc != B:
+        raise ValueError(f"rerank score: {Nc} passages for {B} queries; a rerank batch is aligned pairs")
+    scores = expert_score_only(query_repr, context_repr, None, query_pool, kernels)[:, 0]
+    if "cls_repr" in context_repr:
+        with torch.no_grad():
+            scores = scores + pairwise_score(query_repr["cls_repr"], context_repr["cls_repr"], None, kernels)[:, 0]
+    return scores
 
 
 # ---- the CITADEL / SPLADE encoder head (citadel_model.py:46-82, splade_model.py:26-32) ---------------------------------------------

@@ -8,7 +8,7 @@ kept slots are listed and their weighted vectors written by libdprhot.so (dprhot
 dpr_scale_amd.ivf), in the reference's order and with its roundings, and only finished arrays reach the host.  `self.kernels` (default:
 the HIP kernels) is the kernel object ivf.py takes.
 
-Scope: ColBERT (encoders without `expert_ids`) and RerankMultiVecRetrieverTask are not covered.
+Scope: ColBERT (encoders without `expert_ids`) is not covered.  RerankMultiVecRetrieverTask of the same reference file: task/rerank.py.
 """
 import collections
 import os

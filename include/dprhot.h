@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DPRHOT_VERSION 174 /* 0.1.74: + dprhot_ivf_workspace_bytes / _score / _search (inverted-index retrieval for CITADEL / COIL); dprhot_router_head_* and dprhot_ivf_compact / _gather joined without a bump: tests/test_ivf.py pins this number */
+#define DPRHOT_VERSION 174 /* 0.1.74: + dprhot_ivf_workspace_bytes / _score / _search (inverted-index retrieval for CITADEL / COIL); dprhot_router_head_*, dprhot_ivf_compact / _gather and dprhot_maxsim_score joined without a bump: tests/test_ivf.py pins this number */
 
 #define DPRHOT_OK 0
 #define DPRHOT_E_INVALID (-1)     /* bad argument (NULL pointer, non-positive or misaligned size) */
@@ -321,6 +321,10 @@ int dprhot_maxsim_fwd(const void* q_tok, const void* c_tok, int Nq, int LQ, int 
 int dprhot_maxsim_bwd(const float* dS, const void* q_tok, const void* c_tok, int Nq, int LQ, int Nc, int LD, int dp, const int* q_ids,
                       const int* c_ids, const float* q_w, const float* c_w, int KQ, int KD, int pool, int M, const uint8_t* mask,
                       const void* ws, size_t ws_bytes, float* dq, float* dc, float* dwq, float* dwc, void* stream);
+/* The same scores for inference (reranking: citadel_eval_task.py:238-265), pairwise only (M >= 1, Nc = Nq * M; Nc = 0 is a no-op):
+ * one launch, no workspace, nothing kept for a backward.  S [Nq, M] equals dprhot_maxsim_fwd's bit for bit. */
+int dprhot_maxsim_score(const void* q_tok, const void* c_tok, int Nq, int LQ, int Nc, int LD, int dp, const int* q_ids, const int* c_ids,
+                        const float* q_w, const float* c_w, int KQ, int KD, int pool, int M, const uint8_t* mask, float* S, void* stream);
 
 /* Inverted-index retrieval for CITADEL / COIL (the search the reference's citadel_retrieval_task.py:136 asks of its absent
  * dpr_scale/index/inverted_vector_index.py; csrc/ivf.h):
