@@ -206,8 +206,8 @@ constexpr OptDef kOptDefs[OPT_COUNT] = {
     {OPT_PAIR128_CAP, "pair128_slices", 0, "K slices of a dQ tile in the 128 x 128 backward pair: 0 = the rule of pair128_plan, else that many (A/B)"},
     {OPT_NL128_MIN_TILES, "nl128_min_tiles", 32, "fewest 128 x 128 tiles for the 128-tile one-pass forward (32 against 128, step us: 512 x 2048 44.1 -> 40.7, 768 x 2048 49.7 -> 42.5, 1024 x 1024 47.3 -> 43.5, 256 x 4096 / 192 x 4096 / 256 x 2048 level)"},
     {OPT_P16_STAGED, "p16_staged", 1, "one-pass forward on the 256 x 256 kernel: the fp16 numerators leave through the per-wave LDS patch (64-byte pieces of 16 rows per store instruction instead of 32-byte pieces of 32 rows; bit-identical): 1 = except where the row pitch of G is a multiple of 128 KiB (forward us, arms alternating, profiles/r06_p16_staged_ab.txt: 8192^2 155.4 -> 147.8, 4096 x 8192 83.2 -> 79.3, 4096 x 16384 153 -> 146 and its step 390 -> 372; at 65536 columns the forward gains nothing and the step of 8192 x 65536 LOSES 100 us of 2880), 2 = always, 0 = never"},
-    {OPT_SMALL_SIM, "small_sim", 1, "sim launch of the batch-32 step (B <= 32, fp32 q, 256-deep K chunks: sim_small.h): 1 = one wave per 16 x 16 tile and K chunk, whole-line loads rounded into a wave-private LDS patch, no barrier (bit-identical to the engine; 32 x 256 x 768 step 9.19 -> 8.29 us); 0 = the GEMM engine (tile 5); A/B only: 2 = fp32 straight into fragment registers, no LDS (8.52 us), 3 / 4 = forms 1 / 2 with two waves per workgroup (8.70 / 9.41 us)"},
-    {OPT_SMALL_STEP_ROLES, "small_step_roles", 3, "softmax + backward launch of the batch-32 step (B <= 32, at most 768 columns: step_small_kernel_roles / step_small_kernel_out in step_small.h): one launch split by role -- d / 16 dC workgroups (slabs + Q tile, full softmax, one barrier, dC product and stores) next to one dQ workgroup per 16-row half and column tile (half the slabs + C tile, 8 K slices); 3 = form 2 with loss / logsumexp / dScores / logits written by one output workgroup (block 0, no product) instead of the dC workgroup of tile 0 (a stamping launch of the packed step keeps form 2), 2 = 32-column dQ tiles (d % 32 == 0, else form 1; 32 x 256 x 768 step 8.29 -> 7.74 us), 1 = 16-column dQ tiles (7.84 us), 0 = every workgroup does both products (step_small_kernel); all forms bit-identical (tests/test_small_step_roles.py, tests/test_small_step_out.py)"},
+    {OPT_SMALL_SIM, "small_sim", 1, "sim launch of the batch-32 step (B <= 32, fp32 q, 256-deep K chunks: sim_small.h): 1 = one wave per 16 x 16 tile and K chunk on an exact 3-D grid (row tile, column tile, chunk: no division and one wait on the arguments in front of the first operand load, the mask byte loaded last), whole-line loads rounded into a wave-private LDS patch, no barrier (bit-identical to the engine; 32 x 256 x 768 step 9.19 -> 8.29 us, with the 3-D grid 7.21 -> 7.05); 0 = the GEMM engine (tile 5); A/B only: 2 = fp32 straight into fragment registers, no LDS (8.52 us), 3 / 4 = forms 1 / 2 with two waves per workgroup (8.70 / 9.41 us)"},
+    {OPT_SMALL_STEP_ROLES, "small_step_roles", 3, "softmax + backward launch of the batch-32 step (B <= 32, at most 768 columns: step_small_kernel_roles / step_small_kernel_out in step_small.h): one launch split by role -- d / 16 dC workgroups (slabs + Q tile, full softmax, one barrier, dC product and stores) next to one dQ workgroup per 16-row half and column tile (half the slabs + C tile, 8 K slices); 3 = form 2 with the outputs written by workgroups of their own that have no product to do, in front of the grid, instead of by the dC workgroup of tile 0: a loss block (softmax up to the row loss, logsumexp / row loss, one barrier, the loss sum) and two row-store blocks (one 16-row half each: dScores / logits, no barrier); the device-side scale is the last load of a role, not a wait in front of it (a stamping launch of the packed step keeps form 2), 2 = 32-column dQ tiles (d % 32 == 0, else form 1; 32 x 256 x 768 step 8.29 -> 7.74 us), 1 = 16-column dQ tiles (7.84 us), 0 = every workgroup does both products (step_small_kernel); all forms bit-identical (tests/test_small_step_roles.py, tests/test_small_step_out.py, tests/test_small_step_split_gpu.py)"},
 };
 constexpr bool opt_table_in_enum_order() {  // (round 6: a row added in the wrong place made two options answer to each other's names)
   for (int i = 0; i < OPT_COUNT; ++i)
@@ -720,14 +720,15 @@ bool small_sim_ok(int B, int Nc, int d, const FwdPlan& fp) {
 int launch_sim_small(bool b_f32, const GemmArgs& a, const EpiSim& epi, int splits, hipStream_t st) {
   const int v = opt(OPT_SMALL_SIM);
   const int form = (v == 2 || v == 4) ? SS_REG : SS_PATCH, wpg = (v == 3 || v == 4) ? 2 : 1;
-  const int nrt = cdiv(a.M, 16), nct = cdiv(a.N, 16), total = nrt * nct * splits;
-  const dim3 grid(cdiv(total, wpg)), block(64 * wpg);
+  // an exact 3-D grid (row tile x wpg, column tile, K chunk): the kernel takes its tile from the block index, without a division
+  const int nrt = cdiv(a.M, 16), nct = cdiv(a.N, 16);
+  const dim3 grid(cdiv(nrt, wpg), nct, splits), block(64 * wpg);
   const size_t lds = sim_small_lds(form, b_f32, wpg);
   if (form == SS_REG)
-    return b_f32 ? launch<sim_small_kernel<true, SS_REG>>(grid, block, lds, st, a, epi, nrt, nct, total)
-                 : launch<sim_small_kernel<false, SS_REG>>(grid, block, lds, st, a, epi, nrt, nct, total);
-  return b_f32 ? launch<sim_small_kernel<true, SS_PATCH>>(grid, block, lds, st, a, epi, nrt, nct, total)
-               : launch<sim_small_kernel<false, SS_PATCH>>(grid, block, lds, st, a, epi, nrt, nct, total);
+    return b_f32 ? launch<sim_small_kernel<true, SS_REG>>(grid, block, lds, st, wpg, a, epi)
+                 : launch<sim_small_kernel<false, SS_REG>>(grid, block, lds, st, wpg, a, epi);
+  return b_f32 ? launch<sim_small_kernel<true, SS_PATCH>>(grid, block, lds, st, wpg, a, epi)
+               : launch<sim_small_kernel<false, SS_PATCH>>(grid, block, lds, st, wpg, a, epi);
 }
 
 // the loss launch of the no-logits forward -- or, inside the one-call step, a note for launch_dq
@@ -1909,11 +1910,11 @@ int dprhot_inbatch_step_f32(const float* q, const float* c, dprhot_bf16* Qb, dpr
   // the role-split forms (step_small_kernel_roles, step_small_kernel_out): one row block, the multi-slab plans up to 768 columns
   if (const int roles = opt(OPT_SMALL_STEP_ROLES); roles != 0 && B <= SS_ROWS && ncp <= 768) {
     const int qtw = roles >= 2 && d % 32 == 0 ? 32 : 16;
-    // Form 3 hands the lead's outputs to a workgroup of their own (one more block).  A stamping launch (the packed step) keeps form
+    // Form 3 hands the lead's outputs to workgroups of their own (a loss block and two row-store blocks in front of the grid).  A stamping launch (the packed step) keeps form
     // 2: the loss goes into dC[m][0], whose owner -- the dC workgroup of column 0 -- needs the finished sum, so there the lead stays.
     const bool outwg = roles == 3 && g_packed.stamp_src == nullptr;
     const size_t rlds = step_roles_lds(Nc, qtw);  // (the maximum over the roles, the output role included)
-    const dim3 rgrid(d / 16 + 2 * (d / qtw) + (outwg ? 1 : 0));
+    const dim3 rgrid(d / 16 + 2 * (d / qtw) + (outwg ? SS_OUT_BLOCKS : 0));
 #define DPRHOT_SR_LAUNCH_K(KERN, CPT, NS, QTW) launch<KERN<CPT, NS, QTW>>(rgrid, block, rlds, st, a)
 #define DPRHOT_SR_LAUNCH_Q(CPT, NS, QTW) \
   (outwg ? DPRHOT_SR_LAUNCH_K(step_small_kernel_out, CPT, NS, QTW) : DPRHOT_SR_LAUNCH_K(step_small_kernel_roles, CPT, NS, QTW))

@@ -19,8 +19,12 @@
 //            at all, but an instruction touches 16 lines and half of each: 8.52 us.
 // One wave per workgroup; two (the two row tiles of one column tile and chunk) measured 8.70 / 9.41 us.
 // Every load of the chunk is issued back to back before anything looks at a loaded value; the waits the compiler places are then
-// counted vmcnt(N) in issue order (plain loads: hipcc counts them itself, nothing here is hand-counted), so the conversions and
-// the MFMA chain follow the data in.  The mask byte is fetched first, as EpiSim::begin does.
+// counted vmcnt(N) in issue order (plain loads: hipcc counts them itself), so the conversions and the MFMA chain follow the data in.
+// The front -- what a lone wave per CU executes before its first operand load, at full issue latency per instruction -- is kept
+// short: the tile comes from a three-dimensional block index (no division, no early return), everything the operand addresses
+// are made of sits in the first 64 bytes of the kernel arguments behind ONE wait, and the mask byte, which only the epilogue looks
+// at, is loaded behind the 32 operand loads (first global_load_dwordx4: instruction 45, about 195 before; step of 32 x 256 x 768
+// on the ten-step graph 7.21 -> 7.05 us, profiles/step_fronts_ab.txt; asserted on the assembly by tests/test_step_fronts.py).
 #pragma once
 #include "gemm_bf16.h"
 
@@ -55,21 +59,22 @@ __device__ __forceinline__ bf16x8 sms_patch_frag(const uint16_t* T, int kk, int 
 }
 
 // p.kchunk == SMS_KC and p.K % SMS_KC == 0 (the launch guard): every chunk is whole, nothing lies beyond K.
-// Waves are numbered row tile fastest, then column tile, then K chunk: the waves of one workgroup read the same context rows.
+// The grid is three-dimensional and exact: blockIdx.x = row tile (times wpg waves: the waves of one workgroup are neighbouring row
+// tiles of one column tile and chunk, and read the same context rows), .y = column tile, .z = K chunk.  x runs fastest in dispatch
+// order, so waves start in the order the linear index gave them (row tile, then column tile, then chunk) -- but the three indices
+// cost no division (three v_rcp_iflag sequences stood in front of the first load) and no early return: a wave beyond the last row
+// tile (wpg = 2 at an odd number of row tiles) loads clamped rows and stores nothing, as a ragged tile's rows beyond M do.
+// wpg is the first argument, in the 64 bytes of the kernel arguments that hold everything the operand addresses are made of.
 template <bool B_F32, int FORM>
-__global__ __launch_bounds__(64 * SMS_MAXW) void sim_small_kernel(GemmArgs p, EpiSim epi, int nrt, int nct, int total) {
+__global__ __launch_bounds__(64 * SMS_MAXW) void sim_small_kernel(int wpg, GemmArgs p, EpiSim epi) {
   extern __shared__ __attribute__((aligned(16))) uint16_t sms_smem[];
   const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wid = blockIdx.x * (blockDim.x >> 6) + wave;
-  if (wid >= total) return;  // (no barrier anywhere below)
-  const int rt = wid % nrt, ct = (wid / nrt) % nct, bz = wid / (nrt * nct);
+  const int rt = (int)blockIdx.x * wpg + wave, ct = (int)blockIdx.y, bz = (int)blockIdx.z;
   const int m0 = rt * 16, n0 = ct * 16, kbeg = bz * SMS_KC;
   DPRHOT_TM(0);
 
-  // ---- every global read, back to back: mask byte, then the chunk of both operands
-  const int ncl = min(n0 + i, epi.N - 1);
-  const uint8_t mraw = epi.mask_raw(ncl);
+  // ---- every global read, back to back: the chunk of both operands, then the mask byte
   const float* const Af = reinterpret_cast<const float*>(p.A);
   const int arow = min(m0 + i, p.M - 1), brow = min(n0 + i, p.N - 1);
   bf16x8 af[SMS_KK], bfr[SMS_KK];
@@ -104,10 +109,23 @@ __global__ __launch_bounds__(64 * SMS_MAXW) void sim_small_kernel(GemmArgs p, Ep
 #pragma unroll
     for (int kk = 0; kk < SMS_KK; ++kk) bfr[kk] = *reinterpret_cast<const bf16x8*>(p.B + (size_t)brow * p.ldb + kbeg + kk * 32 + g * 8);
   }
+  __builtin_amdgcn_sched_barrier(0);  // the operand loads are out before the mask byte's address is worked out
+  // The mask byte: one unconditional load -- of the operand's first byte where there is no mask, dropped by the select below -- so
+  // that the text up to the first use of a loaded value is one basic block.  It is the LAST load issued and only the epilogue looks
+  // at it; loads return in order, so the wait it needs is the one the last operand load needs anyway.
+  const int ncl = min(n0 + i, epi.N - 1);
+  const bool has_mask = epi.packed != nullptr || epi.colmask != nullptr;
+  const uint8_t* mptr = epi.colmask != nullptr ? epi.colmask + ncl : reinterpret_cast<const uint8_t*>(p.A);
+  if (epi.packed != nullptr) {  // (EpiSim::mask_raw)
+    const int r = ncl / epi.p_rows_c, j = ncl - r * epi.p_rows_c;
+    mptr = epi.packed + (size_t)(r * epi.p_rows_c + epi.p_n_ctx) * epi.p_row_bytes + min(j, epi.p_n_ctx - 1);
+  }
+  const uint8_t mbyte = *mptr;
   __builtin_amdgcn_sched_barrier(0);  // nothing above uses a loaded value
   DPRHOT_TM(1);
 
-  const bool masked = n0 + i >= epi.N || mraw != 0 || epi.mask_pad(ncl);
+  // what masks the column besides the byte, worked out under the loads (no `||` on the byte: a branch on it would wait for all 33)
+  const bool mpad = (n0 + i >= epi.N) | epi.mask_pad(ncl);
   f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
   if constexpr (FORM == SS_REG) {
 #pragma unroll
@@ -130,6 +148,11 @@ __global__ __launch_bounds__(64 * SMS_MAXW) void sim_small_kernel(GemmArgs p, Ep
 #pragma unroll
     for (int kk = 0; kk < SMS_KK; ++kk) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[kk], bfr[kk], acc, 0, 0, 0);
   }
+  // The mask byte is the load behind the last operand load, and that one the MFMA chain has already waited for.  Its counter is
+  // settled HERE all the same (vmcnt(0), the other counters left alone: the one wait in this file that the compiler did not place):
+  // the compiler waits where the byte is first looked at, below the copies' conditional stores, and as the same counter counts
+  // stores, the slab stores of half the waves would wait for their copies to be acknowledged.
+  __builtin_amdgcn_s_waitcnt(0x0F70);
   DPRHOT_TM(4);
 
   // ---- the bf16 copies the backward reads: each operand row by exactly one wave per chunk (16-byte pieces, 16 rows x 64 B each)
@@ -145,10 +168,11 @@ __global__ __launch_bounds__(64 * SMS_MAXW) void sim_small_kernel(GemmArgs p, Ep
         *reinterpret_cast<bf16x8*>(p.Bcopy + (size_t)(n0 + i) * p.ldb + kbeg + kk * 32 + g * 8) = bfr[kk];
     }
   }
-  if (epi.zero_words != nullptr && wid == 0 && lane < epi.n_zero) epi.zero_words[lane] = 0ull;
+  if (epi.zero_words != nullptr && (rt | ct | bz) == 0 && lane < epi.n_zero) epi.zero_words[lane] = 0ull;
 
   // ---- EpiSim::finish in its slab form (statistics off): * 1/T, masked columns -> -inf, fp32 partial logits of this chunk
   float* const S = epi.S + (size_t)bz * epi.slab_stride;
+  const bool masked = mpad | (has_mask & (mbyte != 0));
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int m = m0 + g * 4 + r;

@@ -402,12 +402,15 @@ __global__ __launch_bounds__(1024) void step_small_kernel(StepSmallArgs p) {
 //                                                   8-15 fetch the C tile; G half image, dQ product in 8 K slices, slice sum, store.
 //   who writes loss / logsumexp / G / logits:       step_small_kernel_roles (forms 1, 2): the dC workgroup of tile 0, the lead, as in
 //                                                   step_small_kernel -- and it ended the launch 0.36 us behind the other 47.
-//                                                   step_small_kernel_out (form 3): one output workgroup of the same grid that has
-//                                                   no product to do; every dC workgroup is a plain one.
+//                                                   step_small_kernel_out (form 3): output workgroups of the same grid that have
+//                                                   no product to do -- a loss block and two row-store blocks (ss_role_loss,
+//                                                   ss_role_rows); every dC workgroup is a plain one.
+// No role waits on memory in front of its operand loads: the device-side scale, used behind the products only, is the LAST load of a
+// role's batch (tests/test_step_fronts.py reads that off the assembly).
 // Every value is formed by the arithmetic instructions of step_small_kernel in their order -- the softmax below is its text without
 // the selects, compares, address arithmetic and LDS lane exchanges that change no value -- so the outputs are the same bits, and
 // step_small_kernel, which is left exactly as it was, is the reference they are compared with (tests/test_small_step_roles.py,
-// tests/test_small_step_out.py, tests/test_small_step_lean.py).
+// tests/test_small_step_out.py, tests/test_small_step_lean.py, tests/test_small_step_split_gpu.py).
 inline size_t step_roles_lds(int Nc, int QTW) {
   const int ncp = (Nc + 31) / 32 * 32, gs = ncp + 8;
   const size_t dc = (size_t)SS_ROWS * gs * 2 + (size_t)SS_ROWS * 24 * 2 + SS_MAXB * sizeof(float);
@@ -419,8 +422,9 @@ inline size_t step_roles_lds(int Nc, int QTW) {
 
 // The row softmax of step_small_kernel for the thread's 8 * CPT scores of `row` (32 lanes per row): slabs added in slab order, one
 // exponential per score, G (bf16) into row `lrow` of the LDS image.  Returns the row loss (lane tr == 0 uses it).
-// G_IMAGE = false (the output role: nobody reads its image) drops the LDS store of G and nothing else: the values are formed all
-// the same for the global store.
+// MODE (compile-time) takes whole parts of the text out for the blocks of form 3 that nobody reads an image from: SS_SM_ROWS drops the
+// LDS store of G and the two per-row stores and nothing else (the values are formed all the same for the global stores); SS_SM_LOSS
+// stops at the row loss.  What remains forms its values exactly as the full text does.
 // Every workgroup of the launch repeats this text on four SIMDs, so its VALU instructions ARE the launch's critical path.  It forms
 // every value with the arithmetic instructions of step_small_kernel, in their order, and spends nothing else ("the lean
 // row softmax"):
@@ -443,7 +447,10 @@ __device__ __forceinline__ void ss_pair16(float x, float& even, float& odd) {
   odd = __uint_as_float(r[1]);
 }
 
-template <int CPT, int NS, bool FULL, bool G_IMAGE = true>
+constexpr int SS_SM_IMAGE = 0;  // dC / dQ roles: G into the LDS image; `lead` (forms 1, 2) also stores every output
+constexpr int SS_SM_LOSS = 1;   // loss block (form 3): logsumexp and row loss only -- no G arithmetic, no G or logits store, no image
+constexpr int SS_SM_ROWS = 2;   // row-store blocks (form 3): G and the logits to memory only -- no image, no logsumexp / row-loss store
+template <int CPT, int NS, bool FULL, int MODE = SS_SM_IMAGE>
 __device__ __forceinline__ float ss_row_softmax(const StepSmallArgs& p, float4 (&sa)[CPT][NS], float4 (&sb)[CPT][NS], int row, bool active,
                                                 int64_t yraw, int tr, bool lead, uint16_t* Gs_row, int ncp) {
   const int Nc = FULL ? 256 * CPT : p.Nc, cpr = Nc >> 3;
@@ -503,10 +510,13 @@ __device__ __forceinline__ float ss_row_softmax(const StepSmallArgs& p, float4 (
   const float lse = m + logf(sm);
   const float inv_sm = 1.0f / sm;  // sm = 0 (dead row): inf * 0 = NaN, like exp(v - lse) with lse = NaN
   const float l = FULL || active ? lse - gold : 0.f;
-  if (tr == 0 && lead && (FULL || active)) {
-    if (p.row_lse) p.row_lse[row] = lse;
-    if (p.row_loss) p.row_loss[row] = l;
+  if constexpr (MODE != SS_SM_ROWS) {
+    if (tr == 0 && lead && (FULL || active)) {
+      if (p.row_lse) p.row_lse[row] = lse;
+      if (p.row_loss) p.row_loss[row] = l;
+    }
   }
+  if constexpr (MODE != SS_SM_LOSS) {  // (compiled out, not masked: the loss needs no probability)
 #pragma unroll
   for (int k = 0; k < CPT; ++k) {
     const int chunk = tr + k * 32;
@@ -531,8 +541,9 @@ __device__ __forceinline__ float ss_row_softmax(const StepSmallArgs& p, float4 (
           }
         }
       }
-      if constexpr (G_IMAGE) *reinterpret_cast<uint4*>(Gs_row + chunk * 8) = gv;
+      if constexpr (MODE == SS_SM_IMAGE) *reinterpret_cast<uint4*>(Gs_row + chunk * 8) = gv;
     }
+  }
   }
   return l;
 }
@@ -567,15 +578,13 @@ __device__ __forceinline__ void ss_role_dc(const StepSmallArgs& p, uint16_t* Gs,
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int Nc = FULL ? 256 * CPT : p.Nc, B = FULL ? SS_ROWS : p.B;
   const int ncp = (Nc + 31) / 32 * 32, gs = ncp + 8;
+  DPRHOT_TMB(1, 0);
   const int lrow = tid >> 5, tr = tid & 31;
-  const float dsc = p.d_scale ? *p.d_scale : 1.0f;
-  const float sc = p.h_scale * dsc;
   const int i = lane & 15, g = lane >> 4;
   const int n0 = tile * TW;
   const bool lead = LEAD && tile == 0;
   uint16_t* const Qs = Gs + SS_ROWS * gs;                           // [32][TS]  Q[:, n0:n0+16]
   float* const s_rl = reinterpret_cast<float*>(Qs + SS_ROWS * TS);  // [32] row losses
-  DPRHOT_TMB(1, 0);
   const int row = lrow;
   const bool active = FULL || row < B;
   const int64_t yraw = active ? p.y[row] : (int64_t)-1;
@@ -583,6 +592,10 @@ __device__ __forceinline__ void ss_role_dc(const StepSmallArgs& p, uint16_t* Gs,
   if (active && tr < TC) qreg = *reinterpret_cast<const uint4*>(p.Qb + (size_t)row * p.d + n0 + tr * 8);
   float4 sa[CPT][NS], sb[CPT][NS];
   ss_load_slabs<CPT, NS, FULL>(p, sa, sb, row, active, tr);
+  // The device-side scale is used behind the product only.  Read at the top under `p.d_scale ? ... : 1.0f` it was a load and a wait
+  // of its own -- a whole trip to memory -- in front of every load above; here it is ONE unconditional load (of a slab word where
+  // there is no scale, dropped by the select at the use), the last of the batch, and nothing in front of the barrier waits for it.
+  const float dsv = *(p.d_scale ? p.d_scale : p.slabs);
   DPRHOT_TMB(1, 1);
   if (tr < TC) *reinterpret_cast<uint4*>(Qs + lrow * TS + tr * 8) = qreg;
   const float l = ss_row_softmax<CPT, NS, FULL>(p, sa, sb, row, active, yraw, tr, lead, Gs + lrow * gs, ncp);
@@ -602,6 +615,7 @@ __device__ __forceinline__ void ss_role_dc(const StepSmallArgs& p, uint16_t* Gs,
     }
     if (stamp) __syncthreads();  // only the stamping launch of the packed step pays this second barrier
   }
+  const float sc = p.h_scale * (p.d_scale ? dsv : 1.0f);
   const bf16x8 bq = ss_tr_frag(Qs, TS, 0, 0, lane);
   float* out = p.dC + (size_t)(wave * 16 + g * 4) * p.d + n0 + i;
   const size_t step = (size_t)256 * p.d;
@@ -635,21 +649,21 @@ __device__ __forceinline__ void ss_role_dq(const StepSmallArgs& p, uint16_t* Gs,
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int Nc = FULL ? 256 * CPT : p.Nc, B = FULL ? SS_ROWS : p.B;
   const int ncp = (Nc + 31) / 32 * 32, gs = ncp + 8;
+  DPRHOT_TMB(2, 0);
   const int lrow = tid >> 5, tr = tid & 31;
-  const float dsc = p.d_scale ? *p.d_scale : 1.0f;
-  const float sc = p.h_scale * dsc;
   const int i = lane & 15, g = lane >> 4;
   const int n0 = qt * QTW, r0 = half * 16;
   if (r0 >= B) return;  // (fewer rows than one half: nothing of dQ is this block's to write)
   uint16_t* const Cs = Gs + 16 * gs;                             // [ncp][QTS]  C[:, n0:n0+QTW]
   float* const red = reinterpret_cast<float*>(Cs + ncp * QTS);   // [8][16][QTW] dQ partial sums
-  DPRHOT_TMB(2, 0);
+  float dsv = 1.0f;  // the device-side scale, as in ss_role_dc: the last load of the batch (the slice sum is threads 0 .. 16 QTW - 1 <= 511)
   if (tid < 512) {  // waves 0-7: the softmax of the half's 16 rows
     const int row = r0 + lrow;
     const bool active = FULL || row < B;
     const int64_t yraw = active ? p.y[row] : (int64_t)-1;
     float4 sa[CPT][NS], sb[CPT][NS];
     ss_load_slabs<CPT, NS, FULL>(p, sa, sb, row, active, tr);
+    dsv = *(p.d_scale ? p.d_scale : p.slabs);
     DPRHOT_TMB(2, 1);
     (void)ss_row_softmax<CPT, NS, FULL>(p, sa, sb, row, active, yraw, tr, false, Gs + lrow * gs, ncp);
   } else {  // waves 8-15: the C tile
@@ -691,6 +705,7 @@ __device__ __forceinline__ void ss_role_dq(const StepSmallArgs& p, uint16_t* Gs,
   __syncthreads();
   DPRHOT_TMB(2, 4);
   if (tid < 16 * QTW) {  // add the 8 K slices in order
+    const float sc = p.h_scale * (p.d_scale ? dsv : 1.0f);
     const int e = tid, r = e / QTW, ccol = e - r * QTW;
     if (r0 + r < B) {
       float s = red[e];
@@ -702,23 +717,28 @@ __device__ __forceinline__ void ss_role_dq(const StepSmallArgs& p, uint16_t* Gs,
   DPRHOT_TMB(2, 5);
 }
 
-// output role (form 3): what the lead did besides its dC tile, and nothing else -- the full softmax with its stores of G, the logits,
-// logsumexp and row loss (ss_row_softmax with lead = true: the same bits), then the loss.  No Q tile, no C tile, no product, and no
-// G image in LDS.
+// The output roles (form 3): what the lead did besides its dC tile, and nothing else.  No Q tile, no C tile, no product, and no G
+// image in LDS.  One workgroup did all of it at first and ended the launch (2.40 us against 2.28 for the last dC workgroup): the
+// full softmax with every store on four waves per SIMD, then a barrier, then the loss.  But the loss needs every row's statistics
+// and neither G nor the logits, and the per-row outputs need no barrier and split by rows -- so they are two roles:
+//   loss block (one):       the softmax of all 32 rows up to the row loss (SS_SM_LOSS), logsumexp and row loss stored, ONE barrier,
+//                           the sum.
+//   row-store blocks (two): one 16-row half each on waves 0-7, as in the dQ role; G and the logits stored (SS_SM_ROWS), no barrier.
+// Each forms its values with the shared softmax text: the same bits as the lead's.
 template <int CPT, int NS, bool FULL>
-__device__ __forceinline__ void ss_role_out(const StepSmallArgs& p, float* s_rl) {  // s_rl: [32] row losses
+__device__ __forceinline__ void ss_role_loss(const StepSmallArgs& p, float* s_rl) {  // s_rl: [32] row losses
   const int tid = threadIdx.x, lane = tid & 63;
+  DPRHOT_TMB(3, 0);
   const int Nc = FULL ? 256 * CPT : p.Nc, B = FULL ? SS_ROWS : p.B;
   const int ncp = (Nc + 31) / 32 * 32;
   const int lrow = tid >> 5, tr = tid & 31;
-  DPRHOT_TMB(3, 0);
   const int row = lrow;
   const bool active = FULL || row < B;
-  const int64_t yraw = active ? p.y[row] : (int64_t)-1;
+  const int64_t yraw = p.y[active ? row : 0];  // (unconditional, on a valid address: the softmax drops the label of an absent row)
   float4 sa[CPT][NS], sb[CPT][NS];
   ss_load_slabs<CPT, NS, FULL>(p, sa, sb, row, active, tr);
   DPRHOT_TMB(3, 1);
-  const float l = ss_row_softmax<CPT, NS, FULL, false>(p, sa, sb, row, active, yraw, tr, true, nullptr, ncp);
+  const float l = ss_row_softmax<CPT, NS, FULL, SS_SM_LOSS>(p, sa, sb, row, active, yraw, tr, true, nullptr, ncp);
   if (tr == 0) s_rl[lrow] = l;
   DPRHOT_TMB(3, 2);
   __syncthreads();
@@ -743,6 +763,27 @@ __device__ __forceinline__ void ss_role_out(const StepSmallArgs& p, float* s_rl)
     if (tid == 0) p.loss_sum[0] = (float)tot * p.loss_scale;
   }
   DPRHOT_TMB(3, 4);
+}
+
+// row-store block of 16-row half `half`: G and the logits of its rows, nothing else
+template <int CPT, int NS, bool FULL>
+__device__ __forceinline__ void ss_role_rows(const StepSmallArgs& p, int half) {
+  const int tid = threadIdx.x;
+  DPRHOT_TMB(0, 0);
+  const int Nc = FULL ? 256 * CPT : p.Nc, B = FULL ? SS_ROWS : p.B;
+  const int ncp = (Nc + 31) / 32 * 32;
+  const int lrow = tid >> 5, tr = tid & 31;
+  const int r0 = half * 16;
+  // waves 8-15 have no row; a half without a row and a step that asks for neither output have nothing to store (no barrier below)
+  if (tid >= 512 || r0 >= B || (p.G == nullptr && p.S_out == nullptr)) return;
+  const int row = r0 + lrow;
+  const bool active = FULL || row < B;
+  const int64_t yraw = p.y[active ? row : 0];  // (as in ss_role_loss)
+  float4 sa[CPT][NS], sb[CPT][NS];
+  ss_load_slabs<CPT, NS, FULL>(p, sa, sb, row, active, tr);
+  DPRHOT_TMB(0, 1);
+  (void)ss_row_softmax<CPT, NS, FULL, SS_SM_ROWS>(p, sa, sb, row, active, yraw, tr, true, nullptr, ncp);
+  DPRHOT_TMB(0, 2);
 }
 
 // CPT, NS: as in step_small_kernel (CPT <= 3).  QTW: columns of d per dQ workgroup (16 or 32; d % QTW == 0).
@@ -778,31 +819,38 @@ __global__ __launch_bounds__(1024) void step_small_kernel_roles(StepSmallArgs p)
   else ss_roles_block<CPT, NS, QTW, false>(p, ss_smem);
 }
 
-// Form 3.  Grid: ONE output block, then d / 16 dC blocks, then 2 * d / QTW dQ blocks.
-// The output block is physical block 0.  Workgroups are handed out in index order, and the roles kernel's stamps show what a late
-// index costs: its dQ blocks, behind the 48 dC blocks, take their first stamp 0.2-0.3 us after block 0 does.  The output block
-// carries a full 32-row softmax -- the longest phase of the launch -- and then a barrier and the loss, so it has to be among the
-// first to start, not behind 96 others; being first costs every other block one place in the queue and nothing else (97 of 256
-// CUs are taken).  It lands in XCD 0, which then holds 13 workgroups on its 32 CUs where the others hold 12.
-// Block index b -> XCD is b % 8, so the tile mappings below are computed from the physical index b, not from b - 1: the blocks of
-// XCD x are b = x + 8 k (x = 0: 8 + 8 k), k = (b - 1) / 8 counts them, and XCD x owns the same contiguous run of column tiles in
-// both roles -- the neighbouring tiles of one 128-byte line of Q / C rows still meet in one L2.
+// Form 3.  Grid: the loss block, the two row-store blocks, then d / 16 dC blocks, then 2 * d / QTW dQ blocks (SS_OUT_BLOCKS = 3 in
+// front of the products).
+// The output blocks are the physical blocks 0-2.  Workgroups are handed out in index order, and the roles kernel's stamps show what
+// a late index costs: its dQ blocks, behind the 48 dC blocks, take their first stamp 0.2-0.3 us after block 0 does.  The loss block
+// carries a full 32-row softmax and then a barrier and the loss, so it has to be the first to start, not behind 96 others; being
+// in front costs every other block three places in the queue and nothing else (99 of 256 CUs are taken).  They land in XCDs 0-2.
+// Block index b -> XCD is b % 8, so the tile mappings below are computed from the physical index b: the blocks of one role are a
+// run of consecutive indices [first, first + n), those of XCD b % 8 among them are 8 apart, so (b - first) / 8 counts them, and with
+// n / 8 blocks per XCD, XCD x owns the same contiguous run of column tiles in both roles -- the neighbouring tiles of one 128-byte
+// line of Q / C rows still meet in one L2 -- and every tile has exactly one owner.
+constexpr int SS_OUT_BLOCKS = 3;
 template <int CPT, int NS, int QTW, bool FULL>
 __device__ __forceinline__ void ss_out_block(const StepSmallArgs& p, uint16_t* smem) {
   const int b = (int)blockIdx.x;
   if (b == 0) {
-    ss_role_out<CPT, NS, FULL>(p, reinterpret_cast<float*>(smem));
+    ss_role_loss<CPT, NS, FULL>(p, reinterpret_cast<float*>(smem));
+    return;
+  }
+  if (b < SS_OUT_BLOCKS) {
+    ss_role_rows<CPT, NS, FULL>(p, b - 1);
     return;
   }
   const int ndc = p.d / 16, nqt = p.d / QTW;
-  if (b <= ndc) {
-    const int tile = (ndc % 8 == 0) ? (b % 8) * (ndc / 8) + (b - 1) / 8 : b - 1;
+  if (b < SS_OUT_BLOCKS + ndc) {
+    const int v = b - SS_OUT_BLOCKS;
+    const int tile = (ndc % 8 == 0) ? (b % 8) * (ndc / 8) + v / 8 : v;
     ss_role_dc<CPT, NS, false, FULL>(p, smem, tile);
     return;
   }
-  const int u = b - 1 - ndc;
+  const int u = b - SS_OUT_BLOCKS - ndc;
   int qt, half;
-  if (ndc % 8 == 0 && nqt % 8 == 0) {  // b % 8 == (u + 1) % 8, and u / 8 counts the dQ blocks of that XCD
+  if (ndc % 8 == 0 && nqt % 8 == 0) {  // u / 8 counts the dQ blocks of XCD b % 8: per tiles, both halves of each
     const int per = nqt / 8;
     qt = (b % 8) * per + (u / 8) % per;
     half = (u / 8) / per;

@@ -1,6 +1,8 @@
 // experiment: per-workgroup wall-clock stamps (10 ns ticks) of the batch-32 step's softmax + backward launch, as it is (small_step_roles = 0:
-// step_small_kernel, slots = DPRHOT_TM 8..15) and split by role (1 / 2: step_small_kernel_roles; 3: step_small_kernel_out, whose output
-// workgroup has a stamp row of its own, DPRHOT_TMB kind 3).  Not shipped.
+// step_small_kernel, slots = DPRHOT_TM 8..15) and split by role (1 / 2: step_small_kernel_roles; 3: step_small_kernel_out, whose loss
+// block has a stamp row of its own, DPRHOT_TMB kind 3, and whose two row-store blocks use kind 0, which form 0 alone uses otherwise).
+// Every role's stamp 0 is the first statement of its body.  Also the sim launch's own stamps (sim_small_kernel, workgroup (0, 0, 0):
+// DPRHOT_TM 0 / 1 / 4 / 6).  Not shipped.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 scratch/step_small_stamps.hip -o scratch/step_small_stamps
 //   scratch/step_small_stamps [Nc = 256] [d = 768] [small_step_roles = 0] [launches = 41]
 // Prints, per role: workgroup 0 (the lead), a middle one and the last to finish -- start and end since the launch's first stamp and the
@@ -23,31 +25,42 @@ int main(int argc, char** argv) {
   dprhot_workspace_bytes(B, Nc, d, &wsb);
   CK(hipMalloc(&q, (size_t)B * d * 4)); CK(hipMalloc(&c, (size_t)Nc * d * 4)); CK(hipMalloc(&Qb, (size_t)B * d * 2)); CK(hipMalloc(&Cb, (size_t)Nc * d * 2));
   CK(hipMalloc(&G, (size_t)B * Nc * 2)); CK(hipMalloc(&dq, (size_t)B * d * 4)); CK(hipMalloc(&dc, (size_t)Nc * d * 4));
+  float* dscale; CK(hipMalloc(&dscale, 4));  // the upstream gradient, on the device as the benchmark and the autograd operator pass it
   CK(hipMalloc(&y, B * 8)); CK(hipMalloc(&loss, B * 4)); CK(hipMalloc(&lse, B * 4)); CK(hipMalloc(&sum, 4)); CK(hipMalloc(&ws, wsb));
   std::vector<float> h((size_t)Nc * d);
   unsigned s = 12345;
   for (auto& v : h) { s = s * 1664525u + 1013904223u; v = (((s >> 8) & 0xffff) / 65536.0f - 0.5f) * 0.4f; }
   CK(hipMemcpy(q, h.data() + 17, (size_t)B * d * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(c, h.data(), (size_t)Nc * d * 4, hipMemcpyHostToDevice));
   std::vector<int64_t> hy(B); for (int i = 0; i < B; ++i) hy[i] = i * (Nc / B); CK(hipMemcpy(y, hy.data(), B * 8, hipMemcpyHostToDevice));
+  const float one = 1.0f; CK(hipMemcpy(dscale, &one, 4, hipMemcpyHostToDevice));
   unsigned long long* dptr; CK(hipGetSymbolAddress((void**)&dptr, HIP_SYMBOL(g_dprhot_tmb)));
   std::vector<unsigned long long> t(4 * 4096 * 8);
   const int NK = 4;
-  const char* rname[NK] = {"step_small_kernel (both products per workgroup)", "dC role", "dQ role", "output role"};
-  const int nst[NK] = {8, 5, 6, 5};
+  const bool split = roles == 3;  // kind 0 is the row-store role there
+  const char* rname[NK] = {split ? "row-store role" : "step_small_kernel (both products per workgroup)", "dC role", "dQ role", split ? "loss role" : "output role"};
+  const int nst[NK] = {split ? 3 : 8, 5, 6, 5};
+  const char* pname0[8] = {"", "issue loads", "softmax + G / logits stores (waits for slabs; thread 0)", "", "", "", "", ""};
   const char* pname[NK][8] = {{"", "issue loads", "tiles->LDS (waits for Q, C)", "slab sum (waits for slabs)", "softmax + G", "barrier", "dQ MFMA + slice store + barrier", "dC MFMA + stores + dQ slice sum"},
                              {"", "issue loads", "softmax + G (waits for slabs)", "barrier", "dC MFMA + stores", "", "", ""},
                              {"", "issue loads (waves 0-7)", "softmax + G half (thread 0)", "barrier (C tile of waves 8-15)", "dQ MFMA + slice store + barrier", "slice sum + store", "", ""},
-                             {"", "issue loads", "softmax + G / logits / row stores (waits for slabs)", "barrier", "loss sum + store", "", "", ""}};
+                             {"", "issue loads", "softmax + row stores (waits for slabs)", "barrier", "loss sum + store", "", "", ""}};
+  if (split) for (int i = 0; i < 8; ++i) pname[0][i] = pname0[i];
+  unsigned long long* dtm; CK(hipGetSymbolAddress((void**)&dtm, HIP_SYMBOL(g_dprhot_tm)));
+  unsigned long long tm[64];
+  std::vector<double> sim[3];  // sim launch, workgroup (0, 0, 0): stamps 0 -> 1 -> 4 -> 6
   // [role][which workgroup: 0 = wg 0, 1 = middle, 2 = last to finish][column: 0 = start, 1.. = phases, nst = end] -> samples
   std::vector<double> samp[NK][3][10], span, spank[NK];
   int nwg[NK] = {0, 0, 0, 0};
   for (int it = 0; it < launches + 3; ++it) {
     CK(hipMemset(dptr, 0, t.size() * 8));
-    int rc = dprhot_inbatch_step_f32(q, c, Qb, Cb, B, Nc, d, y, 0, nullptr, 1.f, 1.f / B, 1.f, nullptr, nullptr, loss, lse, sum, G, dq, dc, ws, wsb, nullptr);
+    CK(hipMemset(dtm, 0, sizeof(tm)));
+    int rc = dprhot_inbatch_step_f32(q, c, Qb, Cb, B, Nc, d, y, 0, nullptr, 1.f, 1.f / B, 1.f, dscale, nullptr, loss, lse, sum, G, dq, dc, ws, wsb, nullptr);
     if (rc) { printf("rc=%d %s\n", rc, dprhot_last_error()); return 1; }
     CK(hipDeviceSynchronize());
     CK(hipMemcpy(t.data(), dptr, t.size() * 8, hipMemcpyDeviceToHost));
+    CK(hipMemcpy(tm, dtm, sizeof(tm), hipMemcpyDeviceToHost));
     if (it < 3) continue;
+    if (tm[0] && tm[6]) { sim[0].push_back((tm[1] - tm[0]) * 0.01); sim[1].push_back((tm[4] - tm[1]) * 0.01); sim[2].push_back((tm[6] - tm[4]) * 0.01); }
     unsigned long long g0 = ~0ull, g1 = 0;
     for (int k = 0; k < NK; ++k)
       for (int b = 0; b < 4096; ++b) { const unsigned long long* r = &t[((size_t)k * 4096 + b) * 8]; if (r[0]) { g0 = std::min(g0, r[0]); if (r[nst[k] - 1]) g1 = std::max(g1, r[nst[k] - 1]); } }
@@ -82,6 +95,9 @@ int main(int argc, char** argv) {
       printf(" end %.2f\n", med(samp[k][w][nst[k]]));
     }
   }
+  if (!sim[0].empty())
+    printf("sim launch (sim_small_kernel, workgroup (0, 0, 0), from its first stamp): address arithmetic + issue loads %.2f | waits, conversions, MFMA chain %.2f | copies + slab stores issued %.2f | in all %.2f\n",
+           med(sim[0]), med(sim[1]), med(sim[2]), med(sim[0]) + med(sim[1]) + med(sim[2]));
   float hs; CK(hipMemcpy(&hs, sum, 4, hipMemcpyDeviceToHost)); printf("loss_sum %.4f\n", hs);
   return 0;
 }
