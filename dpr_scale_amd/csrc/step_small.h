@@ -447,62 +447,120 @@ __device__ __forceinline__ void ss_pair16(float x, float& even, float& odd) {
   odd = __uint_as_float(r[1]);
 }
 
+// The row maximum over the 32 lanes of a query row, as ONE asm statement: four DPP row rotations (8, 4, 2, 1) inside each 16-lane half,
+// then the two halves through v_permlane16_swap.  dprhot_row16_max + ss_pair16 + fmaxf form the same values, but fmaxf on a DPP or
+// swap result makes hipcc put a canonicalising v_max_f32 x, x, x (and a v_mov_b32_dpp) in front of every v_max_f32: 17 vector
+// instructions where 7 do (profiles/valu_issue_probe.txt: 9.9 against 3.0 cycles per SIMD and rotation step at four waves per SIMD).
+// The canonicalisation only quiets a signalling NaN, and x is never any NaN here: the thread's maximum starts from -inf, and
+// v_max3_f32 returns a number when one operand is one.  v_max_f32 of two numbers is their maximum whichever operand comes first (the
+// DPP operand has to be src0); its one order-dependent case is max(+0, -0), see ss_pair16.
+// Wait states (inside the string, the hazard recognizer does not look into it): a DPP read and a v_permlane read each need two behind
+// the VALU write of their operand -- s_nop 1 in front of every rotation (the first covers the instruction that formed x) and of the swap.
+// NOT covered: a VALU write of EXEC (v_cmpx) needs five wait states before a DPP read, and an SGPR written by v_readlane /
+// v_readfirstlane is no operand here -- the kernels of this file have no v_cmpx; do not call this directly behind one.
+// The no-NaN argument holds for any NS: with NS >= 2 the scores are sums (an arithmetic result is never a signalling NaN), and with
+// NS == 1 they are the words the sim launch stored, arithmetic results as well; hipcc canonicalises such loaded words in front of
+// v_max3_f32 itself.  A caller that feeds this softmax slabs from elsewhere has to check that again.
+__device__ __forceinline__ float ss_row32_max(float x) {
+  float t;
+  asm("s_nop 1\n\t"
+      "v_max_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\t"
+      "v_max_f32_dpp %0, %0, %0 row_ror:4 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\t"
+      "v_max_f32_dpp %0, %0, %0 row_ror:2 row_mask:0xf bank_mask:0xf\n\t"
+      "s_nop 1\n\t"
+      "v_max_f32_dpp %0, %0, %0 row_ror:1 row_mask:0xf bank_mask:0xf\n\t"
+      "v_mov_b32 %1, %0\n\t"
+      "s_nop 1\n\t"
+      "v_permlane16_swap_b32 %0, %1\n\t"  // %0 = x of the row's lanes 0-15, %1 = of its lanes 16-31, in every lane (ss_pair16)
+      "v_max_f32 %0, %0, %1"
+      : "+v"(x), "=&v"(t));
+  return x;
+}
+
+typedef float ss_f32x2 __attribute__((ext_vector_type(2)));
+
 constexpr int SS_SM_IMAGE = 0;  // dC / dQ roles: G into the LDS image; `lead` (forms 1, 2) also stores every output
 constexpr int SS_SM_LOSS = 1;   // loss block (form 3): logsumexp and row loss only -- no G arithmetic, no G or logits store, no image
 constexpr int SS_SM_ROWS = 2;   // row-store blocks (form 3): G and the logits to memory only -- no image, no logsumexp / row-loss store
+// Issue cycles ("the priced row softmax"; prices: profiles/valu_issue_probe.txt).  At four waves per SIMD a packed fp32
+// instruction costs what any other vector instruction does (3.0 cycles per SIMD) and forms two values, so the element-wise parts
+// -- slab sums, v - m0, * log2(e), e * (1 / sum) and * grad_scale -- are written on two-element vectors: v_pk_add_f32 / v_pk_mul_f32 /
+// v_pk_fma_f32 are the same IEEE operation on each half, in the order of the scalar text.  The row maximum is ss_row32_max.  The probability is
+// fma(e, 1 / sum, addend) with addend -1 at the gold element (the contracted `e * inv - 1` of step_small_kernel) and -0 elsewhere:
+// e * inv is +0 or greater, or NaN, and x + (-0) = x for each of those, so the fma rounds the product as the multiplication did --
+// the select acts on eight constants, ahead of the slabs' arrival, and not on eight pairs of results behind the division.
 template <int CPT, int NS, bool FULL, int MODE = SS_SM_IMAGE>
 __device__ __forceinline__ float ss_row_softmax(const StepSmallArgs& p, float4 (&sa)[CPT][NS], float4 (&sb)[CPT][NS], int row, bool active,
                                                 int64_t yraw, int tr, bool lead, uint16_t* Gs_row, int ncp) {
   const int Nc = FULL ? 256 * CPT : p.Nc, cpr = Nc >> 3;
-  float v[CPT][8];
+  const int yi = FULL || active ? (int)(yraw + p.y_offset) : -1;
+  unsigned dg[CPT];  // the gold column is element dg of the thread's chunk k (dg < 8 in one lane of the row and nowhere else; yi = -1 matches nothing)
+  ss_f32x2 addend[CPT][4];
 #pragma unroll
   for (int k = 0; k < CPT; ++k) {
-    float4 a = sa[k][0], b = sb[k][0];
+    dg[k] = (unsigned)yi - (unsigned)((tr + k * 32) * 8);
+    if constexpr (MODE != SS_SM_LOSS) {
 #pragma unroll
-    for (int z = 1; z < NS; ++z) {  // slab order 0, 1, 2, 3
-      a.x += sa[k][z].x; a.y += sa[k][z].y; a.z += sa[k][z].z; a.w += sa[k][z].w;
-      b.x += sb[k][z].x; b.y += sb[k][z].y; b.z += sb[k][z].z; b.w += sb[k][z].w;
-    }
-    if constexpr (FULL) {
-      v[k][0] = a.x; v[k][1] = a.y; v[k][2] = a.z; v[k][3] = a.w;
-      v[k][4] = b.x; v[k][5] = b.y; v[k][6] = b.z; v[k][7] = b.w;
-    } else {
-      const bool ok = active && (tr + k * 32) < cpr;
-      v[k][0] = ok ? a.x : -INFINITY; v[k][1] = ok ? a.y : -INFINITY; v[k][2] = ok ? a.z : -INFINITY; v[k][3] = ok ? a.w : -INFINITY;
-      v[k][4] = ok ? b.x : -INFINITY; v[k][5] = ok ? b.y : -INFINITY; v[k][6] = ok ? b.z : -INFINITY; v[k][7] = ok ? b.w : -INFINITY;
+      for (int j = 0; j < 4; ++j) addend[k][j] = ss_f32x2{dg[k] == (unsigned)(2 * j) ? -1.0f : -0.0f, dg[k] == (unsigned)(2 * j + 1) ? -1.0f : -0.0f};
+      // (an empty statement that ties the addends to the chunk of the first slab: the label arrives ahead of the slabs, and the
+      // selects are to issue while the SIMD waits for them, not among the sums or behind the division where hipcc would sink them.
+      // Not where the slabs in flight and the addends together would not fit the 128 registers of a 1024-thread workgroup -- three
+      // chunks of four slabs: there the addends are formed where hipcc likes, with nothing spilled)
+      if constexpr (CPT * (NS + 1) * 8 <= 96)
+        asm("" : "+v"(addend[k][0]), "+v"(addend[k][1]), "+v"(addend[k][2]), "+v"(addend[k][3]), "+v"(sa[k][0].x), "+v"(sa[k][0].y),
+            "+v"(sa[k][0].z), "+v"(sa[k][0].w), "+v"(sb[k][0].x), "+v"(sb[k][0].y), "+v"(sb[k][0].z), "+v"(sb[k][0].w));
     }
   }
-  const int yi = FULL || active ? (int)(yraw + p.y_offset) : -1;
+  ss_f32x2 v[CPT][4];  // elements 2 j, 2 j + 1 of chunk k
+#pragma unroll
+  for (int k = 0; k < CPT; ++k) {
+    v[k][0] = ss_f32x2{sa[k][0].x, sa[k][0].y}; v[k][1] = ss_f32x2{sa[k][0].z, sa[k][0].w};
+    v[k][2] = ss_f32x2{sb[k][0].x, sb[k][0].y}; v[k][3] = ss_f32x2{sb[k][0].z, sb[k][0].w};
+#pragma unroll
+    for (int z = 1; z < NS; ++z) {  // slab order 0, 1, 2, 3
+      v[k][0] += ss_f32x2{sa[k][z].x, sa[k][z].y}; v[k][1] += ss_f32x2{sa[k][z].z, sa[k][z].w};
+      v[k][2] += ss_f32x2{sb[k][z].x, sb[k][z].y}; v[k][3] += ss_f32x2{sb[k][z].z, sb[k][z].w};
+    }
+    if constexpr (!FULL) {
+      const bool ok = active && (tr + k * 32) < cpr;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[k][j] = ss_f32x2{ok ? v[k][j][0] : -INFINITY, ok ? v[k][j][1] : -INFINITY};
+    }
+  }
   float m = -INFINITY;
 #pragma unroll
   for (int k = 0; k < CPT; ++k)
 #pragma unroll
-    for (int e = 0; e < 8; ++e) m = fmaxf(m, v[k][e]);
-  m = dprhot_row16_max(m);
-  float even, odd;
-  ss_pair16(m, even, odd);
-  m = fmaxf(even, odd);
-  float sm = 0.f, gold = 0.f;  // exactly one lane of the row holds the gold column
-  unsigned dg[CPT];            // ... as element dg of its chunk k (dg < 8 there, and nowhere else; yi = -1 matches nothing)
-#pragma unroll
-  for (int k = 0; k < CPT; ++k) {
-    dg[k] = (unsigned)yi - (unsigned)((tr + k * 32) * 8);
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      if (dg[k] == (unsigned)e) gold = v[k][e];
-  }
-  float ex[CPT][8];
-  const bool dead = m == -INFINITY;  // a row with every column masked (the reference yields NaN there as well)
-  const float m0 = dead ? 0.f : m;   // every score of a dead row is -inf: exp(-inf - 0) = +0
+    for (int e = 0; e < 8; ++e) m = fmaxf(m, v[k][e >> 1][e & 1]);
+  m = ss_row32_max(m);
+  float gold = 0.f;  // exactly one lane of the row holds the gold column
 #pragma unroll
   for (int k = 0; k < CPT; ++k)
 #pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      ex[k][e] = __expf(v[k][e] - m0);
-      sm += ex[k][e];
+    for (int e = 0; e < 8; ++e)
+      if (dg[k] == (unsigned)e) gold = v[k][e >> 1][e & 1];
+  float ex[CPT][8];
+  const bool dead = m == -INFINITY;  // a row with every column masked (the reference yields NaN there as well)
+  const float m0 = dead ? 0.f : m;   // every score of a dead row is -inf: exp(-inf - 0) = +0
+  const ss_f32x2 m2 = {m0, m0}, log2e = {0x1.715476p+0f, 0x1.715476p+0f};  // __expf(x) = exp2(log2(e) * x), the constant of the HIP header
+#pragma unroll
+  for (int k = 0; k < CPT; ++k)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const ss_f32x2 t = log2e * (v[k][j] - m2);
+      ex[k][2 * j] = __builtin_amdgcn_exp2f(t[0]);
+      ex[k][2 * j + 1] = __builtin_amdgcn_exp2f(t[1]);
     }
+  float sm = 0.f + ex[0][0];  // (as step_small_kernel has it; starting from ex[0][0] is exact and measured no gain: scratch/negative/README.md)
+#pragma unroll
+  for (int k = 0; k < CPT; ++k)
+#pragma unroll
+    for (int e = (k == 0 ? 1 : 0); e < 8; ++e) sm += ex[k][e];
   sm = dprhot_row16_sum(sm);
   gold = dprhot_row16_sum(gold);
+  float even, odd;
   ss_pair16(sm, even, odd);
   sm = even + odd;
   ss_pair16(gold, even, odd);
@@ -517,6 +575,7 @@ __device__ __forceinline__ float ss_row_softmax(const StepSmallArgs& p, float4 (
     }
   }
   if constexpr (MODE != SS_SM_LOSS) {  // (compiled out, not masked: the loss needs no probability)
+  const ss_f32x2 inv2 = {inv_sm, inv_sm}, gs2 = {p.grad_scale, p.grad_scale};
 #pragma unroll
   for (int k = 0; k < CPT; ++k) {
     const int chunk = tr + k * 32;
@@ -524,20 +583,20 @@ __device__ __forceinline__ float ss_row_softmax(const StepSmallArgs& p, float4 (
       uint4 gv = make_uint4(0u, 0u, 0u, 0u);
       if (FULL || (active && chunk < cpr)) {
         const int c0 = chunk * 8;
-        float gg[8];
+        uint32_t gw[4];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          float pr = ex[k][e] * inv_sm;
-          if (dg[k] == (unsigned)e) pr -= 1.0f;
-          gg[e] = pr * p.grad_scale;
+        for (int j = 0; j < 4; ++j) {
+          const ss_f32x2 pr = __builtin_elementwise_fma(ss_f32x2{ex[k][2 * j], ex[k][2 * j + 1]}, inv2, addend[k][j]);
+          const ss_f32x2 gg = pr * gs2;
+          gw[j] = pk_bf16(gg[0], gg[1]);
         }
-        gv = make_uint4(pk_bf16(gg[0], gg[1]), pk_bf16(gg[2], gg[3]), pk_bf16(gg[4], gg[5]), pk_bf16(gg[6], gg[7]));
+        gv = make_uint4(gw[0], gw[1], gw[2], gw[3]);
         if (lead) {
           if (p.G != nullptr) *reinterpret_cast<uint4*>(p.G + (size_t)row * Nc + c0) = gv;
           if (p.S_out != nullptr) {
             float* dst = p.S_out + (size_t)row * Nc + c0;
-            *reinterpret_cast<float4*>(dst) = make_float4(v[k][0], v[k][1], v[k][2], v[k][3]);
-            *reinterpret_cast<float4*>(dst + 4) = make_float4(v[k][4], v[k][5], v[k][6], v[k][7]);
+            *reinterpret_cast<float4*>(dst) = make_float4(v[k][0][0], v[k][0][1], v[k][1][0], v[k][1][1]);
+            *reinterpret_cast<float4*>(dst + 4) = make_float4(v[k][2][0], v[k][2][1], v[k][3][0], v[k][3][1]);
           }
         }
       }
