@@ -114,6 +114,12 @@ SIGNATURES = {
     "dprhot_ivf_search": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                   c_int, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p,
                                   c_int, c_void_p, c_size_t, c_void_p]),
+    "dprhot_pq_encode": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "dprhot_ivf_pq_score": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                    c_void_p, c_int, c_int, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "dprhot_ivf_pq_search": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                     c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_int64, c_int64, c_int64, c_int64, c_int, c_int,
+                                     c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "dprhot_ivf_compact": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
                                    c_void_p, c_void_p, c_int64, c_void_p]),
     "dprhot_ivf_gather": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,

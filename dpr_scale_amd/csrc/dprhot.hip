@@ -34,6 +34,7 @@
 #include "maxsim.h"
 #include "ivf.h"
 #include "ivf_pack.h"
+#include "ivf_pq.h"
 #include "router_head.h"
 
 using namespace dprhot;
@@ -2430,13 +2431,13 @@ int dprhot_ivf_score(const dprhot_bf16* post_vec, const int32_t* post_doc, const
   return launch<ivf_score_kernel>(dim3(blocks), dim3(64 * IVF_WAVES), 0, (hipStream_t)stream, a);
 }
 
-int dprhot_ivf_search(const dprhot_bf16* post_vec, const int32_t* post_doc, const int64_t* exp_off, int64_t n_postings, int n_experts, int dp,
-                      const dprhot_bf16* ent_vec, const int32_t* ent_q, int n_entries, const int32_t* bexp, const int32_t* bexp_off,
-                      int n_bexp, int nq, const dprhot_bf16* cls_q, const dprhot_bf16* cls_doc, int dc, int64_t cls_rows,
-                      int64_t corpus_len, int64_t id_begin, int64_t id_end, int k, int chunk, float* values, int64_t* indices, int first,
-                      void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = ivf_check_index(post_vec, post_doc, exp_off, n_postings, n_experts, dp)) return rc;
-  if (int rc = ivf_check_batch(nq, n_entries, n_bexp, ent_vec, ent_q, bexp, bexp_off)) return rc;
+extern "C++" {
+// the chunk loop of dprhot_ivf_search and dprhot_ivf_pq_search behind their index and batch checks: score(j0, cols, S, ld) adds the
+// expert part of doc ids j0 .. j0 + cols into S
+template <class Score>
+static int ivf_search_chunks(Score score, int nq, const dprhot_bf16* cls_q, const dprhot_bf16* cls_doc, int dc, int64_t cls_rows,
+                             int64_t corpus_len, int64_t id_begin, int64_t id_end, int k, int chunk, float* values, int64_t* indices,
+                             int first, void* workspace, size_t workspace_bytes, void* stream) {
   REQUIRE(values && indices, "NULL pointer");
   REQUIRE(corpus_len > 0 && corpus_len < (1ll << 31), "corpus_len=%lld out of range (1 .. 2^31 - 1)", (long long)corpus_len);
   REQUIRE(k >= 1 && k <= corpus_len, "topk=%d out of range (1 .. corpus_len=%lld)", k, (long long)corpus_len);
@@ -2469,9 +2470,7 @@ int dprhot_ivf_search(const dprhot_bf16* post_vec, const int32_t* post_doc, cons
     } else {
       HIP_TRY(hipMemsetAsync(S, 0, (size_t)nq * ld * sizeof(float), st));
     }
-    if (int rc = dprhot_ivf_score(post_vec, post_doc, exp_off, n_postings, n_experts, dp, ent_vec, ent_q, n_entries, bexp, bexp_off, n_bexp,
-                                  nq, j0, cols, S, ld, stream))
-      return rc;
+    if (int rc = score(j0, cols, S, ld)) return rc;
     const int f = (first && j0 == id_begin) ? 1 : 0;
     if (wide) {
       if (int rc = dprhot_topk_update_wide(S, nq, cols, ld, j0, k, values, indices, f, wide_ws, workspace_bytes - s_bytes, stream)) return rc;
@@ -2480,6 +2479,98 @@ int dprhot_ivf_search(const dprhot_bf16* post_vec, const int32_t* post_doc, cons
     }
   }
   return DPRHOT_OK;
+}
+}  // extern "C++"
+
+int dprhot_ivf_search(const dprhot_bf16* post_vec, const int32_t* post_doc, const int64_t* exp_off, int64_t n_postings, int n_experts, int dp,
+                      const dprhot_bf16* ent_vec, const int32_t* ent_q, int n_entries, const int32_t* bexp, const int32_t* bexp_off,
+                      int n_bexp, int nq, const dprhot_bf16* cls_q, const dprhot_bf16* cls_doc, int dc, int64_t cls_rows,
+                      int64_t corpus_len, int64_t id_begin, int64_t id_end, int k, int chunk, float* values, int64_t* indices, int first,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = ivf_check_index(post_vec, post_doc, exp_off, n_postings, n_experts, dp)) return rc;
+  if (int rc = ivf_check_batch(nq, n_entries, n_bexp, ent_vec, ent_q, bexp, bexp_off)) return rc;
+  auto score = [&](int64_t j0, int cols, float* S, int ld) {
+    return dprhot_ivf_score(post_vec, post_doc, exp_off, n_postings, n_experts, dp, ent_vec, ent_q, n_entries, bexp, bexp_off, n_bexp, nq, j0,
+                            cols, S, ld, stream);
+  };
+  return ivf_search_chunks(score, nq, cls_q, cls_doc, dc, cls_rows, corpus_len, id_begin, id_end, k, chunk, values, indices, first, workspace,
+                           workspace_bytes, stream);
+}
+
+// ---- product-quantised postings (csrc/ivf_pq.h) ----
+static int pq_check_shape(int dp, int dsub) {
+  REQUIRE(dsub == 2 || dsub == 4 || dsub == 8, "dsub=%d: sub-vectors of 2, 4 or 8 features", dsub);
+  REQUIRE(dp > 0 && dp % 32 == 0, "dp=%d must be a positive multiple of 32 (pad with zeros)", dp);
+  if (dp > 64) return fail(DPRHOT_E_UNSUPPORTED, "dp=%d: product-quantised postings are built for dp = 32 and 64", dp);
+  return DPRHOT_OK;
+}
+
+static int ivf_pq_check_index(const void* post_code, const void* codebook, int dsub, const void* post_doc, const void* exp_off,
+                              int64_t n_postings, int n_experts, int dp) {
+  REQUIRE(n_postings >= 0 && n_postings < (1ll << 40), "n_postings=%lld out of range (< 2^40)", (long long)n_postings);
+  REQUIRE(n_experts > 0 && exp_off, "bad index: n_experts=%d", n_experts);
+  REQUIRE(codebook != nullptr, "NULL pointer (codebook)");
+  REQUIRE(n_postings == 0 || (post_code && post_doc), "NULL pointer (postings)");
+  if (int rc = pq_check_shape(dp, dsub)) return rc;
+  REQUIRE(aligned16(codebook) && (n_postings == 0 || aligned16(post_code)), "codes and codebook must be 16-byte aligned");
+  return DPRHOT_OK;
+}
+
+extern "C++" {
+template <int DSUB>
+static int ivf_pq_launch(int dp, unsigned blocks, hipStream_t st, const IvfPqArgs& a) {
+  if (dp == 32) return launch<ivf_pq_score_kernel<DSUB, 32>>(dim3(blocks), dim3(64 * IVF_WAVES), 0, st, a);
+  return launch<ivf_pq_score_kernel<DSUB, 64>>(dim3(blocks), dim3(64 * IVF_WAVES), 0, st, a);
+}
+}  // extern "C++"
+
+int dprhot_pq_encode(const dprhot_bf16* vec, int64_t n, int dp, const dprhot_bf16* codebook, int dsub, uint8_t* codes, void* stream) {
+  REQUIRE(n >= 0 && n < (1ll << 40), "n=%lld out of range (0 .. 2^40 - 1)", (long long)n);
+  REQUIRE(codebook != nullptr, "NULL pointer (codebook)");
+  REQUIRE(n == 0 || (vec && codes), "NULL pointer (vec, codes)");
+  if (int rc = pq_check_shape(dp, dsub)) return rc;
+  if (n == 0) return DPRHOT_OK;
+  PqEncodeArgs a{reinterpret_cast<const uint16_t*>(vec), (long long)n, dp, reinterpret_cast<const uint16_t*>(codebook), codes};
+  const long long want = (n + PQ_ENC_THREADS - 1) / PQ_ENC_THREADS;
+  const dim3 grid((unsigned)(want < 65536 ? want : 65536), (unsigned)(dp / dsub)), block(PQ_ENC_THREADS);  // (rows beyond: grid stride)
+  hipStream_t st = (hipStream_t)stream;
+  if (dsub == 2) return launch<pq_encode_kernel<2>>(grid, block, 0, st, a);
+  if (dsub == 4) return launch<pq_encode_kernel<4>>(grid, block, 0, st, a);
+  return launch<pq_encode_kernel<8>>(grid, block, 0, st, a);
+}
+
+int dprhot_ivf_pq_score(const uint8_t* post_code, const dprhot_bf16* codebook, int dsub, const int32_t* post_doc, const int64_t* exp_off,
+                        int64_t n_postings, int n_experts, int dp, const dprhot_bf16* ent_vec, const int32_t* ent_q, int n_entries,
+                        const int32_t* bexp, const int32_t* bexp_off, int n_bexp, int nq, int64_t doc_begin, int cols, float* S, int64_t ld,
+                        void* stream) {
+  if (int rc = ivf_pq_check_index(post_code, codebook, dsub, post_doc, exp_off, n_postings, n_experts, dp)) return rc;
+  if (int rc = ivf_check_batch(nq, n_entries, n_bexp, ent_vec, ent_q, bexp, bexp_off)) return rc;
+  REQUIRE(S != nullptr, "NULL pointer (S)");
+  REQUIRE(cols > 0 && ld >= cols, "bad shape cols=%d ld=%lld", cols, (long long)ld);
+  REQUIRE(doc_begin >= 0 && doc_begin + cols < (1ll << 31), "doc ids %lld .. +%d must stay below 2^31", (long long)doc_begin, cols);
+  if (n_entries == 0 || n_postings == 0) return DPRHOT_OK;
+  IvfPqArgs a{post_code, reinterpret_cast<const uint16_t*>(codebook), post_doc, reinterpret_cast<const long long*>(exp_off), n_experts,
+              reinterpret_cast<const uint16_t*>(ent_vec), ent_q, bexp, bexp_off, n_bexp, nq, (long long)doc_begin, cols, S, (long long)ld};
+  const unsigned blocks = (unsigned)cdiv(cdiv(cols, IVF_T), IVF_WAVES);
+  hipStream_t st = (hipStream_t)stream;
+  if (dsub == 2) return ivf_pq_launch<2>(dp, blocks, st, a);
+  if (dsub == 4) return ivf_pq_launch<4>(dp, blocks, st, a);
+  return ivf_pq_launch<8>(dp, blocks, st, a);
+}
+
+int dprhot_ivf_pq_search(const uint8_t* post_code, const dprhot_bf16* codebook, int dsub, const int32_t* post_doc, const int64_t* exp_off,
+                         int64_t n_postings, int n_experts, int dp, const dprhot_bf16* ent_vec, const int32_t* ent_q, int n_entries,
+                         const int32_t* bexp, const int32_t* bexp_off, int n_bexp, int nq, const dprhot_bf16* cls_q,
+                         const dprhot_bf16* cls_doc, int dc, int64_t cls_rows, int64_t corpus_len, int64_t id_begin, int64_t id_end, int k,
+                         int chunk, float* values, int64_t* indices, int first, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = ivf_pq_check_index(post_code, codebook, dsub, post_doc, exp_off, n_postings, n_experts, dp)) return rc;
+  if (int rc = ivf_check_batch(nq, n_entries, n_bexp, ent_vec, ent_q, bexp, bexp_off)) return rc;
+  auto score = [&](int64_t j0, int cols, float* S, int ld) {
+    return dprhot_ivf_pq_score(post_code, codebook, dsub, post_doc, exp_off, n_postings, n_experts, dp, ent_vec, ent_q, n_entries, bexp,
+                               bexp_off, n_bexp, nq, j0, cols, S, ld, stream);
+  };
+  return ivf_search_chunks(score, nq, cls_q, cls_doc, dc, cls_rows, corpus_len, id_begin, id_end, k, chunk, values, indices, first, workspace,
+                           workspace_bytes, stream);
 }
 
 // ---- postings and query batches from encoder outputs (csrc/ivf_pack.h) ----

@@ -607,6 +607,40 @@ class HipKernels:
                                                    int(id_end), values.shape[1], int(chunk), _ptr(values), _ptr(indices),
                                                    int(bool(first)), _ptr(ws), ws.numel(), self._stream()), "dprhot_ivf_search")
 
+    # -- product-quantised postings (csrc/ivf_pq.h; dpr_scale_amd/ivf.py owns training and the index) ----
+    def pq_encode(self, vec, codebook):
+        """codes uint8 [n, m] of the rows vec bf16 [n, dp] under codebook bf16 [m, 256, dsub] (dprhot_pq_encode)."""
+        self._require_gpu(vec, codebook)
+        assert vec.dtype == torch.bfloat16 and codebook.dtype == torch.bfloat16 and vec.dim() == 2 and codebook.dim() == 3
+        vec, codebook = vec.contiguous(), codebook.contiguous()
+        n, dp = vec.shape
+        m, _, dsub = codebook.shape
+        assert codebook.shape[1] == 256 and m * dsub == dp, f"codebook {tuple(codebook.shape)} for rows of width {dp}"
+        codes = torch.empty((n, m), dtype=torch.uint8, device=vec.device)
+        self._lib.check(self.lib.dprhot_pq_encode(_ptr(vec), n, dp, _ptr(codebook), dsub, _ptr(codes), self._stream()), "dprhot_pq_encode")
+        return codes
+
+    def ivf_pq_score(self, index, qb, doc_begin, cols, S):
+        """ivf_score for an IVFPQIndex (dprhot_ivf_pq_score)."""
+        self._require_gpu(index.post_code, index.codebook, index.post_doc, index.exp_off, qb.ent_vec, qb.ent_q, qb.bexp, qb.boff, S)
+        self._lib.check(self.lib.dprhot_ivf_pq_score(_ptr(index.post_code), _ptr(index.codebook), index.dsub, _ptr(index.post_doc),
+                                                     _ptr(index.exp_off), index.n_postings, index.n_experts, index.dp, _ptr(qb.ent_vec),
+                                                     _ptr(qb.ent_q), qb.n_entries, _ptr(qb.bexp), _ptr(qb.boff), int(qb.bexp.shape[0]),
+                                                     qb.nq, int(doc_begin), int(cols), _ptr(S), S.stride(0), self._stream()),
+                        "dprhot_ivf_pq_score")
+
+    def ivf_pq_search(self, index, qb, id_begin, id_end, values, indices, first, chunk, ws):
+        """ivf_search for an IVFPQIndex (dprhot_ivf_pq_search); the workspace is ivf_workspace's."""
+        self._require_gpu(index.post_code, index.codebook, index.post_doc, index.exp_off, index.cls, qb.ent_vec, qb.ent_q, qb.bexp, qb.boff,
+                          qb.cls, values, indices, ws)
+        self._lib.check(self.lib.dprhot_ivf_pq_search(_ptr(index.post_code), _ptr(index.codebook), index.dsub, _ptr(index.post_doc),
+                                                      _ptr(index.exp_off), index.n_postings, index.n_experts, index.dp, _ptr(qb.ent_vec),
+                                                      _ptr(qb.ent_q), qb.n_entries, _ptr(qb.bexp), _ptr(qb.boff), int(qb.bexp.shape[0]),
+                                                      qb.nq, _ptr(qb.cls), _ptr(index.cls), index.dc,
+                                                      0 if index.cls is None else index.cls.shape[0], index.corpus_len, int(id_begin),
+                                                      int(id_end), values.shape[1], int(chunk), _ptr(values), _ptr(indices),
+                                                      int(bool(first)), _ptr(ws), ws.numel(), self._stream()), "dprhot_ivf_pq_search")
+
     # -- postings and query batches from encoder outputs (csrc/ivf_pack.h; dpr_scale_amd/ivf.py drives them) ----
     def ivf_compact(self, expert_ids, weights, att, row_ids, test_weight, min_weight=0.0, capacity=None):
         """The kept slots of a repr dict in (b, t, k) order (dprhot_ivf_compact).  expert_ids [B, L, K] of any integer type, weights

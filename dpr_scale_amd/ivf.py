@@ -18,7 +18,12 @@ packed query batch and `IndexBuilder` the postings -- the on-disk tree above or 
 with the kept slots listed and the weighted vectors written by libdprhot.so (dprhot_ivf_compact / dprhot_ivf_gather) in the order and
 with the roundings of the host loops they replace.
 
-Not supported (NotImplementedError / out of scope): product quantisation, `portion` < 1, hnsw, expert parallelism across GPUs, ColBERT.
+Product quantisation (the reference's quantizer="pq", sub_vec_dim): `IVFIndex.quantize` / `load_index(...,
+quantizer="pq")` / `IndexBuilder.finish(quantizer="pq")` give an `IVFPQIndex` whose postings are 8-bit codes over sub-vectors of 2, 4
+or 8 features and one bf16 codebook; its search returns, bit for bit, the dense search over the decoded rows (`IVFPQIndex.decode`).
+
+Not supported (NotImplementedError / out of scope): per-expert codebooks, code widths other than 8 bits, a product-quantised index
+for dp > 64 or on the CPU, `portion` < 1, hnsw, expert parallelism across GPUs, ColBERT.
 """
 import collections
 import glob
@@ -155,6 +160,8 @@ def read_postings(ctx_embeddings_dir, corpus_len):
 class IVFIndex:
     """Device-resident inverted index; `search` stands where the reference's IVFGPUIndex.search stood."""
 
+    _search_kernel = "ivf_search"  # the kernel-table entry search_packed folds a doc-id range with
+
     def __init__(self, experts, docs, vecs, cls, corpus_len, device, chunk=None, kernels=None):
         """From unsorted CPU postings: expert int64 [P], doc int64 [P], vec fp32 [P, d], cls fp32 [corpus_len, dc] or None."""
         corpus_len = int(corpus_len)
@@ -201,6 +208,11 @@ class IVFIndex:
         self.latency = collections.defaultdict(float)
         self.latency["encode_time"] += 0.0  # test_epoch_end of the retrieval task pops this key
 
+    @property
+    def nbytes(self):
+        """Bytes of device memory the index holds (posting rows, doc ids, offsets, CLS rows)."""
+        return sum(t.numel() * t.element_size() for t in (self.post_doc, self.post_vec, self.exp_off, self.cls) if t is not None)
+
     def _kernels(self):
         if self.kn is None:
             from . import hotpath
@@ -234,7 +246,7 @@ class IVFIndex:
         ws = kn.ivf_workspace(qb.nq, qb.n_entries, chunk, self.cls is not None, topk, self.post_doc)
         first = True
         for b, e in (id_ranges if id_ranges is not None else [(0, self.corpus_len)]):
-            kn.ivf_search(self, qb, int(b), int(e), values, indices, first, chunk, ws)
+            getattr(kn, self._search_kernel)(self, qb, int(b), int(e), values, indices, first, chunk, ws)
             first = False
         return values, indices
 
@@ -247,16 +259,188 @@ class IVFIndex:
         self.latency["search_time"] += time.perf_counter() - tic
         return out
 
+    def quantize(self, dsub=4, codebook=None, **train_kwargs):
+        """The IVFPQIndex of this index: posting rows replaced by 8-bit codes over sub-vectors of `dsub` features (DESIGN.md section
+        10.2).  Trains a codebook on the index's own rows (train_pq(**train_kwargs)) unless one is given; the result shares
+        post_doc, exp_off and the CLS rows with this index and keeps no reference to the dense rows."""
+        kn = self._kernels()
+        if codebook is None:
+            codebook = train_pq(self.post_vec, dsub=dsub, kernels=kn, **train_kwargs)
+        elif train_kwargs:
+            raise TypeError(f"a codebook was given: nothing to train with {sorted(train_kwargs)}")
+        codebook = _check_codebook(codebook, self.dp, dsub).to(self.device).contiguous()
+        codes = kn.pq_encode(self.post_vec, codebook)
+        return IVFPQIndex.from_packed(self.post_doc, codes, codebook, self.exp_off, self.cls, self.corpus_len, self.d, chunk=self.chunk,
+                                      kernels=kn)
 
-def load_index(ctx_embeddings_dir, corpus_len, device=None, chunk=None, kernels=None):
+
+# ---- product-quantised postings (DESIGN.md section 10.2) -----------------------------------------------------------------------------
+
+PQ_SUB_VEC_DIMS = (2, 4, 8)  # whole sub-vectors inside the 8 consecutive bf16 values of an MFMA fragment
+PQ_MAX_DP = 64               # dprhot_ivf_pq_score keeps the codebook (dp * 512 bytes) in LDS next to its 32 KiB table
+
+
+def _check_pq_shape(dp, dsub):
+    if dsub not in PQ_SUB_VEC_DIMS:
+        raise ValueError(f"sub_vec_dim={dsub}: one of {PQ_SUB_VEC_DIMS}")
+    if dp > PQ_MAX_DP:
+        raise NotImplementedError(f"product quantisation of rows of padded width {dp}: at most {PQ_MAX_DP}")
+
+
+def _check_codebook(codebook, dp, dsub):
+    _check_pq_shape(dp, dsub)
+    if codebook.dtype != _BF16 or tuple(codebook.shape) != (dp // int(dsub), 256, int(dsub)):
+        raise ValueError(f"codebook {codebook.dtype} {tuple(codebook.shape)}; bf16 {(dp // int(dsub), 256, int(dsub))} expected")
+    return codebook
+
+
+def pq_decode(codes, codebook):
+    """bf16 [n, m * dsub]: row p holds codebook[j, codes[p, j], :] for j = 0 .. m - 1.  codes uint8 [n, m], codebook [m, 256, dsub]
+    (any dtype); plain indexing, on whatever device the tensors live."""
+    m, _, dsub = codebook.shape
+    if codes.dim() != 2 or codes.shape[1] != m or codes.dtype != torch.uint8:
+        raise ValueError(f"codes {codes.dtype} {tuple(codes.shape)} for a codebook of {m} subspaces")
+    cols = torch.arange(m, device=codes.device).unsqueeze(0)
+    parts = [codebook[cols, codes[lo:lo + (1 << 22)].long()].reshape(-1, m * dsub) for lo in range(0, codes.shape[0], 1 << 22)]
+    return torch.cat(parts, 0) if parts else codebook.new_zeros((0, m * dsub))
+
+
+def train_pq(post_vec, dsub=4, iters=10, train_size=65536, seed=0, kernels=None, on_iteration=None):
+    """Codebook bf16 [dp / dsub, 256, dsub] for the bf16 rows post_vec [P, dp] on a HIP device: Lloyd's k-means per subspace on a
+    seeded sample of `train_size` rows (all of them when there are no more; rows with a non-finite value are left out).
+      init      per subspace 256 distinct sub-vectors of the sample (a seeded choice among the distinct ones in sorted order); with
+                fewer than 256 distinct ones all of them, the remaining slots zeros
+      assign    dprhot_pq_encode -- the rule the index is encoded with, on the bf16 centroids search will see
+      update    fp32 sum of a centroid's sub-vectors in sample order by ONE owner (a stable sort by (subspace, code), then
+                torch.segment_reduce: no floating-point atomics), divided by the count in fp32, rounded to bf16 after every
+                iteration; an empty centroid keeps its value
+    Same inputs and seed: torch.equal codebooks.  `on_iteration(i, codebook)` sees the codebook before the first (i = 0) and after
+    every iteration."""
+    kn = _default_kernels(kernels)
+    if post_vec.dtype != _BF16 or post_vec.dim() != 2:
+        raise ValueError(f"rows {post_vec.dtype} {tuple(post_vec.shape)}; bf16 [P, dp] expected")
+    P, dp = int(post_vec.shape[0]), int(post_vec.shape[1])
+    dsub, dev = int(dsub), post_vec.device
+    _check_pq_shape(dp, dsub)
+    m = dp // dsub
+    gen = torch.Generator().manual_seed(int(seed))
+    if P > int(train_size):
+        x = post_vec[torch.randperm(P, generator=gen)[: int(train_size)].sort().values.to(dev)]
+    else:
+        x = post_vec
+    x = x[torch.isfinite(x.float()).all(1)].contiguous()
+    ns = int(x.shape[0])
+    sub = x.view(ns, m, dsub)
+    codebook = torch.zeros((m, 256, dsub), dtype=_BF16, device=dev)
+    for j in range(m):
+        u = torch.unique(sub[:, j].float() + 0.0, dim=0)  # sorted rows; + 0.0: one zero, not two
+        if u.shape[0] > 256:
+            u = u[torch.randperm(u.shape[0], generator=gen)[:256].sort().values.to(dev)]
+        codebook[j, : u.shape[0]] = u.to(_BF16)
+    if on_iteration is not None:
+        on_iteration(0, codebook.clone())
+    base = (torch.arange(m, device=dev) * 256).unsqueeze(0)
+    flat = sub.reshape(ns * m, dsub).float()
+    for it in range(int(iters) if ns else 0):
+        key = (kn.pq_encode(x, codebook).long() + base).reshape(-1)
+        order = torch.sort(key, stable=True).indices  # sample order survives inside a centroid
+        counts = torch.bincount(key, minlength=m * 256)
+        sums = torch.segment_reduce(flat[order], "sum", lengths=counts, axis=0, unsafe=True)
+        mean = (sums / counts.clamp(min=1).to(torch.float32).unsqueeze(1)).to(_BF16).view(m, 256, dsub)
+        codebook = torch.where((counts > 0).view(m, 256, 1), mean, codebook)
+        if on_iteration is not None:
+            on_iteration(it + 1, codebook.clone())
+    return codebook
+
+
+class IVFPQIndex(IVFIndex):
+    """IVFIndex with product-quantised postings: post_code uint8 [P, m] and ONE codebook bf16 [m, 256, dsub] instead of post_vec.
+    `search` / `search_packed` return, bit for bit, what `decode()` -- the IVFIndex over the decoded rows -- returns."""
+
+    _search_kernel = "ivf_pq_search"
+
+    def __init__(self, *args, **kwargs):
+        raise TypeError("an IVFPQIndex comes from IVFIndex.quantize, IVFPQIndex.from_packed or load_pq_index")
+
+    @classmethod
+    def from_packed(cls, post_doc, post_code, codebook, exp_off, cls_rows, corpus_len, d, chunk=None, kernels=None):
+        """From tensors in the device layout (csrc/ivf_pq.h), on their device: post_doc int32 [P] sorted by (expert, doc), post_code
+        uint8 [P, m] in the same order, codebook bf16 [m, 256, dsub], exp_off int64 [V + 1], cls_rows as for IVFIndex.from_packed."""
+        self = cls.__new__(cls)
+        m, _, dsub = codebook.shape
+        _check_codebook(codebook, m * dsub, dsub)
+        assert post_doc.dtype == torch.int32 and exp_off.dtype == torch.int64 and post_code.dtype == torch.uint8
+        assert post_code.shape == (post_doc.shape[0], m) and post_code.is_contiguous() and codebook.is_contiguous()
+        self.device = post_doc.device
+        self.corpus_len, self.d = int(corpus_len), int(d)
+        self.n_experts, self.n_postings = int(exp_off.shape[0]) - 1, int(post_doc.shape[0])
+        self.post_doc, self.post_code, self.codebook, self.exp_off = post_doc, post_code, codebook, exp_off
+        self.dsub, self.dp = int(dsub), int(m * dsub)
+        self.cls, self.dc = cls_rows, (0 if cls_rows is None else int(cls_rows.shape[1]))
+        self.chunk = None if chunk is None else int(chunk)
+        self.kn = kernels
+        self.latency = collections.defaultdict(float)
+        self.latency["encode_time"] += 0.0
+        return self
+
+    def _tensors(self):
+        return dict(post_doc=self.post_doc, post_code=self.post_code, codebook=self.codebook, exp_off=self.exp_off, cls=self.cls)
+
+    @property
+    def nbytes(self):
+        """Bytes of device memory the index holds (codes, doc ids, offsets, codebook, CLS rows)."""
+        return sum(t.numel() * t.element_size() for t in self._tensors().values() if t is not None)
+
+    def decode(self):
+        """The IVFIndex whose post_vec rows are pq_decode(post_code, codebook): the index this one searches, by definition."""
+        return IVFIndex.from_packed(self.post_doc, pq_decode(self.post_code, self.codebook), self.exp_off, self.cls, self.corpus_len, self.d,
+                                    chunk=self.chunk, kernels=self.kn)
+
+    def quantize(self, *args, **kwargs):
+        raise TypeError("the index is quantised already")
+
+    def save(self, path):
+        """One torch.save of the tensors (on the CPU) and sizes; load_pq_index reads it back."""
+        blob = {k: (None if t is None else t.cpu()) for k, t in self._tensors().items()}
+        blob.update(format="dpr_scale_amd.ivf_pq/1", corpus_len=self.corpus_len, d=self.d, dsub=self.dsub)
+        torch.save(blob, path)
+        return path
+
+
+def load_pq_index(path, device=None, chunk=None, kernels=None):
+    """The IVFPQIndex that IVFPQIndex.save wrote, placed on `device`."""
+    device = torch.device(device) if device is not None else torch.device("cuda", 0)
+    blob = torch.load(path, map_location="cpu", weights_only=True)
+    if blob.get("format") != "dpr_scale_amd.ivf_pq/1":
+        raise ValueError(f"{path}: not a product-quantised index file")
+    mv = lambda t: None if t is None else t.contiguous().to(device)
+    return IVFPQIndex.from_packed(mv(blob["post_doc"]), mv(blob["post_code"]), mv(blob["codebook"]), mv(blob["exp_off"]), mv(blob["cls"]),
+                                  blob["corpus_len"], blob["d"], chunk=chunk, kernels=kernels)
+
+
+def _quantized(index, quantizer, sub_vec_dim, train_kwargs):
+    if quantizer in (None, "None"):
+        if train_kwargs:
+            raise TypeError(f"unexpected arguments {sorted(train_kwargs)}")
+        return index
+    if quantizer != "pq":
+        raise NotImplementedError(f"quantizer={quantizer!r}: None or 'pq'")
+    return index.quantize(dsub=sub_vec_dim, **train_kwargs)
+
+
+def load_index(ctx_embeddings_dir, corpus_len, device=None, chunk=None, kernels=None, quantizer=None, sub_vec_dim=4, **train_kwargs):
     """Reads every `expert_*/{id}.pkl` and `cls_*.pkl` under `ctx_embeddings_dir`, merges the shard directories into ONE index (a
     doc's score is a sum over experts: shards are never searched one by one) and places it on `device`.
 
     Doc ids are the corpus ids the writer stored.  With CLS files they must equal the row numbers of the CLS files concatenated in rank
-    order (rank r's ids inside rank r's rows, all rows together = corpus_len); an index for which that does not hold raises."""
+    order (rank r's ids inside rank r's rows, all rows together = corpus_len); an index for which that does not hold raises.
+
+    quantizer="pq" (the reference's option; sub_vec_dim in {2, 4, 8}): the index is quantised on the device once it is built
+    (IVFIndex.quantize; `train_kwargs` go to train_pq) and an IVFPQIndex comes back."""
     device = torch.device(device) if device is not None else torch.device("cuda", 0)
     experts, docs, vecs, cls = read_postings(ctx_embeddings_dir, int(corpus_len))
-    return IVFIndex(experts, docs, vecs, cls, corpus_len, device, chunk=chunk, kernels=kernels)
+    return _quantized(IVFIndex(experts, docs, vecs, cls, corpus_len, device, chunk=chunk, kernels=kernels), quantizer, sub_vec_dim,
+                      train_kwargs)
 
 
 # ---- both sides from the encoders' repr tensors, on the device ----------------------------------------------------------------------
@@ -426,9 +610,9 @@ class IndexBuilder:
             lo += c
         return ctx_embeddings_dir
 
-    def finish(self, chunk=None):
+    def finish(self, chunk=None, quantizer=None, sub_vec_dim=4, **train_kwargs):
         """The IVFIndex of everything added: postings stably sorted by (expert, doc), vectors rounded to bf16 and padded to a multiple
-        of 32 columns by dprhot_ivf_gather, CLS rows with their zero tail."""
+        of 32 columns by dprhot_ivf_gather, CLS rows with their zero tail.  quantizer="pq": its quantize(sub_vec_dim, **train_kwargs)."""
         if self.corpus_len is None or not 0 < self.corpus_len < 2 ** 31:
             raise ValueError(f"corpus_len={self.corpus_len} out of range (1 .. 2^31 - 1)")
         expert, doc, _, vec = self._cat()
@@ -459,4 +643,4 @@ class IndexBuilder:
         out = [post_doc, post_vec, exp_off, cls_rows]
         if self.device is not None and self.device != dev:
             out = [None if t is None else t.to(self.device) for t in out]
-        return IVFIndex.from_packed(*out, self.corpus_len, d, chunk=chunk, kernels=self.kn)
+        return _quantized(IVFIndex.from_packed(*out, self.corpus_len, d, chunk=chunk, kernels=self.kn), quantizer, sub_vec_dim, train_kwargs)

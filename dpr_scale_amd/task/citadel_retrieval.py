@@ -5,8 +5,10 @@ Same constructor kwargs (:15-30), `_eval_step` (:84-140), `test_epoch_end` (:145
 ship; here the index is dpr_scale_amd.ivf.load_index (one device-resident inverted index, scored by libdprhot.so).  Query batches whose
 repr tensors are on the index's device are packed there (ivf.pack_queries_device; `device_pack = False` keeps the host loop).
 
-Scope: `quantizer="pq"`, `cuda=False`, `portion` below 1.0 and `hnsw_index` raise NotImplementedError; `expert_parallel` (the
-reference's split of experts across GPUs) is accepted and ignored: the index lives on one device.
+Scope: `cuda=False`, `portion` below 1.0 and `hnsw_index` raise NotImplementedError; `expert_parallel` (the reference's split of
+experts across GPUs) is accepted and ignored: the index lives on one device.  `quantizer="pq"` raises NotImplementedError in
+CITADELRetrievalTask, whose index is the plain one, and is what CITADELPQRetrievalTask is for: the same task over an
+ivf.IVFPQIndex (8-bit codes over sub-vectors of `sub_vec_dim` in {2, 4, 8} features).
 """
 import collections
 import json
@@ -97,7 +99,10 @@ class CITADELRetrievalTask(MultiVecRetrieverTask):
         print(f"Loading passages from {self.passages}")
         self.ctxs = PassageTable(self.passages)
         print("Setting up index...")
-        self.index = ivf.load_index(self.ctx_embeddings_dir, len(self.ctxs), self.device if self.device.type == "cuda" else None)
+        self.index = self._load_index(self.device if self.device.type == "cuda" else None)
+
+    def _load_index(self, device):
+        return ivf.load_index(self.ctx_embeddings_dir, len(self.ctxs), device)
 
     def forward(self, query_ids):
         return self.encode_queries(query_ids)
@@ -176,3 +181,35 @@ class CITADELRetrievalTask(MultiVecRetrieverTask):
                 ctxs.append({"id": row["id"], "title": row["title"], "text": row["text"], "score": float(score)})
             out.append({"question": question, "answers": answer, "ctxs": ctxs})
         return out
+
+
+class CITADELPQRetrievalTask(CITADELRetrievalTask):
+    """CITADELRetrievalTask with quantizer="pq": same constructor kwargs, same _eval_step, over a product-quantised index.  `setup`
+    loads `ctx_embeddings_dir/pq_index.pt` when that file exists (ivf.load_pq_index); otherwise it builds the plain index, trains a
+    codebook on it and encodes it (ivf.load_index(..., quantizer="pq")) -- and writes the file when `save_quantized` is set, so that
+    a large index is not retrained at every start."""
+
+    save_quantized = False  # write ctx_embeddings_dir/pq_index.pt after quantising (True: the next setup loads it)
+    PQ_FILE = "pq_index.pt"
+
+    def __init__(self, *args, quantizer="pq", sub_vec_dim=4, **kwargs):
+        if quantizer != "pq":
+            raise NotImplementedError(f'quantizer={quantizer!r}: CITADELPQRetrievalTask is the quantizer="pq" task '
+                                      f"(CITADELRetrievalTask takes the plain index)")
+        if sub_vec_dim not in ivf.PQ_SUB_VEC_DIMS:
+            raise NotImplementedError(f"sub_vec_dim={sub_vec_dim}: sub-vectors of {ivf.PQ_SUB_VEC_DIMS} features")
+        super().__init__(*args, quantizer=None, sub_vec_dim=sub_vec_dim, **kwargs)  # refuses what the plain task refuses
+        self.quantizer = "pq"
+
+    def _load_index(self, device):
+        path = os.path.join(self.ctx_embeddings_dir, self.PQ_FILE)
+        if os.path.exists(path):
+            index = ivf.load_pq_index(path, device)
+            if index.corpus_len != len(self.ctxs) or index.dsub != self.sub_vec_dim:
+                raise ValueError(f"{path}: an index of {index.corpus_len} passages with sub_vec_dim={index.dsub}; "
+                                 f"{len(self.ctxs)} passages and sub_vec_dim={self.sub_vec_dim} were asked for")
+            return index
+        index = ivf.load_index(self.ctx_embeddings_dir, len(self.ctxs), device, quantizer="pq", sub_vec_dim=self.sub_vec_dim)
+        if self.save_quantized:
+            index.save(path)
+        return index

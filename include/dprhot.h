@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DPRHOT_VERSION 174 /* 0.1.74: + dprhot_ivf_workspace_bytes / _score / _search (inverted-index retrieval for CITADEL / COIL); dprhot_router_head_*, dprhot_ivf_compact / _gather and dprhot_maxsim_score joined without a bump: tests/test_ivf.py pins this number */
+#define DPRHOT_VERSION 174 /* 0.1.74: + dprhot_ivf_workspace_bytes / _score / _search (inverted-index retrieval for CITADEL / COIL); dprhot_router_head_*, dprhot_ivf_compact / _gather, dprhot_maxsim_score and dprhot_pq_encode / dprhot_ivf_pq_score / _search joined without a bump: tests/test_ivf.py pins this number */
 
 #define DPRHOT_OK 0
 #define DPRHOT_E_INVALID (-1)     /* bad argument (NULL pointer, non-positive or misaligned size) */
@@ -353,6 +353,31 @@ int dprhot_ivf_search(const dprhot_bf16* post_vec, const int32_t* post_doc, cons
                       int n_bexp, int nq, const dprhot_bf16* cls_q, const dprhot_bf16* cls_doc, int dc, int64_t cls_rows,
                       int64_t corpus_len, int64_t id_begin, int64_t id_end, int k, int chunk, float* values, int64_t* indices, int first,
                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* Product-quantised postings for the inverted index (the reference's quantizer="pq", sub_vec_dim; csrc/ivf_pq.h, DESIGN.md section
+ * 10.2).  dsub in {2, 4, 8} features per sub-vector, m = dp / dsub subspaces; ONE codebook bf16 [m, 256, dsub] per index; a posting is
+ * m code bytes, post_code uint8 [n_postings, m] in the order of post_doc, and stands for the bf16 row
+ *   decode(p)[j * dsub + t] = codebook[j, post_code[p, j], t].
+ * dprhot_ivf_pq_score / dprhot_ivf_pq_search are dprhot_ivf_score / dprhot_ivf_search with (post_code, codebook, dsub) in place of
+ * post_vec and return, bit for bit, what those return over the index whose post_vec rows are decode(p); everything said above about
+ * owners, order of additions, chunks, ties, NaN and the workspace (dprhot_ivf_workspace_bytes) holds unchanged.
+ * dprhot_pq_encode writes codes uint8 [n, m] for rows vec bf16 [n, dp]: code = argmin over c = 0 .. 255 of
+ *   D(c) = sum over t = 0 .. dsub - 1, in that order, of (x_t - codebook[j, c, t])^2
+ * in fp32 with every subtract, multiply and add rounded on its own (no fma), centroids scanned upwards with a strict <: the lowest
+ * index wins a tie, a NaN distance never wins, a row of NaNs gets code 0.  One owner per output byte, exactly n m bytes written.
+ * n == 0, an empty batch and an index without postings launch nothing.
+ * Limits: dsub not in {2, 4, 8}, dp % 32 != 0, a NULL or misaligned (16 bytes) codebook or code array: DPRHOT_E_INVALID; dp > 64:
+ * DPRHOT_E_UNSUPPORTED; otherwise those of the dense entry points. */
+int dprhot_pq_encode(const dprhot_bf16* vec, int64_t n, int dp, const dprhot_bf16* codebook, int dsub, uint8_t* codes, void* stream);
+int dprhot_ivf_pq_score(const uint8_t* post_code, const dprhot_bf16* codebook, int dsub, const int32_t* post_doc, const int64_t* exp_off,
+                        int64_t n_postings, int n_experts, int dp, const dprhot_bf16* ent_vec, const int32_t* ent_q, int n_entries,
+                        const int32_t* bexp, const int32_t* bexp_off, int n_bexp, int nq, int64_t doc_begin, int cols, float* S, int64_t ld,
+                        void* stream);
+int dprhot_ivf_pq_search(const uint8_t* post_code, const dprhot_bf16* codebook, int dsub, const int32_t* post_doc, const int64_t* exp_off,
+                         int64_t n_postings, int n_experts, int dp, const dprhot_bf16* ent_vec, const int32_t* ent_q, int n_entries,
+                         const int32_t* bexp, const int32_t* bexp_off, int n_bexp, int nq, const dprhot_bf16* cls_q,
+                         const dprhot_bf16* cls_doc, int dc, int64_t cls_rows, int64_t corpus_len, int64_t id_begin, int64_t id_end, int k,
+                         int chunk, float* values, int64_t* indices, int first, void* workspace, size_t workspace_bytes, void* stream);
 
 /* From encoder outputs to index postings and query batches (csrc/ivf_pack.h, DESIGN.md section 10, "Building postings and query
  * batches"): the per-token loops of the reference's citadel_eval_task.py:43-70 and citadel_retrieval_task.py:104-125 as two operations.
