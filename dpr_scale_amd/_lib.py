@@ -124,6 +124,11 @@ SIGNATURES = {
                                    c_void_p, c_void_p, c_int64, c_void_p]),
     "dprhot_ivf_gather": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
                                   c_void_p, c_int64, c_void_p]),
+    "dprhot_colbert_workspace_bytes": (c_int, [c_int, c_int, POINTER(c_size_t)]),
+    "dprhot_colbert_score": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_void_p,
+                                     c_int64, c_void_p]),
+    "dprhot_colbert_search": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int,
+                                      c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "dprhot_router_head_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
     "dprhot_router_head_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -220,6 +225,12 @@ def maxsim_workspace_bytes(Nq: int, LQ: int, KQ: int, Ny: int, has_weights: bool
 def ivf_workspace_bytes(nq: int, n_entries: int, chunk: int, has_cls: bool) -> int:
     out = c_size_t(0)
     check(lib.dprhot_ivf_workspace_bytes(int(nq), int(n_entries), int(chunk), int(bool(has_cls)), ctypes.byref(out)), "dprhot_ivf_workspace_bytes")
+    return out.value
+
+
+def colbert_workspace_bytes(nq: int, chunk: int) -> int:
+    out = c_size_t(0)
+    check(lib.dprhot_colbert_workspace_bytes(int(nq), int(chunk), ctypes.byref(out)), "dprhot_colbert_workspace_bytes")
     return out.value
 
 

@@ -36,6 +36,7 @@
 #include "ivf_pack.h"
 #include "ivf_pq.h"
 #include "router_head.h"
+#include "colbert.h"
 
 using namespace dprhot;
 
@@ -2610,6 +2611,86 @@ int dprhot_ivf_gather(const float* repr, int64_t repr_ld, int64_t n_rows, const 
                   prod_round, entry_round, out, (long long)out_ld};
   if (out_kind == IVFP_BF16) return launch<ivf_gather_kernel<IVFP_BF16>>(dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
   return launch<ivf_gather_kernel<IVFP_FP32>>(dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+}
+
+// ---- exhaustive ColBERT search (csrc/colbert.h) ----
+static int cb_check(const void* tok, const void* doc_blk, int64_t n_blk, int64_t corpus_len, int dp, const void* q_tok, int nq, int LQ,
+                    int pool) {
+  REQUIRE(corpus_len > 0 && corpus_len < (1ll << 31), "corpus_len=%lld out of range (1 .. 2^31 - 1)", (long long)corpus_len);
+  REQUIRE(n_blk >= 0 && n_blk < (1ll << 36), "n_blk=%lld out of range (< 2^36)", (long long)n_blk);
+  REQUIRE(dp > 0 && dp % 32 == 0, "dp=%d must be a positive multiple of 32 (pad with zeros)", dp);
+  REQUIRE(LQ >= 1 && LQ <= DPRHOT_MAXSIM_MAX_LEN, "LQ=%d out of range (1 .. %d)", LQ, DPRHOT_MAXSIM_MAX_LEN);
+  REQUIRE(nq > 0, "bad shape nq=%d", nq);
+  REQUIRE(pool == DPRHOT_POOL_SUM || pool == DPRHOT_POOL_MAX, "unknown pool %d", pool);
+  REQUIRE(doc_blk && q_tok && (n_blk == 0 || tok), "NULL pointer (tok, doc_blk and q_tok are required)");
+  REQUIRE(aligned16(tok) && aligned16(q_tok), "token rows must be 16-byte aligned");
+  if (dp > CB_MAX_DP) return fail(DPRHOT_E_UNSUPPORTED, "dp=%d: the ColBERT search is built for dp <= %d", dp, CB_MAX_DP);
+  return DPRHOT_OK;
+}
+
+int dprhot_colbert_workspace_bytes(int nq, int chunk, size_t* bytes) {
+  REQUIRE(bytes != nullptr, "NULL out pointer");
+  REQUIRE(nq > 0 && chunk > 0 && chunk % 8 == 0, "bad shape nq=%d chunk=%d (chunk: a positive multiple of 8)", nq, chunk);
+  *bytes = align256((size_t)nq * (size_t)chunk * 4);
+  return DPRHOT_OK;
+}
+
+int dprhot_colbert_score(const dprhot_bf16* tok, const int64_t* doc_blk, int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok,
+                         int nq, int LQ, int pool, int64_t doc_begin, int cols, float* S, int64_t ld, void* stream) {
+  if (int rc = cb_check(tok, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool)) return rc;
+  REQUIRE(S != nullptr, "NULL pointer (S)");
+  REQUIRE(cols > 0 && ld >= cols, "bad shape cols=%d ld=%lld", cols, (long long)ld);
+  REQUIRE(doc_begin >= 0 && doc_begin + cols <= corpus_len, "doc ids %lld .. +%d outside the corpus of %lld", (long long)doc_begin, cols,
+          (long long)corpus_len);
+  const int FQ = cdiv(LQ, 16);
+  const int QPW = FQ >= CB_FPP ? 1 : CB_FPP / FQ;  // whole queries per workgroup: QPW * FQ <= max(CB_FPP, FQ) <= CB_FMAX fragments
+  const int rowb = dp * 2 + 16;
+  const int TB = CB_TILE_BYTES / (16 * rowb);
+  REQUIRE(cdiv(nq, QPW) <= 65535, "nq=%d: too many queries for one launch", nq);
+  CbArgs a{reinterpret_cast<const uint16_t*>(tok), reinterpret_cast<const long long*>(doc_blk), (long long)n_blk, dp,
+           reinterpret_cast<const uint16_t*>(q_tok), nq, LQ, pool, (long long)doc_begin, cols, S, (long long)ld, FQ, QPW, TB};
+  const dim3 grid((unsigned)cdiv(cols, CB_RUNP), (unsigned)cdiv(nq, QPW)), block(256);
+  const size_t lds = (size_t)TB * 16 * rowb + (size_t)CB_RUNP * (QPW * FQ * 16 + 1) * sizeof(float);  // the tile, then the term table
+  hipStream_t st = (hipStream_t)stream;
+  switch (dp) {
+    case 32: return launch<cb_score_kernel<1>>(grid, block, lds, st, a);
+    case 64: return launch<cb_score_kernel<2>>(grid, block, lds, st, a);
+    case 96: return launch<cb_score_kernel<3>>(grid, block, lds, st, a);
+    case 128: return launch<cb_score_kernel<4>>(grid, block, lds, st, a);
+    default: return launch<cb_score_kernel<0>>(grid, block, lds, st, a);
+  }
+}
+
+int dprhot_colbert_search(const dprhot_bf16* tok, const int64_t* doc_blk, int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok,
+                          int nq, int LQ, int pool, int64_t id_begin, int64_t id_end, int k, int chunk, float* values, int64_t* indices,
+                          int first, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = cb_check(tok, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool)) return rc;
+  REQUIRE(values && indices, "NULL pointer");
+  REQUIRE(k >= 1 && k <= corpus_len, "topk=%d out of range (1 .. corpus_len=%lld)", k, (long long)corpus_len);
+  REQUIRE(0 <= id_begin && id_begin < id_end && id_end <= corpus_len, "bad doc-id range [%lld, %lld) of %lld", (long long)id_begin,
+          (long long)id_end, (long long)corpus_len);
+  REQUIRE(chunk > 0 && chunk % 8 == 0, "chunk=%d must be a positive multiple of 8", chunk);
+  const bool wide = k > TK_KWIDE;
+  const size_t s_bytes = align256((size_t)nq * (size_t)chunk * 4);
+  const size_t need = s_bytes + (wide ? wsel_ws_bytes(nq, k) : 0);
+  if (workspace == nullptr || workspace_bytes < need)
+    return fail(DPRHOT_E_WORKSPACE, "colbert_search needs %zu workspace bytes (dprhot_colbert_workspace_bytes%s), got %zu", need,
+                wide ? " + dprhot_topk_wide_workspace_bytes" : "", workspace_bytes);
+  REQUIRE(aligned16(workspace), "workspace must be 16-byte aligned");
+  float* S = static_cast<float*>(workspace);
+  void* wide_ws = static_cast<char*>(workspace) + s_bytes;
+  for (int64_t j0 = id_begin; j0 < id_end; j0 += chunk) {
+    const int cols = (int)(id_end - j0 < chunk ? id_end - j0 : chunk);
+    const int ld = (cols + 7) / 8 * 8;  // (<= chunk: chunk is a multiple of 8)
+    if (int rc = dprhot_colbert_score(tok, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool, j0, cols, S, ld, stream)) return rc;
+    const int f = (first && j0 == id_begin) ? 1 : 0;
+    if (wide) {
+      if (int rc = dprhot_topk_update_wide(S, nq, cols, ld, j0, k, values, indices, f, wide_ws, workspace_bytes - s_bytes, stream)) return rc;
+    } else {
+      if (int rc = dprhot_topk_update(S, nq, cols, ld, j0, k, values, indices, f, stream)) return rc;
+    }
+  }
+  return DPRHOT_OK;
 }
 
 }  // extern "C"

@@ -607,6 +607,32 @@ class HipKernels:
                                                    int(id_end), values.shape[1], int(chunk), _ptr(values), _ptr(indices),
                                                    int(bool(first)), _ptr(ws), ws.numel(), self._stream()), "dprhot_ivf_search")
 
+    # -- exhaustive ColBERT search (csrc/colbert.h; dpr_scale_amd/colbert.py owns the index) -------------
+    def colbert_workspace(self, nq, chunk, k, like):
+        n = self._lib.colbert_workspace_bytes(nq, chunk)
+        if k > 4096:  # the HBM-resident selection's state lives behind the score buffer
+            m = ctypes.c_size_t(0)
+            self._lib.check(self.lib.dprhot_topk_wide_workspace_bytes(int(nq), int(k), ctypes.byref(m)), "dprhot_topk_wide_workspace_bytes")
+            n += m.value
+        return torch.empty(n, dtype=torch.uint8, device=like.device)
+
+    def colbert_score(self, index, q, pool, doc_begin, cols, S):
+        """Writes the scores of doc ids doc_begin .. doc_begin + cols into S [nq, >= cols] fp32 (dprhot_colbert_score); q bf16 [nq, LQ, dp]."""
+        self._require_gpu(index.tok, index.doc_blk, q, S)
+        nq, LQ, dp = q.shape
+        self._lib.check(self.lib.dprhot_colbert_score(_ptr(index.tok), _ptr(index.doc_blk), index.n_blk, index.corpus_len, dp, _ptr(q), nq, LQ,
+                                                      int(pool), int(doc_begin), int(cols), _ptr(S), S.stride(0), self._stream()),
+                        "dprhot_colbert_score")
+
+    def colbert_search(self, index, q, pool, id_begin, id_end, values, indices, first, chunk, ws):
+        """Folds doc ids [id_begin, id_end) of a device-resident token index into the running top-k (dprhot_colbert_search)."""
+        self._require_gpu(index.tok, index.doc_blk, q, values, indices, ws)
+        nq, LQ, dp = q.shape
+        self._lib.check(self.lib.dprhot_colbert_search(_ptr(index.tok), _ptr(index.doc_blk), index.n_blk, index.corpus_len, dp, _ptr(q), nq, LQ,
+                                                       int(pool), int(id_begin), int(id_end), values.shape[1], int(chunk), _ptr(values),
+                                                       _ptr(indices), int(bool(first)), _ptr(ws), ws.numel(), self._stream()),
+                        "dprhot_colbert_search")
+
     # -- product-quantised postings (csrc/ivf_pq.h; DESIGN.md section 10.2; dpr_scale_amd/ivf.py owns training and the index) ----
     def pq_encode(self, vec, codebook):
         """codes uint8 [n, m] of the rows vec bf16 [n, dp] under codebook bf16 [m, 256, dsub] (dprhot_pq_encode)."""

@@ -23,7 +23,8 @@ quantizer="pq")` / `IndexBuilder.finish(quantizer="pq")` give an `IVFPQIndex` wh
 or 8 features and one bf16 codebook; its search returns, bit for bit, the dense search over the decoded rows (`IVFPQIndex.decode`).
 
 Not supported (NotImplementedError / out of scope): per-expert codebooks, code widths other than 8 bits, a product-quantised index
-for dp > 64 or on the CPU, `portion` < 1, hnsw, expert parallelism across GPUs, ColBERT.
+for dp > 64 or on the CPU, `portion` < 1, hnsw, expert parallelism across GPUs.  ColBERT (no expert ids to index by) is searched by
+dpr_scale_amd/colbert.py.
 """
 import collections
 import glob

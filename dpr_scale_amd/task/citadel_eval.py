@@ -8,7 +8,7 @@ kept slots are listed and their weighted vectors written by libdprhot.so (dprhot
 dpr_scale_amd.ivf), in the reference's order and with its roundings, and only finished arrays reach the host.  `self.kernels` (default:
 the HIP kernels) is the kernel object ivf.py takes.
 
-Scope: ColBERT (encoders without `expert_ids`) is not covered.  RerankMultiVecRetrieverTask of the same reference file: task/rerank.py.
+Scope: ColBERT (encoders without `expert_ids`) is not covered here: task/colbert_retrieval.py holds its writer and retrieval task.  RerankMultiVecRetrieverTask of the same reference file: task/rerank.py.
 """
 import collections
 import os
@@ -51,7 +51,8 @@ class GenerateMultiVecEmbeddingsTask(MultiVecRetrieverTask):
         contexts_ids = batch["contexts_ids"]
         contexts_repr = {k: v.detach() for k, v in self(contexts_ids).items()}
         if "expert_ids" not in contexts_repr:
-            raise NotImplementedError("ColBERT (an encoder without expert_ids) is not covered by the index writer")
+            raise NotImplementedError("ColBERT (an encoder without expert_ids) is not covered by the index writer: "
+                                      "task/colbert_retrieval.py GenerateColBERTEmbeddingsTask writes its token index")
         if self.builder is None:
             self.builder = ivf.IndexBuilder(None, kernels=self.kernels)
         corpus_ids = torch.tensor([int(c) for c in batch["corpus_ids"]], dtype=torch.int64)
@@ -93,7 +94,8 @@ class GenerateMultiVecQueryEmbeddingsTask(GenerateMultiVecEmbeddingsTask):
         topic_ids = batch["topic_ids"]  # add question topic id
         queries_repr = {k: v.detach() for k, v in self(query_ids).items()}
         if "expert_ids" not in queries_repr:
-            raise NotImplementedError("ColBERT (an encoder without expert_ids) is not covered by the query writer")
+            raise NotImplementedError("ColBERT (an encoder without expert_ids) is not covered by the query writer: "
+                                      "task/colbert_retrieval.py ColBERTRetrievalTask searches its queries as they leave the encoder")
         batch_cls = queries_repr["cls_repr"].cpu() if "cls_repr" in queries_repr else []
         n = len(topic_ids)
         expert, row, weight, vec = (t.cpu() for t in ivf.query_entries(queries_repr, n, kernels=self.kernels))

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DPRHOT_VERSION 174 /* 0.1.74: + dprhot_ivf_workspace_bytes / _score / _search (inverted-index retrieval for CITADEL / COIL); dprhot_router_head_*, dprhot_ivf_compact / _gather, dprhot_maxsim_score and dprhot_pq_encode / dprhot_ivf_pq_score / _search joined without a bump: tests/test_ivf.py pins this number */
+#define DPRHOT_VERSION 174 /* 0.1.74: + dprhot_ivf_workspace_bytes / _score / _search (inverted-index retrieval for CITADEL / COIL); dprhot_router_head_*, dprhot_ivf_compact / _gather, dprhot_maxsim_score and dprhot_pq_encode / dprhot_ivf_pq_score / _search, dprhot_colbert_* joined without a bump: tests/test_ivf.py pins this number */
 
 #define DPRHOT_OK 0
 #define DPRHOT_E_INVALID (-1)     /* bad argument (NULL pointer, non-positive or misaligned size) */
@@ -407,6 +407,31 @@ int dprhot_ivf_compact(const int32_t* expert_ids, const float* weights, const ui
                        float* out_weight, int64_t capacity, void* stream);
 int dprhot_ivf_gather(const float* repr, int64_t repr_ld, int64_t n_rows, const float* weights, const int32_t* slot, const int64_t* perm,
                       int64_t n, int d, int K, int prod_round, int entry_round, int out_kind, void* out, int64_t out_ld, void* stream);
+
+/* Exhaustive MaxSim search of ColBERT (csrc/colbert.h):
+ *   score(n, doc) = POOL over query tokens i < LQ of max(0, max over stored tokens j of doc of <q[n,i], c[doc,j]>),  POOL = sum or max
+ * Index (device): token blocks of 16 rows, tok bf16 [n_blk * 16, dp] (dp = d zero-padded to a multiple of 32, 16-byte aligned rows) and
+ * doc_blk int64 [corpus_len + 1], non-decreasing block offsets: passage doc owns blocks doc_blk[doc] .. doc_blk[doc + 1], the rows behind
+ * its last token are zero (a zero row scores exactly 0, which the clamp makes neutral).  Only attended tokens are stored; a passage
+ * without a token scores 0.  q_tok bf16 [nq, LQ, dp], padded query tokens are zero rows.  The clamp makes the score the training and
+ * rerank score on any padded batch in which every passage has a padded slot.  A NaN product never wins: its token counts as absent.
+ * dprhot_colbert_score WRITES S[n][doc - doc_begin] for doc_begin <= doc < doc_begin + cols <= corpus_len, every cell and nothing else
+ * of S [nq, ld].  One owner per cell, query-token terms pooled in one fixed order, no floating-point atomics: two runs are bit-identical
+ * and a cell does not depend on the chunk, the id range, the other queries or the other passages.  Offsets are clamped to [0, n_blk]:
+ * nothing is read behind row n_blk * 16 - 1.
+ * dprhot_colbert_search runs doc ids [id_begin, id_end) in chunks of `chunk` (a multiple of 8): the chunk's scores into the workspace,
+ * then the streaming top-k (dprhot_topk_update; dprhot_topk_update_wide for k > 4096) with col_offset = the chunk's first id.  values /
+ * indices / first as in dprhot_search: disjoint id ranges may be folded into one result; score descending, ties to the lower doc id.
+ * workspace: dprhot_colbert_workspace_bytes(nq, chunk) (+ dprhot_topk_wide_workspace_bytes(nq, k) behind it when k > 4096);
+ * DPRHOT_E_WORKSPACE when smaller.
+ * Limits (DPRHOT_E_INVALID): 1 <= LQ <= DPRHOT_MAXSIM_MAX_LEN, dp % 32 == 0, corpus_len < 2^31, n_blk < 2^36, 1 <= k <= corpus_len,
+ * chunk % 8 == 0, pool one of DPRHOT_POOL_SUM / DPRHOT_POOL_MAX; dp > 768: DPRHOT_E_UNSUPPORTED.  No limit on a passage's length. */
+int dprhot_colbert_workspace_bytes(int nq, int chunk, size_t* bytes);
+int dprhot_colbert_score(const dprhot_bf16* tok, const int64_t* doc_blk, int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok,
+                         int nq, int LQ, int pool, int64_t doc_begin, int cols, float* S, int64_t ld, void* stream);
+int dprhot_colbert_search(const dprhot_bf16* tok, const int64_t* doc_blk, int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok,
+                          int nq, int LQ, int pool, int64_t id_begin, int64_t id_end, int k, int chunk, float* values, int64_t* indices,
+                          int first, void* workspace, size_t workspace_bytes, void* stream);
 
 /* The CITADEL / SPLADE encoder head behind the MLM logits (dpr_scale/models/citadel_models/citadel_model.py:46-82, splade_model.py:26-32;
  * csrc/router_head.h), forward and backward without a [B, T, V] temporary.  logits [B, T1, V] of `dtype` (0 bf16,
