@@ -21,7 +21,6 @@ top-k run in libdprhot.so (dprhot_colbert_search); there is no torch fallback.  
 Not supported (out of scope): compressed or residual token vectors, centroid pruning (PLAID-style candidate generation), an index
 across several GPUs, a CPU index.
 """
-import collections
 import glob
 import os
 import pickle
@@ -29,18 +28,12 @@ import time
 
 import torch
 
+from ._chunked import ChunkedIndex
+
 _BF16 = torch.bfloat16
 _POOL = {"sum": 0, "max": 1}  # DPRHOT_POOL_SUM / DPRHOT_POOL_MAX
 BLOCK = 16                    # token rows per block: one MFMA fragment, one passage
 MAX_QUERY_LEN = 512           # DPRHOT_MAXSIM_MAX_LEN
-
-
-def _default_kernels(kernels):
-    if kernels is None:
-        from . import hotpath
-
-        kernels = hotpath.default_kernels()
-    return kernels
 
 
 def _bf16_padded(x, dp):
@@ -53,7 +46,7 @@ def _bf16_padded(x, dp):
     return out
 
 
-class ColBERTIndex:
+class ColBERTIndex(ChunkedIndex):
     """Device-resident token index of a ColBERT corpus; `search` is the exhaustive MaxSim top-k."""
 
     def __init__(self, doc_ids, lengths, rows, corpus_len, device, chunk=None, kernels=None):
@@ -112,25 +105,12 @@ class ColBERTIndex:
         self.tok, self.doc_blk = tok, doc_blk
         self.corpus_len, self.d, self.dp = corpus_len, d, int(tok.shape[1])
         self.n_blk = int(tok.shape[0]) // BLOCK
-        self.chunk = None if chunk is None else int(chunk)
-        self.kn = kernels
-        self.latency = collections.defaultdict(float)
-        self.latency["encode_time"] += 0.0  # test_epoch_end of the retrieval task pops this key
+        self._init_search(chunk, kernels)
 
     @property
     def nbytes(self):
         """Bytes of device memory the index holds (token rows and block offsets)."""
         return sum(t.numel() * t.element_size() for t in (self.tok, self.doc_blk))
-
-    def _kernels(self):
-        self.kn = _default_kernels(self.kn)
-        return self.kn
-
-    def default_chunk(self, nq):
-        """Doc ids per pass: the chunk's score buffer is nq x chunk fp32 (at most 8 MiB by default, at least 1024 ids)."""
-        c = self.chunk if self.chunk is not None else max(1024, min(262144, (1 << 21) // max(nq, 1)))
-        c = min(c, (self.corpus_len + 7) // 8 * 8)
-        return max(8, c // 8 * 8)
 
     def _queries(self, q):
         if isinstance(q, dict):
@@ -154,24 +134,16 @@ class ColBERTIndex:
         """(scores fp32 [nq, topk], ids int64 [nq, topk]) on the index's device, score descending with ties to the lower doc id.  q:
         [nq, LQ, d] or a repr dict with `expert_repr`.  `id_ranges`: disjoint (begin, end) doc-id ranges folded into one result."""
         pool, topk = self._pool(query_pool), int(topk)
-        if not 1 <= topk <= self.corpus_len:
-            raise ValueError(f"topk={topk} out of range (1 .. corpus_len={self.corpus_len})")
         tic = time.perf_counter()
         qb = self._queries(q)
         self.latency["encode_time"] += time.perf_counter() - tic
         tic = time.perf_counter()
         kn = self._kernels()
         nq = int(qb.shape[0])
-        chunk = self.default_chunk(nq) if chunk is None else int(chunk)
-        values = torch.empty((nq, topk), dtype=torch.float32, device=self.device)
-        indices = torch.empty((nq, topk), dtype=torch.int64, device=self.device)
-        ws = kn.colbert_workspace(nq, chunk, topk, self.doc_blk)
-        first = True
-        for b, e in (id_ranges if id_ranges is not None else [(0, self.corpus_len)]):
-            kn.colbert_search(self, qb, pool, int(b), int(e), values, indices, first, chunk, ws)
-            first = False
+        out = self._fold(nq, topk, id_ranges, chunk, lambda chunk: kn.colbert_workspace(nq, chunk, topk, self.doc_blk),
+                         lambda *tail: kn.colbert_search(self, qb, pool, *tail))
         self.latency["search_time"] += time.perf_counter() - tic
-        return values, indices
+        return out
 
     def score(self, q, doc_begin=0, cols=None, query_pool="sum"):
         """The score matrix fp32 [nq, cols] of doc ids doc_begin .. doc_begin + cols (default: to the end of the corpus)."""

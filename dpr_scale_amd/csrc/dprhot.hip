@@ -2385,7 +2385,61 @@ int dprhot_router_head_bwd(const void* logits, int dtype, int B, int T1, int V, 
 
 // ---- inverted-index retrieval (csrc/ivf.h) ----
 constexpr int IVF_MAX_ENTRIES_PER_QUERY = 4096;
-static size_t ivf_ws_bytes(int nq, int chunk) { return align256((size_t)nq * (size_t)chunk * 4); }
+
+// one chunk's score buffer, nq x chunk fp32: the workspace of every chunked search up to k = TK_KWIDE
+static size_t chunk_ws_bytes(int nq, int chunk) { return align256((size_t)nq * (size_t)chunk * 4); }
+
+// the output window of the *_score entry points: S [nq, ld] takes doc ids doc_begin .. doc_begin + cols, which end at or below `limit`
+// (corpus_len where the index knows it, 2^31 where it does not)
+static int check_score_window(const float* S, int cols, int64_t ld, int64_t doc_begin, int64_t limit) {
+  REQUIRE(S != nullptr, "NULL pointer (S)");
+  REQUIRE(cols > 0 && ld >= cols, "bad shape cols=%d ld=%lld", cols, (long long)ld);
+  if (limit == (1ll << 31)) {
+    REQUIRE(doc_begin >= 0 && doc_begin + cols < limit, "doc ids %lld .. +%d must stay below 2^31", (long long)doc_begin, cols);
+  } else {
+    REQUIRE(doc_begin >= 0 && doc_begin + cols <= limit, "doc ids %lld .. +%d outside the corpus of %lld", (long long)doc_begin, cols,
+            (long long)limit);
+  }
+  return DPRHOT_OK;
+}
+
+extern "C++" {
+// The one chunked top-k search ("The chunk driver"): walks the doc ids [id_begin, id_end) in chunks, has
+// fill(j0, cols, S, ld) write the scores of doc ids j0 .. j0 + cols into S [nq, ld] and folds them into the running top-k, with the
+// HBM-resident selection above k = TK_KWIDE.  The workspace is one chunk's scores, then the wide selection's state.  `who` names the
+// caller in the workspace error.
+template <class Fill>
+static int topk_search_chunks(const char* who, Fill fill, int nq, int64_t corpus_len, int64_t id_begin, int64_t id_end, int k, int chunk,
+                              float* values, int64_t* indices, int first, void* workspace, size_t workspace_bytes, void* stream) {
+  REQUIRE(values && indices, "NULL pointer");
+  REQUIRE(corpus_len > 0 && corpus_len < (1ll << 31), "corpus_len=%lld out of range (1 .. 2^31 - 1)", (long long)corpus_len);
+  REQUIRE(k >= 1 && k <= corpus_len, "topk=%d out of range (1 .. corpus_len=%lld)", k, (long long)corpus_len);
+  REQUIRE(0 <= id_begin && id_begin < id_end && id_end <= corpus_len, "bad doc-id range [%lld, %lld) of %lld", (long long)id_begin,
+          (long long)id_end, (long long)corpus_len);
+  REQUIRE(chunk > 0 && chunk % 8 == 0, "chunk=%d must be a positive multiple of 8", chunk);
+  const bool wide = k > TK_KWIDE;
+  const size_t s_bytes = chunk_ws_bytes(nq, chunk);
+  const size_t need = s_bytes + (wide ? wsel_ws_bytes(nq, k) : 0);
+  if (workspace == nullptr || workspace_bytes < need)
+    return fail(DPRHOT_E_WORKSPACE, "%s_search needs %zu workspace bytes (dprhot_%s_workspace_bytes%s), got %zu", who, need, who,
+                wide ? " + dprhot_topk_wide_workspace_bytes" : "", workspace_bytes);
+  REQUIRE(aligned16(workspace), "workspace must be 16-byte aligned");
+  float* S = static_cast<float*>(workspace);
+  void* wide_ws = static_cast<char*>(workspace) + s_bytes;
+  for (int64_t j0 = id_begin; j0 < id_end; j0 += chunk) {
+    const int cols = (int)(id_end - j0 < chunk ? id_end - j0 : chunk);
+    const int ld = (cols + 7) / 8 * 8;  // (<= chunk: chunk is a multiple of 8)
+    if (int rc = fill(j0, cols, S, ld)) return rc;
+    const int f = (first && j0 == id_begin) ? 1 : 0;
+    if (wide) {
+      if (int rc = dprhot_topk_update_wide(S, nq, cols, ld, j0, k, values, indices, f, wide_ws, workspace_bytes - s_bytes, stream)) return rc;
+    } else {
+      if (int rc = dprhot_topk_update(S, nq, cols, ld, j0, k, values, indices, f, stream)) return rc;
+    }
+  }
+  return DPRHOT_OK;
+}
+}  // extern "C++"
 
 static int ivf_check_batch(int nq, int n_entries, int n_bexp, const void* ent_vec, const void* ent_q, const void* bexp, const void* bexp_off) {
   REQUIRE(nq > 0, "bad shape nq=%d", nq);
@@ -2398,12 +2452,29 @@ static int ivf_check_batch(int nq, int n_entries, int n_bexp, const void* ent_ve
   return DPRHOT_OK;
 }
 
-static int ivf_check_index(const void* post_vec, const void* post_doc, const void* exp_off, int64_t n_postings, int n_experts, int dp) {
+// the postings' frame, shared by the dense and the product-quantised index: `rows` is post_vec or post_code
+static int ivf_check_postings(const void* rows, const void* post_doc, const void* exp_off, int64_t n_postings, int n_experts) {
   REQUIRE(n_postings >= 0 && n_postings < (1ll << 40), "n_postings=%lld out of range (< 2^40)", (long long)n_postings);
   REQUIRE(n_experts > 0 && exp_off, "bad index: n_experts=%d", n_experts);
+  REQUIRE(n_postings == 0 || (rows && post_doc), "NULL pointer (postings)");
+  return DPRHOT_OK;
+}
+
+static int ivf_check_index(const void* post_vec, const void* post_doc, const void* exp_off, int64_t n_postings, int n_experts, int dp) {
+  if (int rc = ivf_check_postings(post_vec, post_doc, exp_off, n_postings, n_experts)) return rc;
   REQUIRE(dp > 0 && dp % 32 == 0, "dp=%d must be a positive multiple of 32 (pad with zeros)", dp);
-  REQUIRE(n_postings == 0 || (post_vec && post_doc), "NULL pointer (postings)");
   REQUIRE(n_postings == 0 || aligned16(post_vec), "posting vectors must be 16-byte aligned");
+  return DPRHOT_OK;
+}
+
+// the CLS part of an IVF search: both sides or neither, cls_doc with its zero rows behind the last doc id searched
+static int ivf_check_cls(const dprhot_bf16* cls_q, const dprhot_bf16* cls_doc, int dc, int64_t cls_rows, int64_t id_end) {
+  if (cls_q == nullptr && cls_doc == nullptr) return DPRHOT_OK;
+  REQUIRE(cls_q && cls_doc, "CLS vectors of one side only");
+  REQUIRE(dc > 0 && dc % 8 == 0, "dc=%d must be a positive multiple of 8 (pad with zeros)", dc);
+  REQUIRE(cls_rows >= 7 && cls_rows - 7 >= id_end, "cls_doc has %lld rows; %lld needed (corpus_len + 7, zero rows behind the corpus)",
+          (long long)cls_rows, (long long)((unsigned long long)id_end + 7));
+  REQUIRE(aligned16(cls_q) && aligned16(cls_doc), "CLS vectors must be 16-byte aligned");
   return DPRHOT_OK;
 }
 
@@ -2413,7 +2484,7 @@ int dprhot_ivf_workspace_bytes(int nq, int n_entries, int chunk, int has_cls, si
   REQUIRE(n_entries >= 0 && (long long)n_entries <= (long long)nq * IVF_MAX_ENTRIES_PER_QUERY, "n_entries=%d: at most %d entries per query",
           n_entries, IVF_MAX_ENTRIES_PER_QUERY);
   (void)has_cls;  // the CLS scores are written straight into the chunk's score buffer
-  *bytes = ivf_ws_bytes(nq, chunk);
+  *bytes = chunk_ws_bytes(nq, chunk);
   return DPRHOT_OK;
 }
 
@@ -2422,9 +2493,7 @@ int dprhot_ivf_score(const dprhot_bf16* post_vec, const int32_t* post_doc, const
                      int n_bexp, int nq, int64_t doc_begin, int cols, float* S, int64_t ld, void* stream) {
   if (int rc = ivf_check_index(post_vec, post_doc, exp_off, n_postings, n_experts, dp)) return rc;
   if (int rc = ivf_check_batch(nq, n_entries, n_bexp, ent_vec, ent_q, bexp, bexp_off)) return rc;
-  REQUIRE(S != nullptr, "NULL pointer (S)");
-  REQUIRE(cols > 0 && ld >= cols, "bad shape cols=%d ld=%lld", cols, (long long)ld);
-  REQUIRE(doc_begin >= 0 && doc_begin + cols < (1ll << 31), "doc ids %lld .. +%d must stay below 2^31", (long long)doc_begin, cols);
+  if (int rc = check_score_window(S, cols, ld, doc_begin, 1ll << 31)) return rc;
   if (n_entries == 0 || n_postings == 0) return DPRHOT_OK;
   IvfArgs a{reinterpret_cast<const uint16_t*>(post_vec), post_doc, reinterpret_cast<const long long*>(exp_off), n_experts, dp,
             reinterpret_cast<const uint16_t*>(ent_vec), ent_q, bexp, bexp_off, n_bexp, nq, (long long)doc_begin, cols, S, (long long)ld};
@@ -2433,53 +2502,23 @@ int dprhot_ivf_score(const dprhot_bf16* post_vec, const int32_t* post_doc, const
 }
 
 extern "C++" {
-// the chunk loop of dprhot_ivf_search and dprhot_ivf_pq_search behind their index and batch checks: score(j0, cols, S, ld) adds the
-// expert part of doc ids j0 .. j0 + cols into S
+// dprhot_ivf_search and dprhot_ivf_pq_search behind their index and batch checks: the chunk driver over a fill that starts S from the
+// CLS scores of the chunk's doc ids (zeros without CLS vectors) and has score(j0, cols, S, ld) add the expert part
 template <class Score>
-static int ivf_search_chunks(Score score, int nq, const dprhot_bf16* cls_q, const dprhot_bf16* cls_doc, int dc, int64_t cls_rows,
-                             int64_t corpus_len, int64_t id_begin, int64_t id_end, int k, int chunk, float* values, int64_t* indices,
-                             int first, void* workspace, size_t workspace_bytes, void* stream) {
-  REQUIRE(values && indices, "NULL pointer");
-  REQUIRE(corpus_len > 0 && corpus_len < (1ll << 31), "corpus_len=%lld out of range (1 .. 2^31 - 1)", (long long)corpus_len);
-  REQUIRE(k >= 1 && k <= corpus_len, "topk=%d out of range (1 .. corpus_len=%lld)", k, (long long)corpus_len);
-  REQUIRE(0 <= id_begin && id_begin < id_end && id_end <= corpus_len, "bad doc-id range [%lld, %lld) of %lld", (long long)id_begin,
-          (long long)id_end, (long long)corpus_len);
-  REQUIRE(chunk > 0 && chunk % 8 == 0, "chunk=%d must be a positive multiple of 8", chunk);
-  const bool has_cls = cls_q != nullptr || cls_doc != nullptr;
-  if (has_cls) {
-    REQUIRE(cls_q && cls_doc, "CLS vectors of one side only");
-    REQUIRE(dc > 0 && dc % 8 == 0, "dc=%d must be a positive multiple of 8 (pad with zeros)", dc);
-    REQUIRE(cls_rows >= id_end + 7, "cls_doc has %lld rows; %lld needed (corpus_len + 7, zero rows behind the corpus)", (long long)cls_rows,
-            (long long)(id_end + 7));
-    REQUIRE(aligned16(cls_q) && aligned16(cls_doc), "CLS vectors must be 16-byte aligned");
-  }
-  const bool wide = k > TK_KWIDE;
-  const size_t s_bytes = ivf_ws_bytes(nq, chunk);
-  const size_t need = s_bytes + (wide ? wsel_ws_bytes(nq, k) : 0);
-  if (workspace == nullptr || workspace_bytes < need)
-    return fail(DPRHOT_E_WORKSPACE, "ivf_search needs %zu workspace bytes (dprhot_ivf_workspace_bytes%s), got %zu", need,
-                wide ? " + dprhot_topk_wide_workspace_bytes" : "", workspace_bytes);
-  REQUIRE(aligned16(workspace), "workspace must be 16-byte aligned");
-  hipStream_t st = (hipStream_t)stream;
-  float* S = static_cast<float*>(workspace);
-  void* wide_ws = static_cast<char*>(workspace) + s_bytes;
-  for (int64_t j0 = id_begin; j0 < id_end; j0 += chunk) {
-    const int cols = (int)(id_end - j0 < chunk ? id_end - j0 : chunk);
-    const int ld = (cols + 7) / 8 * 8;  // (<= chunk: chunk is a multiple of 8)
-    if (has_cls) {
+static int ivf_search_with(Score score, int nq, const dprhot_bf16* cls_q, const dprhot_bf16* cls_doc, int dc, int64_t cls_rows,
+                           int64_t corpus_len, int64_t id_begin, int64_t id_end, int k, int chunk, float* values, int64_t* indices,
+                           int first, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = ivf_check_cls(cls_q, cls_doc, dc, cls_rows, id_end)) return rc;
+  auto fill = [&](int64_t j0, int cols, float* S, int ld) {
+    if (cls_q) {
       if (int rc = dprhot_sim_fwd(cls_q, nq, cls_doc + (size_t)j0 * dc, ld, dc, nullptr, 1.0f, S, stream)) return rc;
     } else {
-      HIP_TRY(hipMemsetAsync(S, 0, (size_t)nq * ld * sizeof(float), st));
+      HIP_TRY(hipMemsetAsync(S, 0, (size_t)nq * ld * sizeof(float), (hipStream_t)stream));
     }
-    if (int rc = score(j0, cols, S, ld)) return rc;
-    const int f = (first && j0 == id_begin) ? 1 : 0;
-    if (wide) {
-      if (int rc = dprhot_topk_update_wide(S, nq, cols, ld, j0, k, values, indices, f, wide_ws, workspace_bytes - s_bytes, stream)) return rc;
-    } else {
-      if (int rc = dprhot_topk_update(S, nq, cols, ld, j0, k, values, indices, f, stream)) return rc;
-    }
-  }
-  return DPRHOT_OK;
+    return score(j0, cols, S, ld);
+  };
+  return topk_search_chunks("ivf", fill, nq, corpus_len, id_begin, id_end, k, chunk, values, indices, first, workspace, workspace_bytes,
+                            stream);
 }
 }  // extern "C++"
 
@@ -2494,8 +2533,8 @@ int dprhot_ivf_search(const dprhot_bf16* post_vec, const int32_t* post_doc, cons
     return dprhot_ivf_score(post_vec, post_doc, exp_off, n_postings, n_experts, dp, ent_vec, ent_q, n_entries, bexp, bexp_off, n_bexp, nq, j0,
                             cols, S, ld, stream);
   };
-  return ivf_search_chunks(score, nq, cls_q, cls_doc, dc, cls_rows, corpus_len, id_begin, id_end, k, chunk, values, indices, first, workspace,
-                           workspace_bytes, stream);
+  return ivf_search_with(score, nq, cls_q, cls_doc, dc, cls_rows, corpus_len, id_begin, id_end, k, chunk, values, indices, first, workspace,
+                         workspace_bytes, stream);
 }
 
 // ---- product-quantised postings (csrc/ivf_pq.h) ----
@@ -2508,10 +2547,8 @@ static int pq_check_shape(int dp, int dsub) {
 
 static int ivf_pq_check_index(const void* post_code, const void* codebook, int dsub, const void* post_doc, const void* exp_off,
                               int64_t n_postings, int n_experts, int dp) {
-  REQUIRE(n_postings >= 0 && n_postings < (1ll << 40), "n_postings=%lld out of range (< 2^40)", (long long)n_postings);
-  REQUIRE(n_experts > 0 && exp_off, "bad index: n_experts=%d", n_experts);
+  if (int rc = ivf_check_postings(post_code, post_doc, exp_off, n_postings, n_experts)) return rc;
   REQUIRE(codebook != nullptr, "NULL pointer (codebook)");
-  REQUIRE(n_postings == 0 || (post_code && post_doc), "NULL pointer (postings)");
   if (int rc = pq_check_shape(dp, dsub)) return rc;
   REQUIRE(aligned16(codebook) && (n_postings == 0 || aligned16(post_code)), "codes and codebook must be 16-byte aligned");
   return DPRHOT_OK;
@@ -2546,9 +2583,7 @@ int dprhot_ivf_pq_score(const uint8_t* post_code, const dprhot_bf16* codebook, i
                         void* stream) {
   if (int rc = ivf_pq_check_index(post_code, codebook, dsub, post_doc, exp_off, n_postings, n_experts, dp)) return rc;
   if (int rc = ivf_check_batch(nq, n_entries, n_bexp, ent_vec, ent_q, bexp, bexp_off)) return rc;
-  REQUIRE(S != nullptr, "NULL pointer (S)");
-  REQUIRE(cols > 0 && ld >= cols, "bad shape cols=%d ld=%lld", cols, (long long)ld);
-  REQUIRE(doc_begin >= 0 && doc_begin + cols < (1ll << 31), "doc ids %lld .. +%d must stay below 2^31", (long long)doc_begin, cols);
+  if (int rc = check_score_window(S, cols, ld, doc_begin, 1ll << 31)) return rc;
   if (n_entries == 0 || n_postings == 0) return DPRHOT_OK;
   IvfPqArgs a{post_code, reinterpret_cast<const uint16_t*>(codebook), post_doc, reinterpret_cast<const long long*>(exp_off), n_experts,
               reinterpret_cast<const uint16_t*>(ent_vec), ent_q, bexp, bexp_off, n_bexp, nq, (long long)doc_begin, cols, S, (long long)ld};
@@ -2570,8 +2605,8 @@ int dprhot_ivf_pq_search(const uint8_t* post_code, const dprhot_bf16* codebook, 
     return dprhot_ivf_pq_score(post_code, codebook, dsub, post_doc, exp_off, n_postings, n_experts, dp, ent_vec, ent_q, n_entries, bexp,
                                bexp_off, n_bexp, nq, j0, cols, S, ld, stream);
   };
-  return ivf_search_chunks(score, nq, cls_q, cls_doc, dc, cls_rows, corpus_len, id_begin, id_end, k, chunk, values, indices, first, workspace,
-                           workspace_bytes, stream);
+  return ivf_search_with(score, nq, cls_q, cls_doc, dc, cls_rows, corpus_len, id_begin, id_end, k, chunk, values, indices, first, workspace,
+                         workspace_bytes, stream);
 }
 
 // ---- postings and query batches from encoder outputs (csrc/ivf_pack.h) ----
@@ -2631,17 +2666,14 @@ static int cb_check(const void* tok, const void* doc_blk, int64_t n_blk, int64_t
 int dprhot_colbert_workspace_bytes(int nq, int chunk, size_t* bytes) {
   REQUIRE(bytes != nullptr, "NULL out pointer");
   REQUIRE(nq > 0 && chunk > 0 && chunk % 8 == 0, "bad shape nq=%d chunk=%d (chunk: a positive multiple of 8)", nq, chunk);
-  *bytes = align256((size_t)nq * (size_t)chunk * 4);
+  *bytes = chunk_ws_bytes(nq, chunk);
   return DPRHOT_OK;
 }
 
 int dprhot_colbert_score(const dprhot_bf16* tok, const int64_t* doc_blk, int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok,
                          int nq, int LQ, int pool, int64_t doc_begin, int cols, float* S, int64_t ld, void* stream) {
   if (int rc = cb_check(tok, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool)) return rc;
-  REQUIRE(S != nullptr, "NULL pointer (S)");
-  REQUIRE(cols > 0 && ld >= cols, "bad shape cols=%d ld=%lld", cols, (long long)ld);
-  REQUIRE(doc_begin >= 0 && doc_begin + cols <= corpus_len, "doc ids %lld .. +%d outside the corpus of %lld", (long long)doc_begin, cols,
-          (long long)corpus_len);
+  if (int rc = check_score_window(S, cols, ld, doc_begin, corpus_len)) return rc;
   const int FQ = cdiv(LQ, 16);
   const int QPW = FQ >= CB_FPP ? 1 : CB_FPP / FQ;  // whole queries per workgroup: QPW * FQ <= max(CB_FPP, FQ) <= CB_FMAX fragments
   const int rowb = dp * 2 + 16;
@@ -2665,32 +2697,11 @@ int dprhot_colbert_search(const dprhot_bf16* tok, const int64_t* doc_blk, int64_
                           int nq, int LQ, int pool, int64_t id_begin, int64_t id_end, int k, int chunk, float* values, int64_t* indices,
                           int first, void* workspace, size_t workspace_bytes, void* stream) {
   if (int rc = cb_check(tok, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool)) return rc;
-  REQUIRE(values && indices, "NULL pointer");
-  REQUIRE(k >= 1 && k <= corpus_len, "topk=%d out of range (1 .. corpus_len=%lld)", k, (long long)corpus_len);
-  REQUIRE(0 <= id_begin && id_begin < id_end && id_end <= corpus_len, "bad doc-id range [%lld, %lld) of %lld", (long long)id_begin,
-          (long long)id_end, (long long)corpus_len);
-  REQUIRE(chunk > 0 && chunk % 8 == 0, "chunk=%d must be a positive multiple of 8", chunk);
-  const bool wide = k > TK_KWIDE;
-  const size_t s_bytes = align256((size_t)nq * (size_t)chunk * 4);
-  const size_t need = s_bytes + (wide ? wsel_ws_bytes(nq, k) : 0);
-  if (workspace == nullptr || workspace_bytes < need)
-    return fail(DPRHOT_E_WORKSPACE, "colbert_search needs %zu workspace bytes (dprhot_colbert_workspace_bytes%s), got %zu", need,
-                wide ? " + dprhot_topk_wide_workspace_bytes" : "", workspace_bytes);
-  REQUIRE(aligned16(workspace), "workspace must be 16-byte aligned");
-  float* S = static_cast<float*>(workspace);
-  void* wide_ws = static_cast<char*>(workspace) + s_bytes;
-  for (int64_t j0 = id_begin; j0 < id_end; j0 += chunk) {
-    const int cols = (int)(id_end - j0 < chunk ? id_end - j0 : chunk);
-    const int ld = (cols + 7) / 8 * 8;  // (<= chunk: chunk is a multiple of 8)
-    if (int rc = dprhot_colbert_score(tok, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool, j0, cols, S, ld, stream)) return rc;
-    const int f = (first && j0 == id_begin) ? 1 : 0;
-    if (wide) {
-      if (int rc = dprhot_topk_update_wide(S, nq, cols, ld, j0, k, values, indices, f, wide_ws, workspace_bytes - s_bytes, stream)) return rc;
-    } else {
-      if (int rc = dprhot_topk_update(S, nq, cols, ld, j0, k, values, indices, f, stream)) return rc;
-    }
-  }
-  return DPRHOT_OK;
+  auto fill = [&](int64_t j0, int cols, float* S, int ld) {
+    return dprhot_colbert_score(tok, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool, j0, cols, S, ld, stream);
+  };
+  return topk_search_chunks("colbert", fill, nq, corpus_len, id_begin, id_end, k, chunk, values, indices, first, workspace, workspace_bytes,
+                            stream);
 }
 
 }  // extern "C"

@@ -80,6 +80,7 @@ def _ptr(t):
 
 _RH_DTYPE = {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}  # the dtype codes of dprhot_router_head_*
 _IVF_ROUND = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}  # DPRHOT_IVF_FP32 / _BF16 / _FP16 of dprhot_ivf_gather
+TOPK_KWIDE = 4096  # largest k of the streaming top-k kernel (dprhot_topk_update: 8192 sort slots in 96 KB of LDS); beyond: the HBM-resident selection
 
 
 class HipKernels:
@@ -563,10 +564,24 @@ class HipKernels:
         """The error words of the last dprhot_topk_update_wide call on `ws` (one int32 per row; host sync when inspected)."""
         return ws[: rows * 32].view(torch.int32).view(rows, 8)[:, 5]
 
-    def topk_wide_workspace(self, rows, k, like):
+    def _topk_wide_bytes(self, rows, k):
         n = ctypes.c_size_t(0)
         self._lib.check(self.lib.dprhot_topk_wide_workspace_bytes(int(rows), int(k), ctypes.byref(n)), "dprhot_topk_wide_workspace_bytes")
-        return torch.empty(n.value, dtype=torch.uint8, device=like.device)
+        return n.value
+
+    def topk_wide_workspace(self, rows, k, like):
+        return torch.empty(self._topk_wide_bytes(rows, k), dtype=torch.uint8, device=like.device)
+
+    def _chunk_workspace(self, score_bytes, nq, k, like):
+        """The workspace of a chunked search (the chunk driver of csrc/dprhot.hip): one chunk's score buffer, then the HBM-resident
+        selection's state when k is beyond the streaming kernel's."""
+        wide = self._topk_wide_bytes(nq, k) if k > TOPK_KWIDE else 0
+        return torch.empty(score_bytes + wide, dtype=torch.uint8, device=like.device)
+
+    def _topk_tail(self, id_begin, id_end, values, indices, first, chunk, ws):
+        """id_begin, id_end, k, chunk, values, indices, first, ws, len, stream: the arguments every chunked search ends with."""
+        return (int(id_begin), int(id_end), values.shape[1], int(chunk), _ptr(values), _ptr(indices), int(bool(first)), _ptr(ws), ws.numel(),
+                self._stream())
 
     def search_workspace(self, nq, chunk, like):
         return torch.empty(self._lib.search_workspace_bytes(nq, chunk), dtype=torch.uint8, device=like.device)
@@ -581,40 +596,36 @@ class HipKernels:
 
     # -- inverted-index retrieval (csrc/ivf.h; dpr_scale_amd/ivf.py owns the packing) ---------------------
     def ivf_workspace(self, nq, n_entries, chunk, has_cls, k, like):
-        n = self._lib.ivf_workspace_bytes(nq, n_entries, chunk, has_cls)
-        if k > 4096:  # the HBM-resident selection's state lives behind the score buffer
-            m = ctypes.c_size_t(0)
-            self._lib.check(self.lib.dprhot_topk_wide_workspace_bytes(int(nq), int(k), ctypes.byref(m)), "dprhot_topk_wide_workspace_bytes")
-            n += m.value
-        return torch.empty(n, dtype=torch.uint8, device=like.device)
+        return self._chunk_workspace(self._lib.ivf_workspace_bytes(nq, n_entries, chunk, has_cls), nq, k, like)
+
+    def _ivf_batch(self, qb):
+        """ent_vec, ent_q, n_entries, bexp, bexp_off, n_bexp, nq: the query-batch arguments of the four IVF entry points."""
+        self._require_gpu(qb.ent_vec, qb.ent_q, qb.bexp, qb.boff)
+        return _ptr(qb.ent_vec), _ptr(qb.ent_q), qb.n_entries, _ptr(qb.bexp), _ptr(qb.boff), int(qb.bexp.shape[0]), qb.nq
+
+    @staticmethod
+    def _ivf_cls(index, qb):
+        """cls_q, cls_doc, dc, cls_rows, corpus_len: what the two IVF searches pass between the query batch and the top-k tail."""
+        return _ptr(qb.cls), _ptr(index.cls), index.dc, 0 if index.cls is None else index.cls.shape[0], index.corpus_len
 
     def ivf_score(self, index, qb, doc_begin, cols, S):
         """Adds the expert part of doc ids doc_begin .. doc_begin + cols into S [nq, >= cols] fp32 (dprhot_ivf_score)."""
-        self._require_gpu(index.post_vec, index.post_doc, index.exp_off, qb.ent_vec, qb.ent_q, qb.bexp, qb.boff, S)
+        self._require_gpu(index.post_vec, index.post_doc, index.exp_off, S)
         self._lib.check(self.lib.dprhot_ivf_score(_ptr(index.post_vec), _ptr(index.post_doc), _ptr(index.exp_off), index.n_postings,
-                                                  index.n_experts, index.dp, _ptr(qb.ent_vec), _ptr(qb.ent_q), qb.n_entries, _ptr(qb.bexp),
-                                                  _ptr(qb.boff), int(qb.bexp.shape[0]), qb.nq, int(doc_begin), int(cols), _ptr(S),
+                                                  index.n_experts, index.dp, *self._ivf_batch(qb), int(doc_begin), int(cols), _ptr(S),
                                                   S.stride(0), self._stream()), "dprhot_ivf_score")
 
     def ivf_search(self, index, qb, id_begin, id_end, values, indices, first, chunk, ws):
         """Folds doc ids [id_begin, id_end) of a device-resident index into the running top-k (dprhot_ivf_search)."""
-        self._require_gpu(index.post_vec, index.post_doc, index.exp_off, index.cls, qb.ent_vec, qb.ent_q, qb.bexp, qb.boff, qb.cls, values,
-                          indices, ws)
+        self._require_gpu(index.post_vec, index.post_doc, index.exp_off, index.cls, qb.cls, values, indices, ws)
         self._lib.check(self.lib.dprhot_ivf_search(_ptr(index.post_vec), _ptr(index.post_doc), _ptr(index.exp_off), index.n_postings,
-                                                   index.n_experts, index.dp, _ptr(qb.ent_vec), _ptr(qb.ent_q), qb.n_entries, _ptr(qb.bexp),
-                                                   _ptr(qb.boff), int(qb.bexp.shape[0]), qb.nq, _ptr(qb.cls), _ptr(index.cls), index.dc,
-                                                   0 if index.cls is None else index.cls.shape[0], index.corpus_len, int(id_begin),
-                                                   int(id_end), values.shape[1], int(chunk), _ptr(values), _ptr(indices),
-                                                   int(bool(first)), _ptr(ws), ws.numel(), self._stream()), "dprhot_ivf_search")
+                                                   index.n_experts, index.dp, *self._ivf_batch(qb), *self._ivf_cls(index, qb),
+                                                   *self._topk_tail(id_begin, id_end, values, indices, first, chunk, ws)),
+                        "dprhot_ivf_search")
 
     # -- exhaustive ColBERT search (csrc/colbert.h; DESIGN.md section 12; dpr_scale_amd/colbert.py owns the index) -------------
     def colbert_workspace(self, nq, chunk, k, like):
-        n = self._lib.colbert_workspace_bytes(nq, chunk)
-        if k > 4096:  # the HBM-resident selection's state lives behind the score buffer
-            m = ctypes.c_size_t(0)
-            self._lib.check(self.lib.dprhot_topk_wide_workspace_bytes(int(nq), int(k), ctypes.byref(m)), "dprhot_topk_wide_workspace_bytes")
-            n += m.value
-        return torch.empty(n, dtype=torch.uint8, device=like.device)
+        return self._chunk_workspace(self._lib.colbert_workspace_bytes(nq, chunk), nq, k, like)
 
     def colbert_score(self, index, q, pool, doc_begin, cols, S):
         """Writes the scores of doc ids doc_begin .. doc_begin + cols into S [nq, >= cols] fp32 (dprhot_colbert_score); q bf16 [nq, LQ, dp]."""
@@ -629,8 +640,7 @@ class HipKernels:
         self._require_gpu(index.tok, index.doc_blk, q, values, indices, ws)
         nq, LQ, dp = q.shape
         self._lib.check(self.lib.dprhot_colbert_search(_ptr(index.tok), _ptr(index.doc_blk), index.n_blk, index.corpus_len, dp, _ptr(q), nq, LQ,
-                                                       int(pool), int(id_begin), int(id_end), values.shape[1], int(chunk), _ptr(values),
-                                                       _ptr(indices), int(bool(first)), _ptr(ws), ws.numel(), self._stream()),
+                                                       int(pool), *self._topk_tail(id_begin, id_end, values, indices, first, chunk, ws)),
                         "dprhot_colbert_search")
 
     # -- product-quantised postings (csrc/ivf_pq.h; dpr_scale_amd/ivf.py owns training and the index) ----
@@ -646,26 +656,23 @@ class HipKernels:
         self._lib.check(self.lib.dprhot_pq_encode(_ptr(vec), n, dp, _ptr(codebook), dsub, _ptr(codes), self._stream()), "dprhot_pq_encode")
         return codes
 
+    def _ivf_pq_index(self, index):
+        self._require_gpu(index.post_code, index.codebook, index.post_doc, index.exp_off)
+        return (_ptr(index.post_code), _ptr(index.codebook), index.dsub, _ptr(index.post_doc), _ptr(index.exp_off), index.n_postings,
+                index.n_experts, index.dp)
+
     def ivf_pq_score(self, index, qb, doc_begin, cols, S):
         """ivf_score for an IVFPQIndex (dprhot_ivf_pq_score)."""
-        self._require_gpu(index.post_code, index.codebook, index.post_doc, index.exp_off, qb.ent_vec, qb.ent_q, qb.bexp, qb.boff, S)
-        self._lib.check(self.lib.dprhot_ivf_pq_score(_ptr(index.post_code), _ptr(index.codebook), index.dsub, _ptr(index.post_doc),
-                                                     _ptr(index.exp_off), index.n_postings, index.n_experts, index.dp, _ptr(qb.ent_vec),
-                                                     _ptr(qb.ent_q), qb.n_entries, _ptr(qb.bexp), _ptr(qb.boff), int(qb.bexp.shape[0]),
-                                                     qb.nq, int(doc_begin), int(cols), _ptr(S), S.stride(0), self._stream()),
-                        "dprhot_ivf_pq_score")
+        self._require_gpu(S)
+        self._lib.check(self.lib.dprhot_ivf_pq_score(*self._ivf_pq_index(index), *self._ivf_batch(qb), int(doc_begin), int(cols), _ptr(S),
+                                                     S.stride(0), self._stream()), "dprhot_ivf_pq_score")
 
     def ivf_pq_search(self, index, qb, id_begin, id_end, values, indices, first, chunk, ws):
         """ivf_search for an IVFPQIndex (dprhot_ivf_pq_search); the workspace is ivf_workspace's."""
-        self._require_gpu(index.post_code, index.codebook, index.post_doc, index.exp_off, index.cls, qb.ent_vec, qb.ent_q, qb.bexp, qb.boff,
-                          qb.cls, values, indices, ws)
-        self._lib.check(self.lib.dprhot_ivf_pq_search(_ptr(index.post_code), _ptr(index.codebook), index.dsub, _ptr(index.post_doc),
-                                                      _ptr(index.exp_off), index.n_postings, index.n_experts, index.dp, _ptr(qb.ent_vec),
-                                                      _ptr(qb.ent_q), qb.n_entries, _ptr(qb.bexp), _ptr(qb.boff), int(qb.bexp.shape[0]),
-                                                      qb.nq, _ptr(qb.cls), _ptr(index.cls), index.dc,
-                                                      0 if index.cls is None else index.cls.shape[0], index.corpus_len, int(id_begin),
-                                                      int(id_end), values.shape[1], int(chunk), _ptr(values), _ptr(indices),
-                                                      int(bool(first)), _ptr(ws), ws.numel(), self._stream()), "dprhot_ivf_pq_search")
+        self._require_gpu(index.cls, qb.cls, values, indices, ws)
+        self._lib.check(self.lib.dprhot_ivf_pq_search(*self._ivf_pq_index(index), *self._ivf_batch(qb), *self._ivf_cls(index, qb),
+                                                      *self._topk_tail(id_begin, id_end, values, indices, first, chunk, ws)),
+                        "dprhot_ivf_pq_search")
 
     # -- postings and query batches from encoder outputs (csrc/ivf_pack.h; dpr_scale_amd/ivf.py drives them) ----
     def ivf_compact(self, expert_ids, weights, att, row_ids, test_weight, min_weight=0.0, capacity=None):
@@ -1352,7 +1359,7 @@ class CorpusSearch:
     into the running top-k on the device (dprhot_search)."""
 
     KMAX = 1024   # largest k of dprhot_search (GEMM with the filter epilogue); run_retrieval_pytorch.py:149 accepts any --topk
-    KWIDE = 4096  # largest k of the streaming top-k kernel (dprhot_topk_update: 8192 sort slots in 96 KB of LDS)
+    KWIDE = TOPK_KWIDE
 
     def __init__(self, query_embs, k, chunk=None, kernels=None):
         self.kn = kernels if kernels is not None else default_kernels()
@@ -1370,10 +1377,9 @@ class CorpusSearch:
         self.wide_ws = None
         self.first = True
 
-    def _add_wide_native(self, Cb, first_id):
-        """1024 < k <= 4096: the scores of a chunk from the MFMA path (dprhot_sim_fwd), folded into the running top-k by the streaming
-        kernel's wide instantiation (dprhot_topk_update: radix select from an empty state, then a threshold filter + bitonic merges in
-        LDS) -- no torch sort anywhere.  Chunks of 65536 passages: the score matrix of a chunk is nq x 256 KiB."""
+    def _add_chunks(self, Cb, first_id, fold):
+        """k beyond 1024: the scores of a chunk come from the MFMA path (dprhot_sim_fwd) and fold(S, cols, col_offset) takes them into
+        the running top-k -- no torch sort, no host sync per chunk.  Chunks of 65536 passages: a chunk's score matrix is nq x 256 KiB."""
         n, d = Cb.shape
         step = min(self.chunk, 65536)
         for j0 in range(0, n, step):
@@ -1382,34 +1388,26 @@ class CorpusSearch:
             blk = Cb[j0:j0 + cols]
             if pad:
                 blk = torch.cat([blk, torch.zeros((pad, d), dtype=_BF16, device=Cb.device)], 0)
-            S = self.kn.sim(self.Qb, blk.contiguous(), None, 1.0)
-            self.kn.topk_update(S, cols, first_id + j0, self.values, self.indices, self.first)
+            fold(self.kn.sim(self.Qb, blk.contiguous(), None, 1.0), cols, first_id + j0)
             self.first = False
 
-    def _add_wide(self, Cb, first_id):
-        """k beyond 4096: the scores come from the MFMA path chunk by chunk (dprhot_sim_fwd), the selection is the library's
-        HBM-resident one (dprhot_topk_update_wide, csrc/wideselect.h: exact radix select over state + chunk, ties at the k-th score
-        resolved by passage id, then only the k winners are sorted) -- no torch sort, no host sync per chunk.  _fold_rows_torch below is
+    def _fold_native(self, S, cols, col_offset):
+        """1024 < k <= 4096: the streaming kernel's wide instantiation (dprhot_topk_update: radix select from an empty state, then a
+        threshold filter + bitonic merges in LDS)."""
+        self.kn.topk_update(S, cols, col_offset, self.values, self.indices, self.first)
+
+    def _fold_wide(self, S, cols, col_offset):
+        """k beyond 4096: the library's HBM-resident selection (dprhot_topk_update_wide, csrc/wideselect.h: exact radix select over
+        state + chunk, ties at the k-th score resolved by passage id, then only the k winners are sorted).  _fold_rows_torch below is
         the path of the stand-in kernels only."""
-        n, d = Cb.shape
-        step = min(self.chunk, 65536)
         if self.wide_ws is None and hasattr(self.kn, "topk_update_wide"):
-            self.wide_ws = self.kn.topk_wide_workspace(self.values.shape[0], self.k, Cb)
-        for j0 in range(0, n, step):
-            cols = min(step, n - j0)
-            pad = (-cols) % 8
-            blk = Cb[j0:j0 + cols]
-            if pad:
-                blk = torch.cat([blk, torch.zeros((pad, d), dtype=_BF16, device=Cb.device)], 0)
-            S = self.kn.sim(self.Qb, blk.contiguous(), None, 1.0)
-            if self.wide_ws is not None:
-                self.kn.topk_update_wide(S, cols, first_id + j0, self.values, self.indices, self.first, self.wide_ws)
-            else:
-                if self.first:
-                    self.values.fill_(float("-inf"))
-                    self.indices.fill_(-1)
-                self._fold_rows_torch(None, S[:, :cols], first_id + j0)
-            self.first = False
+            self.wide_ws = self.kn.topk_wide_workspace(self.values.shape[0], self.k, S)
+        if self.wide_ws is not None:
+            return self.kn.topk_update_wide(S, cols, col_offset, self.values, self.indices, self.first, self.wide_ws)
+        if self.first:
+            self.values.fill_(float("-inf"))
+            self.indices.fill_(-1)
+        self._fold_rows_torch(None, S[:, :cols], col_offset)
 
     def _fold_rows_torch(self, rows, S, first_col):
         """Exact fold of one chunk into the state of `rows` (None: all) with torch's stable sorts, in the same total order (score desc,
@@ -1437,9 +1435,8 @@ class CorpusSearch:
             Cb = self.kn.empty((n, d), _BF16, corpus_embs)
             self.kn.cast_bf16(corpus_embs, Cb)
         if self.wide_k:
-            if self.k <= self.KWIDE and hasattr(self.kn, "topk_update"):
-                return self._add_wide_native(Cb, first_id)
-            return self._add_wide(Cb, first_id)
+            native = self.k <= self.KWIDE and hasattr(self.kn, "topk_update")
+            return self._add_chunks(Cb, first_id, self._fold_native if native else self._fold_wide)
         n8 = n // 8 * 8
         if n8:
             self.kn.search(self.Qb, Cb[:n8], first_id, self.values, self.indices, self.first, self.chunk, self.ws)

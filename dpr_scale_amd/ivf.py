@@ -35,9 +35,10 @@ import time
 
 import torch
 
+from ._chunked import ChunkedIndex, _default_kernels
+
 _BF16 = torch.bfloat16
 MAX_ENTRIES_PER_QUERY = 4096  # dprhot_ivf_search's limit
-KNARROW = 4096                # largest k of dprhot_topk_update; beyond it the HBM-resident selection runs
 
 
 def _pad_cols(x, mult):
@@ -158,10 +159,8 @@ def read_postings(ctx_embeddings_dir, corpus_len):
     return torch.cat(experts), torch.cat(docs), torch.cat(vecs, 0), (torch.cat(cls_parts, 0) if cls_parts else None)
 
 
-class IVFIndex:
+class IVFIndex(ChunkedIndex):
     """Device-resident inverted index; `search` stands where the reference's IVFGPUIndex.search stood."""
-
-    _search_kernel = "ivf_search"  # the kernel-table entry search_packed folds a doc-id range with
 
     def __init__(self, experts, docs, vecs, cls, corpus_len, device, chunk=None, kernels=None):
         """From unsorted CPU postings: expert int64 [P], doc int64 [P], vec fp32 [P, d], cls fp32 [corpus_len, dc] or None."""
@@ -196,43 +195,34 @@ class IVFIndex:
         self._set(post_doc, post_vec, exp_off, cls_rows, int(corpus_len), int(d), chunk, kernels)
         return self
 
-    def _set(self, post_doc, post_vec, exp_off, cls_rows, corpus_len, d, chunk, kernels):
-        assert post_doc.dtype == torch.int32 and post_vec.dtype == _BF16 and exp_off.dtype == torch.int64 and post_vec.shape[1] % 32 == 0
+    def _set_frame(self, post_doc, exp_off, cls_rows, corpus_len, d, dp, chunk, kernels):
+        """Everything but the posting rows themselves, which the dense and the product-quantised index hold in their own form."""
+        assert post_doc.dtype == torch.int32 and exp_off.dtype == torch.int64
         self.device = post_doc.device
-        self.corpus_len, self.d = corpus_len, d
+        self.corpus_len, self.d, self.dp = corpus_len, d, dp
         self.n_experts, self.n_postings = int(exp_off.shape[0]) - 1, int(post_doc.shape[0])
-        self.post_doc, self.post_vec, self.exp_off = post_doc, post_vec, exp_off
-        self.dp = int(post_vec.shape[1])
+        self.post_doc, self.exp_off = post_doc, exp_off
         self.cls, self.dc = cls_rows, (0 if cls_rows is None else int(cls_rows.shape[1]))
-        self.chunk = None if chunk is None else int(chunk)
-        self.kn = kernels
-        self.latency = collections.defaultdict(float)
-        self.latency["encode_time"] += 0.0  # test_epoch_end of the retrieval task pops this key
+        self._init_search(chunk, kernels)
+
+    def _set(self, post_doc, post_vec, exp_off, cls_rows, corpus_len, d, chunk, kernels):
+        assert post_vec.dtype == _BF16 and post_vec.shape[1] % 32 == 0
+        self._set_frame(post_doc, exp_off, cls_rows, corpus_len, d, int(post_vec.shape[1]), chunk, kernels)
+        self.post_vec = post_vec
 
     @property
     def nbytes(self):
         """Bytes of device memory the index holds (posting rows, doc ids, offsets, CLS rows)."""
         return sum(t.numel() * t.element_size() for t in (self.post_doc, self.post_vec, self.exp_off, self.cls) if t is not None)
 
-    def _kernels(self):
-        if self.kn is None:
-            from . import hotpath
-
-            self.kn = hotpath.default_kernels()
-        return self.kn
-
-    def default_chunk(self, nq):
-        """Doc ids per pass: the chunk's score buffer is nq x chunk fp32 (at most 8 MiB by default, at least 1024 ids)."""
-        c = self.chunk if self.chunk is not None else max(1024, min(262144, (1 << 21) // max(nq, 1)))
-        c = min(c, (self.corpus_len + 7) // 8 * 8)
-        return max(8, c // 8 * 8)
+    def _search_range(self, kn, qb, *tail):
+        """One doc-id range through the index's search kernel (the product-quantised index has its own)."""
+        kn.ivf_search(self, qb, *tail)
 
     def search_packed(self, qb, topk, id_ranges=None, chunk=None):
         """(scores [nq, topk] fp32, ids [nq, topk] int64) for a packed batch on the index's device.  `id_ranges`: disjoint
         (begin, end) doc-id ranges folded into one result (default: the whole corpus)."""
         topk = int(topk)
-        if not 1 <= topk <= self.corpus_len:
-            raise ValueError(f"topk={topk} out of range (1 .. corpus_len={self.corpus_len})")
         if (qb.cls is None) != (self.cls is None):
             raise ValueError("CLS vectors on one side only: the index and the queries must both have them or both lack them")
         if qb.cls is not None and qb.cls.shape[1] != self.dc:
@@ -241,15 +231,9 @@ class IVFIndex:
             raise ValueError(f"query vectors of padded width {qb.ent_vec.shape[1]}, index of {self.dp}")
         kn = self._kernels()
         qb = qb.to(self.device)
-        chunk = self.default_chunk(qb.nq) if chunk is None else int(chunk)
-        values = torch.empty((qb.nq, topk), dtype=torch.float32, device=self.device)
-        indices = torch.empty((qb.nq, topk), dtype=torch.int64, device=self.device)
-        ws = kn.ivf_workspace(qb.nq, qb.n_entries, chunk, self.cls is not None, topk, self.post_doc)
-        first = True
-        for b, e in (id_ranges if id_ranges is not None else [(0, self.corpus_len)]):
-            getattr(kn, self._search_kernel)(self, qb, int(b), int(e), values, indices, first, chunk, ws)
-            first = False
-        return values, indices
+        return self._fold(qb.nq, topk, id_ranges, chunk,
+                          lambda chunk: kn.ivf_workspace(qb.nq, qb.n_entries, chunk, self.cls is not None, topk, self.post_doc),
+                          lambda *tail: self._search_range(kn, qb, *tail))
 
     def search(self, batch_cls, batch_embeddings, batch_weights, topk, id_ranges=None, chunk=None):
         tic = time.perf_counter()
@@ -358,8 +342,6 @@ class IVFPQIndex(IVFIndex):
     """IVFIndex with product-quantised postings: post_code uint8 [P, m] and ONE codebook bf16 [m, 256, dsub] instead of post_vec.
     `search` / `search_packed` return, bit for bit, what `decode()` -- the IVFIndex over the decoded rows -- returns."""
 
-    _search_kernel = "ivf_pq_search"
-
     def __init__(self, *args, **kwargs):
         raise TypeError("an IVFPQIndex comes from IVFIndex.quantize, IVFPQIndex.from_packed or load_pq_index")
 
@@ -370,19 +352,14 @@ class IVFPQIndex(IVFIndex):
         self = cls.__new__(cls)
         m, _, dsub = codebook.shape
         _check_codebook(codebook, m * dsub, dsub)
-        assert post_doc.dtype == torch.int32 and exp_off.dtype == torch.int64 and post_code.dtype == torch.uint8
+        assert post_code.dtype == torch.uint8
         assert post_code.shape == (post_doc.shape[0], m) and post_code.is_contiguous() and codebook.is_contiguous()
-        self.device = post_doc.device
-        self.corpus_len, self.d = int(corpus_len), int(d)
-        self.n_experts, self.n_postings = int(exp_off.shape[0]) - 1, int(post_doc.shape[0])
-        self.post_doc, self.post_code, self.codebook, self.exp_off = post_doc, post_code, codebook, exp_off
-        self.dsub, self.dp = int(dsub), int(m * dsub)
-        self.cls, self.dc = cls_rows, (0 if cls_rows is None else int(cls_rows.shape[1]))
-        self.chunk = None if chunk is None else int(chunk)
-        self.kn = kernels
-        self.latency = collections.defaultdict(float)
-        self.latency["encode_time"] += 0.0
+        self._set_frame(post_doc, exp_off, cls_rows, int(corpus_len), int(d), int(m * dsub), chunk, kernels)
+        self.post_code, self.codebook, self.dsub = post_code, codebook, int(dsub)
         return self
+
+    def _search_range(self, kn, qb, *tail):
+        kn.ivf_pq_search(self, qb, *tail)
 
     def _tensors(self):
         return dict(post_doc=self.post_doc, post_code=self.post_code, codebook=self.codebook, exp_off=self.exp_off, cls=self.cls)
@@ -468,14 +445,6 @@ def query_dicts(queries_repr, n):
         batch_embeddings.append(embeddings)
         batch_weights.append(weights)
     return batch_embeddings, batch_weights
-
-
-def _default_kernels(kernels):
-    if kernels is None:
-        from . import hotpath
-
-        kernels = hotpath.default_kernels()
-    return kernels
 
 
 def _slots(repr_, n=None):

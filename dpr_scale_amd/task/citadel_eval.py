@@ -62,11 +62,15 @@ class GenerateMultiVecEmbeddingsTask(MultiVecRetrieverTask):
     def test_step(self, batch, batch_idx):
         return self._eval_step(batch, batch_idx)
 
+    def _index_file(self):
+        """What `builder.write` leaves under ctx_embeddings_dir for this rank."""
+        return f"expert_{self.global_rank:04}"
+
     def test_epoch_end(self, contexts_reprs):
         if not self.ctx_embeddings_dir:
             self.ctx_embeddings_dir = self.trainer.weights_save_path
         if self.builder is not None:
-            print(f"\nWriting tensors to {os.path.join(self.ctx_embeddings_dir, f'expert_{self.global_rank:04}')}")
+            print(f"\nWriting tensors to {os.path.join(self.ctx_embeddings_dir, self._index_file())}")
             self.builder.write(self.ctx_embeddings_dir, self.global_rank)
             self.builder = None
         _barrier()

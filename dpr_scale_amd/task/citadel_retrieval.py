@@ -114,8 +114,13 @@ class CITADELRetrievalTask(MultiVecRetrieverTask):
         answers = batch["answers"] if "answers" in batch else []
         questions = batch["question"] if "question" in batch else []
         queries_repr = {k: v.detach() for k, v in self(query_ids).items()}
-        batch_cls = queries_repr["cls_repr"] if "cls_repr" in queries_repr else []
         n = len(topic_ids) if len(topic_ids) > 0 else len(query_ids["input_ids"])
+        batch_top_scores, batch_top_ids = self._search(queries_repr, n, tic)
+        return batch_top_scores.cpu().tolist(), batch_top_ids.cpu().tolist(), topic_ids, questions, answers
+
+    def _search(self, queries_repr, n, tic):
+        """(scores, ids) of the first n queries of the batch; `tic` is when the step began (encode_time runs up to the search)."""
+        batch_cls = queries_repr["cls_repr"] if "cls_repr" in queries_repr else []
         if self.device_pack and queries_repr["expert_repr"].is_cuda and self.index.device.type == "cuda":
             # the batch is packed where the encoder left it (ivf.pack_queries_device): same tensors as the host path below, bit for bit
             qb = ivf.pack_queries_device(queries_repr, batch_cls, n, kernels=self.index._kernels())
@@ -123,11 +128,10 @@ class CITADELRetrievalTask(MultiVecRetrieverTask):
             tic = time.perf_counter()
             batch_top_scores, batch_top_ids = self.index.search_packed(qb, self.topk)
             self.index.latency["search_time"] += time.perf_counter() - tic
-            return batch_top_scores.cpu().tolist(), batch_top_ids.cpu().tolist(), topic_ids, questions, answers
+            return batch_top_scores, batch_top_ids
         batch_embeddings, batch_weights = ivf.query_dicts(queries_repr, n)
         self.latency["encode_time"] += time.perf_counter() - tic
-        batch_top_scores, batch_top_ids = self.index.search(batch_cls, batch_embeddings, batch_weights, self.topk)
-        return batch_top_scores.cpu().tolist(), batch_top_ids.cpu().tolist(), topic_ids, questions, answers
+        return self.index.search(batch_cls, batch_embeddings, batch_weights, self.topk)
 
     def test_step(self, batch, batch_idx):
         return self._eval_step(batch, batch_idx)

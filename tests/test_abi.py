@@ -133,6 +133,47 @@ def test_argument_validation_is_host_side():
         _lib.check(-1, "x")
 
 
+_ONE = ctypes.c_void_p(256)  # never dereferenced: validation is host code and fails before any launch
+_TAIL = dict(n=100, b=0, e=100, k=5, chunk=64, vals=_ONE, idx=_ONE, first=1, ws=_ONE, wsb=1 << 20, st=None)  # nq = 2: 512 score bytes
+_IVF_BATCH = dict(ev=_ONE, eq=_ONE, ne=2, be=_ONE, bo=_ONE, nb=1, nq=2, cq=None, cd=None, dc=0, cr=0)
+# the good arguments of each chunked search in the order of its signature; all three end with corpus_len and the top-k tail
+_CHUNKED_SEARCHES = {
+    "ivf": ("dprhot_ivf_search", dict(pv=_ONE, pd=_ONE, eo=_ONE, P=10, V=4, dp=32, **_IVF_BATCH, **_TAIL)),
+    "ivf_pq": ("dprhot_ivf_pq_search", dict(pc=_ONE, cb=_ONE, dsub=4, pd=_ONE, eo=_ONE, P=10, V=4, dp=32, **_IVF_BATCH, **_TAIL)),
+    "colbert": ("dprhot_colbert_search", dict(tok=_ONE, blk=_ONE, nb=10, n=100, dp=32, q=_ONE, nq=2, LQ=5, pool=0,
+                                              **{k: v for k, v in _TAIL.items() if k != "n"})),
+}
+_BAD_TAILS = [  # (what is wrong, code, a word of the error text)
+    (dict(vals=None), -1, b"NULL"), (dict(idx=None), -1, b"NULL"),
+    (dict(k=0), -1, b"topk"), (dict(k=101), -1, b"topk"),
+    (dict(b=50, e=40), -1, b"range"), (dict(b=7, e=7), -1, b"range"), (dict(e=101), -1, b"range"),
+    (dict(chunk=12), -1, b"chunk"), (dict(chunk=0), -1, b"chunk"),
+    (dict(ws=None), -4, b"workspace"), (dict(wsb=16), -4, b"workspace"),
+    (dict(n=6000, e=6000, k=5000, wsb=2 * 64 * 4), -4, b"workspace"),  # k > 4096: the wide selection's state is missing
+]
+
+
+@pytest.mark.parametrize("family", sorted(_CHUNKED_SEARCHES))
+def test_chunked_searches_validate_their_tail_alike(family):
+    """One table of bad tail arguments (outputs, k, doc-id range, chunk, workspace) through the three searches that share the chunk
+    driver: the same code and the same word per case, and a workspace error that names the family's own function."""
+    from dpr_scale_amd import _lib
+
+    lib = _lib.lib
+    symbol, good = _CHUNKED_SEARCHES[family]
+    search = getattr(lib, symbol)
+    # the dense and the product-quantised search share a workspace function, and the error says so
+    who = b"colbert" if family == "colbert" else b"ivf"
+    for bad, code, word in _BAD_TAILS:
+        assert set(bad) <= set(good), bad
+        rc = search(*[bad.get(k, v) for k, v in good.items()])
+        err = lib.dprhot_last_error()
+        assert rc == code and word in err, (family, bad, rc, err)
+        if code == -4:
+            assert who + b"_search needs" in err and b"dprhot_" + who + b"_workspace_bytes" in err, (family, err)
+            assert (b"dprhot_topk_wide_workspace_bytes" in err) == ("k" in bad), (family, err)
+
+
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):
     import importlib
     import sys

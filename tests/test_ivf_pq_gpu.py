@@ -132,6 +132,27 @@ def test_runs_are_bit_identical_and_independent_of_chunk_and_batch(kn):
     assert torch.equal(v, ref[0][3:]) and torch.equal(i, ref[1][3:])
 
 
+def test_wide_k_equals_the_dense_search_and_is_independent_of_the_chunk(kn):
+    """k beyond 4096: the chunk driver folds with the HBM-resident selection (dprhot_topk_update_wide), five chunks of 1024 doc ids
+    (the last one ragged) against one chunk of the whole corpus, and against the dense search over the decoded rows."""
+    ndocs, k = 5003, 4500
+    g = np.random.default_rng(61)
+    docs = [np.sort(g.integers(0, ndocs, size=int(g.integers(30, 110)))) for _ in range(70)]
+    post_doc = torch.from_numpy(np.concatenate(docs).astype(np.int32))
+    exp_off = torch.from_numpy(np.concatenate([[0], np.cumsum([len(d) for d in docs])]).astype(np.int64))
+    tg = torch.Generator().manual_seed(62)
+    codes = torch.randint(0, 256, (post_doc.shape[0], 8), generator=tg).to(torch.uint8)
+    codebook = torch.randn(8, 256, 4, generator=tg).to(BF16)
+    cls = torch.cat([torch.randn(ndocs, 16, generator=tg).to(BF16), torch.zeros((8, 16), dtype=BF16)], 0)
+    pq = ivf.IVFPQIndex.from_packed(post_doc.to(DEV), codes.to(DEV), codebook.to(DEV), exp_off.to(DEV), cls.to(DEV), ndocs, 32, kernels=kn)
+    qb = ivf.pack_queries(torch.randn(6, 16, generator=tg), _queries(63, 32), None).to(DEV)
+    got = pq.search_packed(qb, k, chunk=1024)
+    assert got[0].shape == (6, k) and bool((got[1] >= 0).all()) and bool((got[1] < ndocs).all())
+    assert bool((got[0][:, :-1] >= got[0][:, 1:]).all()) and all(len(set(row)) == k for row in got[1].tolist())
+    assert _same(got, pq.decode().search_packed(qb, k, chunk=1024))
+    assert _same(got, pq.search_packed(qb, k, chunk=5008))
+
+
 def _encode_between_bands(rows, codebook):
     """dprhot_pq_encode through ctypes alone; the codes sit between two 4 KiB bands that must come back intact."""
     from dpr_scale_amd import _lib
