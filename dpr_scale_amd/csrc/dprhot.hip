@@ -164,7 +164,7 @@ int launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... arg
 // ---- explicit process-wide options (dprhot_set_option): test and A/B switches of the plans.  Production never sets one; they replace
 // the environment switches the library used to cache on first use (hidden configuration behind an ABI that advertises none).
 enum OptId { OPT_TILE, OPT_NO_TR, OPT_UNFUSED_BWD, OPT_BIG_MIN, OPT_NO_NL, OPT_NO_BIG_BWD, OPT_NO_SKINNY, OPT_NO_SMALL_STEP, OPT_NO_SHORT,
-             OPT_SK_COLS, OPT_SEARCH_UNFUSED, OPT_NO_8PB, OPT_NO_WIDE, OPT_WIDE_NOCOPY, OPT_NO_8P_STORE, OPT_NO_WIDE_BWD, OPT_NT_STORES, OPT_SK_DQ_SLICES, OPT_SK_FUSED, OPT_SK_DBG, OPT_SK_W8, OPT_SK_PAIR, OPT_SK_SIM_W8, OPT_SK_SIM_PRIV, OPT_SK_TAIL, OPT_SK_DC_REGSCALE, OPT_G8_ONE_TILE, OPT_NL_P16, OPT_SK_DQ_ATOMIC, OPT_NL_MIN, OPT_G128_DMA, OPT_DC_ALONE_8P, OPT_DQ_ONE_ROUND, OPT_DQ_CAP_FEW, OPT_LOSS_WITH_DQ, OPT_NL128, OPT_NL128_BELOW, OPT_PAIR128, OPT_PAIR128_CAP, OPT_NL128_MIN_TILES, OPT_P16_STAGED, OPT_SMALL_SIM, OPT_SMALL_STEP_ROLES, OPT_COUNT };
+             OPT_SK_COLS, OPT_SEARCH_UNFUSED, OPT_NO_8PB, OPT_NO_WIDE, OPT_WIDE_NOCOPY, OPT_NO_8P_STORE, OPT_NO_WIDE_BWD, OPT_NT_STORES, OPT_SK_DQ_SLICES, OPT_SK_FUSED, OPT_SK_DBG, OPT_SK_W8, OPT_SK_PAIR, OPT_SK_SIM_W8, OPT_SK_SIM_PRIV, OPT_SK_TAIL, OPT_SK_DC_REGSCALE, OPT_G8_ONE_TILE, OPT_NL_P16, OPT_SK_DQ_ATOMIC, OPT_NL_MIN, OPT_G128_DMA, OPT_DC_ALONE_8P, OPT_DQ_ONE_ROUND, OPT_DQ_CAP_FEW, OPT_LOSS_WITH_DQ, OPT_NL128, OPT_NL128_BELOW, OPT_PAIR128, OPT_PAIR128_CAP, OPT_NL128_MIN_TILES, OPT_P16_STAGED, OPT_SMALL_SIM, OPT_SMALL_STEP_ROLES, OPT_SMALL_SIM_COPY, OPT_COUNT };
 struct OptDef { OptId id; const char* name; int def; const char* what; };
 constexpr OptDef kOptDefs[OPT_COUNT] = {
     {OPT_TILE, "tile", -1, "0..5 pins the tile of the single-GEMM launches (gemm_bf16.h), -1 = plan"},
@@ -210,6 +210,7 @@ constexpr OptDef kOptDefs[OPT_COUNT] = {
     {OPT_P16_STAGED, "p16_staged", 1, "one-pass forward on the 256 x 256 kernel: the fp16 numerators leave through the per-wave LDS patch (64-byte pieces of 16 rows per store instruction instead of 32-byte pieces of 32 rows; bit-identical): 1 = except where the row pitch of G is a multiple of 128 KiB (forward us, arms alternating, profiles/r06_p16_staged_ab.txt: 8192^2 155.4 -> 147.8, 4096 x 8192 83.2 -> 79.3, 4096 x 16384 153 -> 146 and its step 390 -> 372; at 65536 columns the forward gains nothing and the step of 8192 x 65536 LOSES 100 us of 2880), 2 = always, 0 = never"},
     {OPT_SMALL_SIM, "small_sim", 1, "sim launch of the batch-32 step (B <= 32, fp32 q, 256-deep K chunks: sim_small.h): 1 = one wave per 16 x 16 tile and K chunk on an exact 3-D grid (row tile, column tile, chunk: no division and one wait on the arguments in front of the first operand load, the mask byte loaded last), whole-line loads rounded into a wave-private LDS patch, no barrier (bit-identical to the engine; 32 x 256 x 768 step 9.19 -> 8.29 us, with the 3-D grid 7.21 -> 7.05); 0 = the GEMM engine (tile 5); A/B only: 2 = fp32 straight into fragment registers, no LDS (8.52 us), 3 / 4 = forms 1 / 2 with two waves per workgroup (8.70 / 9.41 us)"},
     {OPT_SMALL_STEP_ROLES, "small_step_roles", 3, "softmax + backward launch of the batch-32 step (B <= 32, at most 768 columns: step_small_kernel_roles / step_small_kernel_out in step_small.h): one launch split by role -- d / 16 dC workgroups (slabs + Q tile, full softmax, one barrier, dC product and stores) next to one dQ workgroup per 16-row half and column tile (half the slabs + C tile, 8 K slices); 3 = form 2 with the outputs written by workgroups of their own that have no product to do, in front of the grid, instead of by the dC workgroup of tile 0: a loss block (softmax up to the row loss, logsumexp / row loss, one barrier, the loss sum) and two row-store blocks (one 16-row half each: dScores / logits, no barrier); the device-side scale is the last load of a role, not a wait in front of it (a stamping launch of the packed step keeps form 2), 2 = 32-column dQ tiles (d % 32 == 0, else form 1; 32 x 256 x 768 step 8.29 -> 7.74 us), 1 = 16-column dQ tiles (7.84 us), 0 = every workgroup does both products (step_small_kernel); all forms bit-identical (tests/test_small_step_roles.py, tests/test_small_step_out.py, tests/test_small_step_split_gpu.py)"},
+    {OPT_SMALL_SIM_COPY, "small_sim_copy", 1, "sim launch of the batch-32 step where small_sim selects form 1: 1 = the bf16 copies Qb / Cb are written by waves of their own behind the compute waves in dispatch order (sim_small_split_kernel: 16 rows x one 256-deep chunk of one operand per wave, whole-line loads, the same v_cvt_pk_bf16_f32 pairing, 8-byte stores; the compute waves go from their MFMA chain straight to their slab stores; bit-identical); 0 = every compute wave of row tile 0 / column tile 0 stores the copies itself, in front of its slab stores (sim_small_kernel)"},
 };
 constexpr bool opt_table_in_enum_order() {  // (round 6: a row added in the wrong place made two options answer to each other's names)
   for (int i = 0; i < OPT_COUNT; ++i)
@@ -724,8 +725,16 @@ int launch_sim_small(bool b_f32, const GemmArgs& a, const EpiSim& epi, int split
   const int form = (v == 2 || v == 4) ? SS_REG : SS_PATCH, wpg = (v == 3 || v == 4) ? 2 : 1;
   // an exact 3-D grid (row tile x wpg, column tile, K chunk): the kernel takes its tile from the block index, without a division
   const int nrt = cdiv(a.M, 16), nct = cdiv(a.N, 16);
-  const dim3 grid(cdiv(nrt, wpg), nct, splits), block(64 * wpg);
   const size_t lds = sim_small_lds(form, b_f32, wpg);
+  if (v == 1 && opt(OPT_SMALL_SIM_COPY) != 0) {
+    // the copies on waves of their own: `splits` layers of copy waves behind the compute waves, one wave per operand tile and chunk
+    // (C tiles only where the contexts are fp32 and have a copy) -- two layers per chunk where a layer of the grid is smaller than that
+    const int units = (b_f32 && a.Bcopy != nullptr ? nct : 0) + (a.Acopy != nullptr ? nrt : 0);
+    const dim3 grid(nrt, nct, splits + cdiv(units, nrt * nct) * splits), block(64);
+    return b_f32 ? launch<sim_small_split_kernel<true>>(grid, block, lds, st, splits, a, epi)
+                 : launch<sim_small_split_kernel<false>>(grid, block, lds, st, splits, a, epi);
+  }
+  const dim3 grid(cdiv(nrt, wpg), nct, splits), block(64 * wpg);
   if (form == SS_REG)
     return b_f32 ? launch<sim_small_kernel<true, SS_REG>>(grid, block, lds, st, wpg, a, epi)
                  : launch<sim_small_kernel<false, SS_REG>>(grid, block, lds, st, wpg, a, epi);

@@ -19,10 +19,12 @@
 
 #ifdef DPRHOT_TIMING
 extern __device__ unsigned long long g_dprhot_tm[64];
+#ifndef DPRHOT_TM  // a stamping tool may bring its own (scratch/step_small_stamps.hip: every workgroup of the sim launch)
 #define DPRHOT_TM(i)                                                                       \
   do {                                                                                     \
     if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0) g_dprhot_tm[i] = wall_clock64(); \
   } while (0)
+#endif
 // per-workgroup stamps (scratch/sk_timing.hip): slot i of workgroup blockIdx.x
 extern __device__ unsigned long long g_dprhot_tmb[4 * 4096 * 8];
 #define DPRHOT_TMB(k, i)                                                                                      \

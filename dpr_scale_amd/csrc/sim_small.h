@@ -65,12 +65,12 @@ __device__ __forceinline__ bf16x8 sms_patch_frag(const uint16_t* T, int kk, int 
 // cost no division (three v_rcp_iflag sequences stood in front of the first load) and no early return: a wave beyond the last row
 // tile (wpg = 2 at an odd number of row tiles) loads clamped rows and stores nothing, as a ragged tile's rows beyond M do.
 // wpg is the first argument, in the 64 bytes of the kernel arguments that hold everything the operand addresses are made of.
-template <bool B_F32, int FORM>
-__global__ __launch_bounds__(64 * SMS_MAXW) void sim_small_kernel(int wpg, GemmArgs p, EpiSim epi) {
-  extern __shared__ __attribute__((aligned(16))) uint16_t sms_smem[];
+//
+// sms_tile is one wave's whole life, shared by the two kernels below.  COPIES: the wave also writes the bf16 copies the backward reads
+// (Qb by the waves of column tile 0, Cb by those of row tile 0); without, they are sim_small_split_kernel's copy waves' to write.
+template <bool B_F32, int FORM, bool COPIES>
+__device__ __forceinline__ void sms_tile(uint16_t* sms_smem, int wave, int rt, int ct, int bz, const GemmArgs& p, const EpiSim& epi) {
   const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int rt = (int)blockIdx.x * wpg + wave, ct = (int)blockIdx.y, bz = (int)blockIdx.z;
   const int m0 = rt * 16, n0 = ct * 16, kbeg = bz * SMS_KC;
   DPRHOT_TM(0);
 
@@ -152,23 +152,27 @@ __global__ __launch_bounds__(64 * SMS_MAXW) void sim_small_kernel(int wpg, GemmA
   // settled HERE all the same (vmcnt(0), the other counters left alone: the one wait in this file that the compiler did not place):
   // the compiler waits where the byte is first looked at, below the copies' conditional stores, and as the same counter counts
   // stores, the slab stores of half the waves would wait for their copies to be acknowledged.
-  __builtin_amdgcn_s_waitcnt(0x0F70);
+  // (Without the copies nothing stands between the chain and the slab stores but the header words' store of ONE wave, which is
+  // moved behind them: the compiler's own wait for the byte is then the chain's.)
+  if constexpr (COPIES) __builtin_amdgcn_s_waitcnt(0x0F70);
   DPRHOT_TM(4);
 
   // ---- the bf16 copies the backward reads: each operand row by exactly one wave per chunk (16-byte pieces, 16 rows x 64 B each)
-  if (p.Acopy != nullptr && ct == 0 && m0 + i < p.M) {
-#pragma unroll
-    for (int kk = 0; kk < SMS_KK; ++kk)
-      *reinterpret_cast<bf16x8*>(p.Acopy + (size_t)(m0 + i) * p.lda + kbeg + kk * 32 + g * 8) = af[kk];
-  }
-  if constexpr (B_F32) {
-    if (p.Bcopy != nullptr && rt == 0 && n0 + i < p.N) {
+  if constexpr (COPIES) {
+    if (p.Acopy != nullptr && ct == 0 && m0 + i < p.M) {
 #pragma unroll
       for (int kk = 0; kk < SMS_KK; ++kk)
-        *reinterpret_cast<bf16x8*>(p.Bcopy + (size_t)(n0 + i) * p.ldb + kbeg + kk * 32 + g * 8) = bfr[kk];
+        *reinterpret_cast<bf16x8*>(p.Acopy + (size_t)(m0 + i) * p.lda + kbeg + kk * 32 + g * 8) = af[kk];
     }
+    if constexpr (B_F32) {
+      if (p.Bcopy != nullptr && rt == 0 && n0 + i < p.N) {
+#pragma unroll
+        for (int kk = 0; kk < SMS_KK; ++kk)
+          *reinterpret_cast<bf16x8*>(p.Bcopy + (size_t)(n0 + i) * p.ldb + kbeg + kk * 32 + g * 8) = bfr[kk];
+      }
+    }
+    if (epi.zero_words != nullptr && (rt | ct | bz) == 0 && lane < epi.n_zero) epi.zero_words[lane] = 0ull;
   }
-  if (epi.zero_words != nullptr && (rt | ct | bz) == 0 && lane < epi.n_zero) epi.zero_words[lane] = 0ull;
 
   // ---- EpiSim::finish in its slab form (statistics off): * 1/T, masked columns -> -inf, fp32 partial logits of this chunk
   float* const S = epi.S + (size_t)bz * epi.slab_stride;
@@ -179,7 +183,77 @@ __global__ __launch_bounds__(64 * SMS_MAXW) void sim_small_kernel(int wpg, GemmA
     const float v = masked ? -INFINITY : acc[r] * epi.inv_T;
     if (m < epi.M && n0 + i < epi.N) S[(size_t)m * epi.N + n0 + i] = v;
   }
+  if constexpr (!COPIES) {
+    if (epi.zero_words != nullptr && (rt | ct | bz) == 0 && lane < epi.n_zero) epi.zero_words[lane] = 0ull;
+  }
   DPRHOT_TM(6);
+}
+
+template <bool B_F32, int FORM>
+__global__ __launch_bounds__(64 * SMS_MAXW) void sim_small_kernel(int wpg, GemmArgs p, EpiSim epi) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t sms_smem[];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  sms_tile<B_F32, FORM, true>(sms_smem, wave, (int)blockIdx.x * wpg + wave, (int)blockIdx.y, (int)blockIdx.z, p, epi);
+}
+
+// The same launch with the bf16 copies on waves of their own (option small_sim_copy; SS_PATCH, one wave per workgroup).  The grid is
+// (row tiles, column tiles, splits + copy layers): the waves of the first `splits` z layers are sms_tile without its copies; behind
+// them in dispatch order, `splits` (or 2 x splits, where one layer of the grid has fewer waves than there are operand tiles: one row
+// tile or one column tile) layers of copy waves.  A copy wave takes 16 rows of one 256-deep chunk of ONE operand: z - splits is the
+// chunk (a second layer: + splits), id = (layer * column tiles + y) * row tiles + x the unit, C tiles first, then Q tiles, the rest
+// return at once.  It loads whole lines as sms_tile does (instruction j: rows (j & 1) * 8 + lane / 8 of line j / 2), all 16 loads
+// before the first use, rounds its four floats with the same v_cvt_pk_bf16_f32 pairing (x, y), (z, w) -- the words of Qb / Cb are
+// the ones sms_tile's fragments hold -- and stores them as one 8-byte piece: 8 rows x 64 contiguous bytes per instruction.  Rows
+// beyond the operand are loaded clamped and not stored.  No LDS hop, no fragment reads, no MFMA chain, half the bytes: on a CU of
+// its own such a wave ends before the compute waves do, and these no longer carry 8 (16) stores between their chain and their slab.
+// Everything either role's addresses are made of is in the first 64 bytes of the kernel arguments (`splits` in wpg's place).
+template <bool B_F32>
+__device__ __forceinline__ void sms_copy_wave(int zc, int splits, const GemmArgs& p) {
+  DPRHOT_TM(0);
+  const int lane = threadIdx.x & 63;
+  const int nrt = (p.M + 15) >> 4, nct = (p.N + 15) >> 4;
+  const int layer = zc >= splits ? 1 : 0, kbeg = (zc - layer * splits) * SMS_KC;
+  const int id = (layer * nct + (int)blockIdx.y) * nrt + (int)blockIdx.x;
+  const int ncu = B_F32 && p.Bcopy != nullptr ? nct : 0, nqu = p.Acopy != nullptr ? nrt : 0;
+  if (id >= ncu + nqu) return;
+  const bool is_c = id < ncu;
+  const float* const src = reinterpret_cast<const float*>(is_c ? p.B : p.A);
+  uint16_t* const dst = is_c ? p.Bcopy : p.Acopy;
+  const int rows = is_c ? p.N : p.M, ld = is_c ? p.ldb : p.lda, r0 = (is_c ? id : id - ncu) * 16 + (lane >> 3);
+  const float* const sp[2] = {src + (size_t)min(r0, rows - 1) * ld + kbeg + (lane & 7) * 4, src + (size_t)min(r0 + 8, rows - 1) * ld + kbeg + (lane & 7) * 4};
+  float4 raw[2 * SMS_KK];
+#pragma unroll
+  for (int j = 0; j < 2 * SMS_KK; ++j) raw[j] = *reinterpret_cast<const float4*>(sp[j & 1] + (j >> 1) * 32);
+  __builtin_amdgcn_sched_barrier(0);  // every load is out before anything looks at a loaded value
+  DPRHOT_TM(1);
+  // All sixteen are waited for in ONE place, in front of the predicated stores (the last store needs the last load anyway).  The
+  // compiler lays this role's text in front of the compute role's and counts what may be in flight where the two join: with its own
+  // waits inside the predicated blocks, a path around them leaves loads in flight, and the compute role's front gets waits on vmcnt.
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+  uint2 v[2 * SMS_KK];
+#pragma unroll
+  for (int j = 0; j < 2 * SMS_KK; ++j) v[j] = make_uint2(cvt_pk_bf16(raw[j].x, raw[j].y), cvt_pk_bf16(raw[j].z, raw[j].w));
+  // (two predicates for sixteen stores: a lane's second row is inside the operand only if its first one is)
+  if (r0 < rows) {
+    uint16_t* const dp = dst + (size_t)r0 * ld + kbeg + (lane & 7) * 4;
+#pragma unroll
+    for (int kk = 0; kk < SMS_KK; ++kk) *reinterpret_cast<uint2*>(dp + kk * 32) = v[2 * kk];
+    if (r0 + 8 < rows) {
+#pragma unroll
+      for (int kk = 0; kk < SMS_KK; ++kk) *reinterpret_cast<uint2*>(dp + (size_t)8 * ld + kk * 32) = v[2 * kk + 1];
+    }
+  }
+  DPRHOT_TM(6);
+}
+
+template <bool B_F32>
+__global__ __launch_bounds__(64) void sim_small_split_kernel(int splits, GemmArgs p, EpiSim epi) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t sms_smem[];
+  const int bz = (int)blockIdx.z;
+  if (bz < splits)
+    sms_tile<B_F32, SS_PATCH, false>(sms_smem, 0, (int)blockIdx.x, (int)blockIdx.y, bz, p, epi);
+  else
+    sms_copy_wave<B_F32>(bz - splits, splits, p);
 }
 
 }  // namespace dprhot
