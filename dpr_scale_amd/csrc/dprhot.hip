@@ -52,64 +52,45 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
-// Multi-rank packed layout (dprhot_inbatch_step_packed_f32): while set, every sim epilogue built on this thread reads the
-// column mask from the gathered buffer and the dC epilogues stamp the loss numerator (see EpiSim / EpiScaleF32).
+// Multi-rank packed layout (dprhot_inbatch_step_packed_f32): where base is set, the sim epilogues read the column mask from the gathered
+// buffer; where stamp_src is set, the dC epilogues stamp the loss numerator (see EpiSim / EpiScaleF32).
 struct PackedSpec {
   const uint8_t* base = nullptr;
   int rows_c = 1, n_ctx = 0, row_bytes = 0;
   const float* stamp_src = nullptr;
 };
-thread_local PackedSpec g_packed;
-struct PackedScope {
-  explicit PackedScope(const PackedSpec& p) { g_packed = p; }
-  ~PackedScope() { g_packed = PackedSpec{}; }
-};
 template <class E>
-E with_packed_mask(E e) {
-  if (g_packed.base != nullptr) {
-    e.packed = g_packed.base;
-    e.p_rows_c = g_packed.rows_c;
-    e.p_n_ctx = g_packed.n_ctx;
-    e.p_row_bytes = g_packed.row_bytes;
+E with_packed_mask(const PackedSpec& pk, E e) {
+  if (pk.base != nullptr) {
+    e.packed = pk.base;
+    e.p_rows_c = pk.rows_c;
+    e.p_n_ctx = pk.n_ctx;
+    e.p_row_bytes = pk.row_bytes;
   }
   return e;
 }
 template <class E>
-E with_loss_stamp(E e) {
-  if (g_packed.stamp_src != nullptr) {
-    e.stamp_src = g_packed.stamp_src;
-    e.stamp_period = g_packed.rows_c;
-    e.stamp_row = g_packed.n_ctx;
+E with_loss_stamp(const PackedSpec& pk, E e) {
+  if (pk.stamp_src != nullptr) {
+    e.stamp_src = pk.stamp_src;
+    e.stamp_period = pk.rows_c;
+    e.stamp_row = pk.n_ctx;
   }
   return e;
 }
 
-// loss_sum[0] = g_loss_scale * sum of the row losses, for every launch built on this thread while a LossScaleScope is alive
-// (dprhot_train_step_*: the mean of dpr_task.py:212 leaves the kernel ready, no separate division launch)
-thread_local float g_loss_scale = 1.0f;
-struct LossScaleScope {
-  explicit LossScaleScope(float s) { g_loss_scale = s; }
-  ~LossScaleScope() { g_loss_scale = 1.0f; }
-};
-// The one-call training step may carry the sum of the row losses into the launch that combines its dQ slabs (splitk_reduce_loss_kernel):
-// `armed` while its forward runs, `pending` from the forward's skipped launch until launch_dq (or the step's own fall-back) consumes it.
+// The one-call training step may carry the sum of the row losses into the launch that combines its dQ slabs (splitk_reduce_loss_kernel): the
+// record is a local of inbatch_step_body, `armed` while its forward runs, `pending` from launch_loss_sum's skipped launch until launch_slab_sum
+// (or the step's own fall-back) consumes it.
 struct LossDefer { bool armed = false, pending = false; const float* src = nullptr; int n = 0; float scale = 1.f; float* out = nullptr; };
-thread_local LossDefer g_loss_defer;
 
-// dC_part as bf16 (the reduce-scatter's wire format written by the dC epilogue): set by dprhot_train_step_* for the plans that have
-// such an epilogue (the skinny step); every other plan refuses while it is set
-thread_local bool g_dc_bf16 = false;
-struct DcKindScope {
-  explicit DcKindScope(bool bf16) { g_dc_bf16 = bf16; }
-  ~DcKindScope() { g_dc_bf16 = false; }
-};
-
-// split-K partial sums of dQ left in a caller buffer (dprhot_train_step_*: the operator's backward launch adds them up): while set,
-// the skinny step writes its slabs there and skips its reduction launch
-thread_local float* g_dq_part = nullptr;
-struct DqPartScope {
-  explicit DqPartScope(float* p) { g_dq_part = p; }
-  ~DqPartScope() { g_dq_part = nullptr; }
+// What a call of the training-step family carries besides its public arguments, passed down explicitly; the default value is a plain call.
+struct StepCtx {
+  PackedSpec packed;
+  float loss_scale = 1.0f;   // loss_sum[0] = loss_scale * sum of the row losses (dprhot_train_step_*: the mean of dpr_task.py:212, no division launch)
+  bool dc_bf16 = false;      // dC_part as bf16, the reduce-scatter's wire format: only the few-rows step has such an epilogue (step_admit)
+  float* dq_part = nullptr;  // the few-rows step leaves its split-K dQ slabs here and skips its reduction launch (dprhot_rescale_grads adds them up)
+  LossDefer* defer = nullptr;
 };
 
 #define HIP_TRY(expr)                                                                      \
@@ -324,10 +305,11 @@ int launch_g8(const GemmArgs& a, const Epi& epi, hipStream_t st) {
   return launch<gemm8p_kernel<Epi, 0, SCHED>>(dim3((unsigned)grid), dim3(G2_THREADS), g8_lds_total, st, a, epi, nbx, nby);
 }
 // the inputs every gemm8p.h sim epilogue shares
-Epi8Base g8_base(const dprhot_bf16* Q, int B, int Nc, const int64_t* y, int64_t y_offset, const uint8_t* colmask, float inv_T, float* gold) {
+Epi8Base g8_base(const PackedSpec& pk, const dprhot_bf16* Q, int B, int Nc, const int64_t* y, int64_t y_offset, const uint8_t* colmask, float inv_T,
+                 float* gold) {
   EpiSim e{nullptr, colmask, B, Nc, inv_T, nullptr, nullptr, y, y_offset, gold, nullptr, 0};
   Epi8Base b;
-  b.sim = with_packed_mask(e);
+  b.sim = with_packed_mask(pk, e);
   b.dummy = Q;
   return b;
 }
@@ -615,11 +597,11 @@ SkFused sk_fused_plan(const SkPlan& sk, int nts, int nk, int B, int Nc, int d) {
 struct FwdPlan { bool short_rows; int tile, splits, kchunk, nt, tpr, cpt, threads, blocks; };
 FwdPlan fwd_plan(int B, int Nc, int d);
 
-// workspace carve-up (all offsets 256-byte aligned)
+// workspace carve-up (all offsets 256-byte aligned); fp and sk are the shape's fwd_plan and sk_plan
 struct WsLayout {
   size_t header, gold, lse, rloss, part_m, part_s, logits, dq_part, total;
 };
-WsLayout ws_layout(int B, int Nc, int d) {
+WsLayout ws_layout(int B, int Nc, int d, const FwdPlan& fp, const SkPlan& sk) {
   WsLayout w;
   const size_t ntmax = (size_t)cdiv(Nc, 32);
   size_t off = 0;
@@ -630,13 +612,12 @@ WsLayout ws_layout(int B, int Nc, int d) {
   w.part_m = off; off += align256((size_t)B * ntmax * 4);
   w.part_s = off; off += align256((size_t)B * ntmax * 4);
   {
-    const FwdPlan fp = fwd_plan(B, Nc, d);  // short rows: split-K slabs of partial logits (4, or up to 32 for wide vectors)
+    // short rows: split-K slabs of partial logits (4, or up to 32 for wide vectors)
     const size_t slabs = (Nc <= 4096 && (B <= 64 || fp.short_rows)) ? (size_t)(fp.short_rows && fp.splits > 4 ? fp.splits : 4) : 1;
     // no-logits shapes: the forward never stores S (a caller who wants the logits passes S_out)
     w.logits = off; off += nl_ok(B, Nc, d) ? 0 : align256((size_t)B * Nc * 4 * slabs);
   }
   const DqPlan p = dq_plan(B, Nc, d);
-  const SkPlan sk = sk_plan(B, Nc, d);
   int slabs = sk.ok && sk.nslices > p.splits ? sk.nslices : p.splits;
   {
     const Pair128Plan pp = pair128_plan(B, Nc, d);
@@ -742,11 +723,63 @@ int launch_sim_small(bool b_f32, const GemmArgs& a, const EpiSim& epi, int split
                : launch<sim_small_kernel<false, SS_PATCH>>(grid, block, lds, st, wpg, a, epi);
 }
 
-// the loss launch of the no-logits forward -- or, inside the one-call step, a note for launch_dq
-int launch_loss_sum(const float* src, int n, float scale, float* out, hipStream_t st) {
-  if (g_loss_defer.armed) {
-    g_loss_defer.pending = true;
-    g_loss_defer.src = src; g_loss_defer.n = n; g_loss_defer.scale = scale; g_loss_defer.out = out;
+// the latency-bound shapes of the one-call step (step_small.h)
+bool small_step_ok(int B, int Nc, int d, const FwdPlan& fp) {
+  // two row blocks (32 < B <= 64) up to 256 columns only -- measured (scratch/rb_probe.py, two launches against three): 64 x 256 x 768
+  // 13.3 against 16.2 us, 64 x 128 x 1024 13.5 / 14.0, but 64 x 512 18.6 / 17.5 and 64 x 768 24.0 / 22.8: every workgroup repeats
+  // BOTH blocks' softmax, and beyond 256 columns that second helping costs more than the launch it saves
+  return !opt(OPT_NO_SMALL_STEP) && B <= SS_MAXB && Nc <= (B <= SS_ROWS ? SS_MAXNC : 256) && d % 16 == 0 && fp.short_rows && fp.splits <= 4 &&
+         !unfused_bwd();
+}
+
+// The plan of one shape, derived once per call: what dprhot_inbatch_step_f32 runs there; every entry point of the family, the host queries
+// (dprhot_step_wants_g, dprhot_train_dq_slabs, dprhot_fwd_one_pass, dprhot_fwd_no_logits) and step_admit read their answers from it.
+enum StepFamily { FAM_FEW_ROWS, FAM_SMALL_STEP, FAM_GENERAL };                                   // sk_step / step_small / forward + backward
+enum FwdKind { FWD_ONE_PASS_128, FWD_ONE_PASS_256, FWD_NO_LOGITS, FWD_SHORT_ROWS, FWD_TILED };  // the general family's forward
+struct StepPlan {
+  StepFamily family;
+  bool nl, nl128;  // nl_ok, nl128_ok
+  FwdPlan fp;
+  SkPlan sk;
+  SkFused fz;  // judged on the plain column tiling: the packed layout's remapped tiles are never more and their slices never longer
+  WsLayout wl;
+  FwdKind fwd(bool logits, bool g) const {  // the forward of a call that wants the logits stored / the dScores
+    if (!logits && g && nl128) return FWD_ONE_PASS_128;
+    if (!logits && g && nl && opt(OPT_NL_P16) != 0) return FWD_ONE_PASS_256;
+    if (!logits && nl) return FWD_NO_LOGITS;
+    return fp.short_rows ? FWD_SHORT_ROWS : FWD_TILED;
+  }
+  // split-K slabs of dQ the step can leave to its caller: the few-rows plan's, unless it runs without the dScores (slice-normalised slabs
+  // need the row statistics to be combined: the step's own finishing launch)
+  int dq_slabs() const { return sk.ok && sk.nslices > 1 && !fz.ok ? sk.nslices : 0; }
+};
+StepPlan step_plan(int B, int Nc, int d) {
+  StepPlan p;
+  p.fp = fwd_plan(B, Nc, d);
+  p.sk = sk_plan(B, Nc, d);
+  p.fz = sk_fused_plan(p.sk, cdiv(Nc, SK_COLS), cdiv(Nc, 64), B, Nc, d);
+  p.family = p.sk.ok ? FAM_FEW_ROWS : (small_step_ok(B, Nc, d, p.fp) ? FAM_SMALL_STEP : FAM_GENERAL);
+  p.nl = nl_ok(B, Nc, d);
+  p.nl128 = nl128_ok(B, Nc, d);
+  p.wl = ws_layout(B, Nc, d, p.fp, p.sk);
+  return p;
+}
+
+// the workspace of an entry point of the family (needed: this call's plan touches it; align: the entry point insists on 16-byte alignment)
+int claim_ws(const char* who, const WsLayout& wl, void* workspace, size_t workspace_bytes, bool needed, bool align, char** ws) {
+  *ws = static_cast<char*>(workspace);
+  if (!needed) return DPRHOT_OK;
+  if (workspace == nullptr || workspace_bytes < wl.total)
+    return fail(DPRHOT_E_WORKSPACE, "%s needs %zu workspace bytes, got %zu", who, wl.total, workspace_bytes);
+  REQUIRE(!align || aligned16(workspace), "workspace must be 16-byte aligned");
+  return DPRHOT_OK;
+}
+
+// the loss launch of the no-logits forward -- or, inside the one-call step, a note for launch_slab_sum
+int launch_loss_sum(const float* src, int n, float scale, float* out, hipStream_t st, LossDefer* defer) {
+  if (defer != nullptr && defer->armed) {
+    defer->pending = true;
+    defer->src = src; defer->n = n; defer->scale = scale; defer->out = out;
     return DPRHOT_OK;
   }
   return launch<reduce_sum_kernel>(dim3(1), dim3(256), 0, st, src, n, scale, out);
@@ -761,20 +794,20 @@ int launch_lse_p2g(const float* part_m, const float* part_s, int npart, int B, i
 }
 
 // dQ = scale * (slab 0 + slab 1 + ...), in slab order; inside the one-call step the same launch also forms the loss sum (launch_loss_sum)
-int launch_slab_sum(const float* part, int splits, int B, int d, float h_scale, const float* d_scale, float* dQ, hipStream_t st) {
+int launch_slab_sum(const float* part, int splits, int B, int d, float h_scale, const float* d_scale, float* dQ, hipStream_t st, LossDefer* defer) {
   const size_t n4 = (size_t)B * d / 4;
   const int blocks = (int)((n4 + 255) / 256 > 1024 ? 1024 : (n4 + 255) / 256);
-  if (g_loss_defer.pending) {
-    g_loss_defer.pending = false;
-    return launch<splitk_reduce_loss_kernel>(dim3(blocks + 1), dim3(256), 0, st, part, splits, n4, h_scale, d_scale, dQ, g_loss_defer.src,
-                                             g_loss_defer.n, g_loss_defer.scale, g_loss_defer.out);
+  if (defer != nullptr && defer->pending) {
+    defer->pending = false;
+    return launch<splitk_reduce_loss_kernel>(dim3(blocks + 1), dim3(256), 0, st, part, splits, n4, h_scale, d_scale, dQ, defer->src, defer->n,
+                                             defer->scale, defer->out);
   }
   return launch<splitk_reduce_kernel>(dim3(blocks), dim3(256), 0, st, part, splits, n4, h_scale, d_scale, dQ);
 }
 
-int launch_dq(const dprhot_bf16* G, const dprhot_bf16* C, int B, int Nc, int d, float h_scale, const float* d_scale, float* dQ,
-              char* ws, const WsLayout& wl, hipStream_t st, bool gemm_too) {
-  DqPlan p = dq_plan(B, Nc, d);
+// dQ = G x C on the plan p (dq_plan): the split-K GEMM (gemm_too) and the sum of its slabs
+int launch_dq(DqPlan p, const dprhot_bf16* G, const dprhot_bf16* C, int B, int Nc, int d, float h_scale, const float* d_scale, float* dQ,
+              char* ws, const WsLayout& wl, hipStream_t st, bool gemm_too, LossDefer* defer) {
   if (p.big) p.tile = 0;  // stand-alone dQ (dprhot_dq): same K slices on the 128x128 tile
   if (gemm_too) {
     GemmArgs a{G, C, B, d, Nc, Nc, d, p.kchunk};
@@ -785,7 +818,7 @@ int launch_dq(const dprhot_bf16* G, const dprhot_bf16* C, int B, int Nc, int d, 
     EpiScaleF32 epi{reinterpret_cast<float*>(ws + wl.dq_part), B, d, 1.0f, nullptr};
     if (int rc = launch_gemm<true, false>(p.tile, a, epi, p.splits, st)) return rc;
   }
-  if (p.splits > 1) return launch_slab_sum(reinterpret_cast<const float*>(ws + wl.dq_part), p.splits, B, d, h_scale, d_scale, dQ, st);
+  if (p.splits > 1) return launch_slab_sum(reinterpret_cast<const float*>(ws + wl.dq_part), p.splits, B, d, h_scale, d_scale, dQ, st, defer);
   return DPRHOT_OK;
 }
 
@@ -819,20 +852,21 @@ int launch_sk_dq_reduce(const float* part, int nslices, int B, int d, float h_sc
   return launch<sk_dq_reduce_kernel>(dim3((unsigned)((n4 + 63) / 64)), dim3(256), 0, st, part, nslices, n4, h_scale, d_scale, dQ);
 }
 
-int sk_step(const float* q, const dprhot_bf16* Cb, dprhot_bf16* Qb, int B, int Nc, int d, const int64_t* y, int64_t y_offset,
+int sk_step(const StepCtx& cx, const float* q, const dprhot_bf16* Cb, dprhot_bf16* Qb, int B, int Nc, int d, const int64_t* y, int64_t y_offset,
             const uint8_t* colmask, float inv_T, float grad_scale, float h_scale, const float* d_scale, float* S_out, float* row_loss,
             float* row_lse, float* loss_sum, dprhot_bf16* G, float* dQ, float* dC_part, char* ws, const WsLayout& wl, const SkPlan& sk,
             hipStream_t st) {
+  const PackedSpec& pk = cx.packed;
   float* S = S_out ? S_out : reinterpret_cast<float*>(ws + wl.logits);
   float* tile_lse = reinterpret_cast<float*>(ws + wl.part_m);
   float* gold = reinterpret_cast<float*>(ws + wl.gold);
   // packed layout whose ranks hold a whole number of sim tiles: only the real rows are multiplied (SkSimArgs::tiles_per_rank)
-  const bool remap = g_packed.base != nullptr && g_packed.rows_c > g_packed.n_ctx && g_packed.n_ctx % sk.scols == 0 &&
-                     Nc % g_packed.rows_c == 0;
-  const int tpr = remap ? g_packed.n_ctx / sk.scols : 0;
-  const int nts = remap ? (Nc / g_packed.rows_c) * tpr : sk.nts;
-  SkSimArgs a{q, nullptr, Cb, Qb, B, Nc, d, y, y_offset, colmask, inv_T, S, tile_lse, gold, g_packed.base, g_packed.rows_c,
-              g_packed.n_ctx, g_packed.row_bytes, tpr};
+  const bool remap = pk.base != nullptr && pk.rows_c > pk.n_ctx && pk.n_ctx % sk.scols == 0 &&
+                     Nc % pk.rows_c == 0;
+  const int tpr = remap ? pk.n_ctx / sk.scols : 0;
+  const int nts = remap ? (Nc / pk.rows_c) * tpr : sk.nts;
+  SkSimArgs a{q, nullptr, Cb, Qb, B, Nc, d, y, y_offset, colmask, inv_T, S, tile_lse, gold, pk.base, pk.rows_c,
+              pk.n_ctx, pk.row_bytes, tpr};
   // G == NULL (nobody wants the dScores): three launches -- the sim launch leaves the tile-local softmax in the logit workspace
   const int nk_f = remap ? 2 * nts : cdiv(Nc, 64);
   const SkFused fz = sk_fused_plan(sk, nts, nk_f, B, Nc, d);
@@ -867,11 +901,11 @@ int sk_step(const float* q, const dprhot_bf16* Cb, dprhot_bf16* Qb, int B, int N
   }
   if (rc) return rc;
   if (fused) {
-    if (g_dq_part != nullptr) return fail(DPRHOT_E_INVALID, "few-rows step without dScores: dQ is finished by the step itself (dprhot_train_dq_slabs = 0)");
+    if (cx.dq_part != nullptr) return fail(DPRHOT_E_INVALID, "few-rows step without dScores: dQ is finished by the step itself (dprhot_train_dq_slabs = 0)");
     float* part = reinterpret_cast<float*>(ws + wl.dq_part);
     const int ndq = fz.nslices * (d / SK_QN), ndq_pad = (ndq + 7) & ~7, ndc = nts * (d / SK_DN);
-    SkBwdFArgs b{a.P, Qb, Cb, B, Nc, d, tile_lse, gold, y, y_offset, nts, tpr, g_packed.rows_c, g_packed.n_ctx, grad_scale, h_scale, d_scale,
-                 dC_part, g_dc_bf16 ? 1 : 0, g_packed.stamp_src != nullptr ? g_packed.rows_c : 0, g_packed.n_ctx, loss_sum, g_loss_scale,
+    SkBwdFArgs b{a.P, Qb, Cb, B, Nc, d, tile_lse, gold, y, y_offset, nts, tpr, pk.rows_c, pk.n_ctx, grad_scale, h_scale, d_scale,
+                 dC_part, cx.dc_bf16 ? 1 : 0, pk.stamp_src != nullptr ? pk.rows_c : 0, pk.n_ctx, loss_sum, cx.loss_scale,
                  row_loss, row_lse, fz.ksteps, fz.nslices, part, dQ, ndq_pad, opt(OPT_NT_STORES) ? 1 : 0, opt(OPT_SK_DBG)};
     b.reg_scale = opt(OPT_SK_DC_REGSCALE) != 0 ? 1 : 0;
     b.dq_atomic = dq_atomic ? 1 : 0;
@@ -921,15 +955,497 @@ int sk_step(const float* q, const dprhot_bf16* Cb, dprhot_bf16* Qb, int B, int N
     if ((rc = launch<sk_g_kernel>(dim3((unsigned)(B * pp)), dim3(SK_THREADS), 0, st, g))) return rc;
   }
   {
-    float* part = g_dq_part != nullptr ? g_dq_part : reinterpret_cast<float*>(ws + wl.dq_part);
+    float* part = cx.dq_part != nullptr ? cx.dq_part : reinterpret_cast<float*>(ws + wl.dq_part);
     const int ndq = sk.nslices * (d / SK_QN), ndq_pad = (ndq + 7) & ~7, ndc = sk.nt * (d / SK_DN);
-    SkBwdArgs b{G, Qb, Cb, B, Nc, d, h_scale, d_scale, dC_part, rl, loss_sum, g_loss_scale, g_dc_bf16 ? 1 : 0,
-                g_packed.stamp_src != nullptr ? g_packed.rows_c : 0, g_packed.n_ctx, sk.ksteps, sk.nslices, part, dQ, ndq_pad, opt(OPT_NT_STORES) ? 1 : 0};
+    SkBwdArgs b{G, Qb, Cb, B, Nc, d, h_scale, d_scale, dC_part, rl, loss_sum, cx.loss_scale, cx.dc_bf16 ? 1 : 0,
+                pk.stamp_src != nullptr ? pk.rows_c : 0, pk.n_ctx, sk.ksteps, sk.nslices, part, dQ, ndq_pad, opt(OPT_NT_STORES) ? 1 : 0};
     if ((rc = launch_sk_bwd(b, ndq_pad + ndc, st))) return rc;
     // (else the caller's finishing launch forms dQ from the slabs: dprhot_rescale_grads; one slice: the dQ units stored the scaled sum themselves)
-    if (g_dq_part == nullptr && sk.nslices > 1) return launch_sk_dq_reduce(part, sk.nslices, B, d, h_scale, d_scale, dQ, st);
+    if (cx.dq_part == nullptr && sk.nslices > 1) return launch_sk_dq_reduce(part, sk.nslices, B, d, h_scale, d_scale, dQ, st);
   }
   return DPRHOT_OK;
+}
+
+// ---- the training step: the bodies of its public entry points.  A body takes the call's context (or the part it reads), the shape's plan
+// and the claimed workspace; it validates nothing and calls no member of the family through its public name ------------------------------
+
+int sim_fwd_body(const PackedSpec& pk, const dprhot_bf16* Q, int B, const dprhot_bf16* C, int Nc, int d, const uint8_t* colmask, float inv_T,
+                 float* S, hipStream_t st) {
+  if (g8_ok(B, Nc, d) && !opt(OPT_NO_8P_STORE)) {
+    // large score matrices (validation with the logits wanted, the head chunk of a retrieval): the phase-interleaved kernel with
+    // the store epilogue that writes whole rows (Epi8Store); the round-1 256 x 256 kernel stays behind the option
+    Epi8Store epi;
+    static_cast<Epi8Base&>(epi) = g8_base(pk, Q, B, Nc, nullptr, 0, colmask, inv_T, nullptr);
+    epi.S = S;
+    GemmArgs a8{Q, C, B, Nc, d, d, d, d};
+    return launch_g8<Epi8Store, 2>(a8, epi, st);
+  }
+  const int tile = (force_tile() < 0 && big_ok(B, Nc, d)) ? kBigTile : pick_tile(B, Nc, d, 1, 2 * kNumCU);
+  GemmArgs a{Q, C, B, Nc, d, d, d, cdiv(d, kTiles[tile].bk) * kTiles[tile].bk};
+  EpiSim epi{S, colmask, B, Nc, inv_T, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0};
+  epi = with_packed_mask(pk, epi);
+  return launch_gemm<true, true>(tile, a, epi, 1, st);
+}
+
+int dc_body(const PackedSpec& pk, const dprhot_bf16* G, const dprhot_bf16* Q, int B, int Nc, int d, float h_scale, const float* d_scale,
+            float* dC_part, hipStream_t st) {
+  // A(m = ctx column, k = query row) = G[k][m]  (mn-major, lda = Nc);  B(k, n) = Q[k][n]  (mn-major, ldb = d)
+  GemmArgs a{G, Q, Nc, d, B, Nc, d, cdiv(B, 64) * 64};
+  const EpiScaleF32 epi = with_loss_stamp(pk, EpiScaleF32{dC_part, Nc, d, h_scale, d_scale});
+  const int tile = force_tile() >= 0 && force_tile() <= 3 ? force_tile() : dc_tile(B, Nc, d);
+  return launch_gemm<false, false>(tile, a, epi, 1, st);
+}
+
+// bf16 copies of the fp32 operands in one launch (c == NULL: the contexts are bf16 already)
+int cast_operands(const float* q, const float* c, dprhot_bf16* Qb, dprhot_bf16* Cb, int B, int Nc, int d, hipStream_t st) {
+  return c != nullptr ? dprhot_prep(q, (size_t)B * d, Qb, c, (size_t)Nc * d, Cb, st) : dprhot_cast_bf16(q, Qb, (size_t)B * d, st);
+}
+
+// launch 1 of the fused forward: logits + per-tile softmax statistics + gold logit (and clears the loss
+// accumulator words the next launch adds into)
+int sim_stats_body(const PackedSpec& pk, const dprhot_bf16* Q, int B, const dprhot_bf16* C, int Nc, int d, const int64_t* y, int64_t y_offset,
+                   const uint8_t* colmask, float inv_T, float* S_out, const StepPlan& p, char* ws, hipStream_t st) {
+  const WsLayout& wl = p.wl;
+  if (S_out == nullptr && p.nl) {
+    // no-logits plan: strip statistics + gold logit only; softmax_finish_body turns them into logsumexp / loss and
+    // dscores_body recomputes the logits into G
+    Epi8Stats epi;
+    static_cast<Epi8Base&>(epi) = g8_base(pk, Q, B, Nc, y, y_offset, colmask, inv_T, reinterpret_cast<float*>(ws + wl.gold));
+    epi.part_m = reinterpret_cast<float*>(ws + wl.part_m);
+    epi.part_s = reinterpret_cast<float*>(ws + wl.part_s);
+    epi.npart = cdiv(Nc, G2_B) * 4;
+    GemmArgs a8{Q, C, B, Nc, d, d, d, d};
+    return launch_g8(a8, epi, st);
+  }
+  const FwdPlan& fp = p.fp;
+  GemmArgs a{Q, C, B, Nc, d, d, d, fp.kchunk};
+  if (fp.short_rows) {  // partial logits per K split; the softmax launch sums them (and fills S_out if asked)
+    EpiSim epi{reinterpret_cast<float*>(ws + wl.logits), colmask, B, Nc, inv_T, nullptr, nullptr, nullptr, 0, nullptr,
+               reinterpret_cast<unsigned long long*>(ws + wl.header), 2, (size_t)B * Nc};
+    epi = with_packed_mask(pk, epi);
+    return launch_gemm<true, true>(fp.tile, a, epi, fp.splits, st);
+  }
+  float* S = S_out ? S_out : reinterpret_cast<float*>(ws + wl.logits);
+  EpiSim epi{S, colmask, B, Nc, inv_T, reinterpret_cast<float*>(ws + wl.part_m), reinterpret_cast<float*>(ws + wl.part_s),
+             y, y_offset, reinterpret_cast<float*>(ws + wl.gold), reinterpret_cast<unsigned long long*>(ws + wl.header), 2};
+  epi = with_packed_mask(pk, epi);
+  return launch_gemm<true, true>(fp.tile, a, epi, 1, st);
+}
+
+// launch 1 with fp32 operands: q [B,d] fp32 always; c [Nc,d] fp32 when non-NULL (single rank: no gather), else
+// Cb is the (gathered) bf16 input.  Qb (and Cb when c is given) receive the bf16 copies the backward reads.
+int sim_stats_f32_body(const PackedSpec& pk, const float* q, const float* c, dprhot_bf16* Qb, dprhot_bf16* Cb, int B, int Nc, int d, const int64_t* y,
+                       int64_t y_offset, const uint8_t* colmask, float inv_T, float* S_out, const StepPlan& p, char* ws, hipStream_t st) {
+  const WsLayout& wl = p.wl;
+  if (B > 128) {
+    // Beyond the latency-bound sizes reading fp32 operands in the GEMM costs more than it saves (twice the staging
+    // registers and bytes per tile, measured 250 vs 580 TFLOP/s at 8192^2): cast once, then the bf16 kernels.
+    if (int rc = cast_operands(q, c, Qb, Cb, B, Nc, d, st)) return rc;
+    return sim_stats_body(pk, Qb, B, Cb, Nc, d, y, y_offset, colmask, inv_T, S_out, p, ws, st);
+  }
+  const FwdPlan& fp = p.fp;
+  GemmArgs a{reinterpret_cast<const uint16_t*>(q), c ? reinterpret_cast<const uint16_t*>(c) : Cb, B, Nc, d, d, d, fp.kchunk};
+  a.Acopy = Qb;
+  a.Bcopy = c ? Cb : nullptr;
+  if (fp.short_rows) {
+    if (c != nullptr && wide_sim_ok(B, Nc, d, fp) && pk.base == nullptr) {
+      // vocabulary-wide fp32 operands: LDS-DMA ring of fp32 tiles, bf16 rounding on the fragment read (wide.h)
+      WideSimArgs wa{q, c, Qb, Cb, B, Nc, d, colmask, inv_T, reinterpret_cast<float*>(ws + wl.logits), (size_t)B * Nc, fp.kchunk,
+                     reinterpret_cast<unsigned long long*>(ws + wl.header), 2, opt(OPT_WIDE_NOCOPY), cdiv(Nc, WD_B), cdiv(B, WD_B)};
+      return launch<wide_sim_kernel>(dim3((unsigned)(wa.nbx * wa.nby * fp.splits)), dim3(WD_THREADS), wd_lds_bytes, st, wa);
+    }
+    EpiSim epi{reinterpret_cast<float*>(ws + wl.logits), colmask, B, Nc, inv_T, nullptr, nullptr, nullptr, 0, nullptr,
+               reinterpret_cast<unsigned long long*>(ws + wl.header), 2, (size_t)B * Nc};
+    epi = with_packed_mask(pk, epi);
+    if (small_sim_ok(B, Nc, d, fp)) return launch_sim_small(c != nullptr, a, epi, fp.splits, st);
+    return c ? launch_sim_f32<true, true>(fp.tile, a, epi, fp.splits, st) : launch_sim_f32<true, false>(fp.tile, a, epi, fp.splits, st);
+  }
+  float* S = S_out ? S_out : reinterpret_cast<float*>(ws + wl.logits);
+  EpiSim epi{S, colmask, B, Nc, inv_T, reinterpret_cast<float*>(ws + wl.part_m), reinterpret_cast<float*>(ws + wl.part_s),
+             y, y_offset, reinterpret_cast<float*>(ws + wl.gold), reinterpret_cast<unsigned long long*>(ws + wl.header), 2};
+  epi = with_packed_mask(pk, epi);
+  return c ? launch_sim_f32<true, true>(fp.tile, a, epi, 1, st) : launch_sim_f32<true, false>(fp.tile, a, epi, 1, st);
+}
+
+// launch 2 of the fused forward: logsumexp from the statistics, G in one pass over S, loss numerator
+int softmax_finish_body(const StepCtx& cx, const float* S_in, int B, int Nc, int d, const int64_t* y, int64_t y_offset, float grad_scale,
+                        float* row_loss, float* row_lse, float* loss_sum, dprhot_bf16* G, const StepPlan& p, char* ws, hipStream_t st) {
+  const WsLayout& wl = p.wl;
+  if (S_in == nullptr && p.nl) {
+    // no-logits plan (same test as sim_stats_body): logsumexp and loss from the strip statistics; there are no logits to turn
+    // into G here -- dscores_body recomputes them
+    if (int rc = launch<g8_lse_kernel>(dim3(cdiv(B, 4)), dim3(256), 0, st, reinterpret_cast<const float*>(ws + wl.part_m),
+                                       reinterpret_cast<const float*>(ws + wl.part_s), cdiv(Nc, G2_B) * 4, reinterpret_cast<const float*>(ws + wl.gold), B,
+                                       reinterpret_cast<float*>(ws + wl.lse), row_lse, row_loss, reinterpret_cast<float*>(ws + wl.rloss)))
+      return rc;
+    return launch_loss_sum(reinterpret_cast<const float*>(ws + wl.rloss), B, cx.loss_scale, loss_sum, st, cx.defer);
+  }
+  const FwdPlan& fp = p.fp;  // same plan as sim_stats_body -> same intermediate layout
+  if (fp.short_rows) {
+    // S_in, when given, is where the caller wants the summed logits (the slabs always live in the workspace)
+    GShortArgs g{reinterpret_cast<const float*>(ws + wl.logits), fp.splits, (size_t)B * Nc, B, Nc, y, y_offset, grad_scale,
+                 const_cast<float*>(S_in), row_loss, row_lse, G, reinterpret_cast<unsigned long long*>(ws + wl.header), loss_sum, fp.tpr, cx.loss_scale};
+    if (fp.blocks > 65535) return fail(DPRHOT_E_UNSUPPORTED, "softmax_finish: B=%d rows need %d workgroups (max 65535)", B, fp.blocks);
+    if (fp.cpt == 1) return launch<gfinal_short_kernel<1>>(dim3(fp.blocks), dim3(fp.threads), 0, st, g);
+    return launch<gfinal_short_kernel<2>>(dim3(fp.blocks), dim3(fp.threads), 0, st, g);
+  }
+  const float* S = S_in ? S_in : reinterpret_cast<const float*>(ws + wl.logits);
+  const int nt = fp.nt;
+  if (nt > kGfMaxPairs) return fail(DPRHOT_E_UNSUPPORTED, "Nc=%d too long for the statistics buffer (%d column tiles)", Nc, nt);
+  GFinalArgs g{S, B, Nc, y, y_offset, grad_scale, reinterpret_cast<const float*>(ws + wl.part_m),
+               reinterpret_cast<const float*>(ws + wl.part_s), nt, reinterpret_cast<const float*>(ws + wl.gold), row_loss, row_lse,
+               G, reinterpret_cast<unsigned long long*>(ws + wl.header), loss_sum, cx.loss_scale};
+  const bool thin = (long)B * (Nc / 8) <= 1L << 18;  // latency-bound sizes: one chunk per thread, many small workgroups
+  int rpb, xblocks;
+  gfinal_geometry(Nc, thin ? 1 : 8, &rpb, &xblocks);
+  if (cdiv(B, rpb) > 65535)  // grid.y limit, and the arrival ticket of the loss accumulation is 16 bits wide
+    return fail(DPRHOT_E_UNSUPPORTED, "softmax_finish: B=%d rows need %d row blocks (max 65535)", B, cdiv(B, rpb));
+  dim3 grid(xblocks, cdiv(B, rpb));
+  if (thin) return launch<gfinal_kernel<1>>(grid, dim3(256), 0, st, g);
+  return launch<gfinal_kernel<8>>(grid, dim3(256), 0, st, g);
+}
+
+// dScores of the no-logits forward: G = (softmax(S) - onehot) * grad_scale with S recomputed tile by tile (the same GEMM as
+// sim_stats_body, bit-identical accumulators) from the rows' logsumexp
+int dscores_body(const PackedSpec& pk, const dprhot_bf16* Q, int B, const dprhot_bf16* C, int Nc, int d, const int64_t* y, int64_t y_offset,
+                 const uint8_t* colmask, float inv_T, float grad_scale, const float* row_lse, dprhot_bf16* G, hipStream_t st) {
+  Epi8G epi;
+  static_cast<Epi8Base&>(epi) = g8_base(pk, Q, B, Nc, y, y_offset, colmask, inv_T, nullptr);
+  epi.row_lse = row_lse;
+  epi.G = G;
+  epi.grad_scale = grad_scale;
+  GemmArgs a8{Q, C, B, Nc, d, d, d, d};
+  return launch_g8<Epi8G, 2>(a8, epi, st);
+}
+
+int inbatch_fwd_body(const StepCtx& cx, const dprhot_bf16* Q, int B, const dprhot_bf16* C, int Nc, int d, const int64_t* y, int64_t y_offset,
+                     const uint8_t* colmask, float inv_T, float grad_scale, float* S_out, float* row_loss, float* row_lse, float* loss_sum,
+                     dprhot_bf16* G, const StepPlan& p, char* ws, hipStream_t st) {
+  const WsLayout& wl = p.wl;
+  const FwdKind kind = p.fwd(S_out != nullptr, G != nullptr);
+  if (kind == FWD_ONE_PASS_128 || kind == FWD_ONE_PASS_256) {
+    // ONE pass of the GEMM (round 6): strip statistics + fp16 softmax numerators into the G buffer, then one row kernel: logsumexp / loss,
+    // and the numerators rescaled into the bf16 dScores in place
+    float *part_m = reinterpret_cast<float*>(ws + wl.part_m), *part_s = reinterpret_cast<float*>(ws + wl.part_s), *gold = reinterpret_cast<float*>(ws + wl.gold);
+    const int npart = kind == FWD_ONE_PASS_128 ? cdiv(Nc, 64) : cdiv(Nc, G2_B) * 4;
+    GemmArgs a{Q, C, B, Nc, d, d, d, d};
+    if (kind == FWD_ONE_PASS_128) {
+      // on the 128 x 128 LDS-DMA tile (EpiSimP): the shapes whose 256-wide tiles cannot fill the chip
+      EpiSimP epi;
+      static_cast<EpiSim&>(epi) = with_packed_mask(cx.packed, EpiSim{nullptr, colmask, B, Nc, inv_T, part_m, part_s, y, y_offset, gold, nullptr, 0});
+      epi.P = G;
+      epi.npart = npart;
+      if (int rc = launch<gemm128d_kernel<true, true, EpiSimP, false>>(dim3(cdiv(Nc, 128), cdiv(B, 128), 1), dim3(256), g1_lds_bytes, st, a, epi)) return rc;
+    } else {
+      // on the 256 x 256 tile of the no-logits forward (Epi8StatsP)
+      Epi8StatsP epi;
+      static_cast<Epi8Base&>(epi) = g8_base(cx.packed, Q, B, Nc, y, y_offset, colmask, inv_T, gold);
+      epi.part_m = part_m;
+      epi.part_s = part_s;
+      epi.npart = npart;
+      epi.P = G;
+      if (opt(OPT_P16_STAGED) == 2 || (opt(OPT_P16_STAGED) == 1 && ((size_t)Nc * 2) % ((size_t)128 << 10) != 0)) {
+        Epi8StatsPS es;
+        static_cast<Epi8Stats&>(es) = static_cast<const Epi8Stats&>(epi);
+        es.P = G;
+        if (int rc = launch_g8<Epi8StatsPS, 2>(a, es, st)) return rc;
+      } else if (int rc = launch_g8<Epi8StatsP, 2>(a, epi, st)) return rc;  // (two-phase schedule, as every storing epilogue; the four-phase instantiation spilled two registers)
+    }
+    if (int rc = launch_lse_p2g(part_m, part_s, npart, B, Nc, y, y_offset, grad_scale, row_lse, row_loss, G, ws, wl, st)) return rc;
+    return launch_loss_sum(reinterpret_cast<const float*>(ws + wl.rloss), B, cx.loss_scale, loss_sum, st, cx.defer);
+  }
+  // no-logits forward: statistics pass -> logsumexp / loss -> dScores pass (logits recomputed), S is never in memory; elsewhere the
+  // softmax launch reads the stored logits and writes G itself
+  const bool recompute = kind == FWD_NO_LOGITS;
+  if (int rc = sim_stats_body(cx.packed, Q, B, C, Nc, d, y, y_offset, colmask, inv_T, S_out, p, ws, st)) return rc;
+  if (int rc = softmax_finish_body(cx, S_out, B, Nc, d, y, y_offset, grad_scale, row_loss, row_lse, loss_sum, recompute ? nullptr : G, p, ws, st))
+    return rc;
+  if (!recompute || G == nullptr) return DPRHOT_OK;
+  return dscores_body(cx.packed, Q, B, C, Nc, d, y, y_offset, colmask, inv_T, grad_scale, reinterpret_cast<const float*>(ws + wl.lse), G, st);
+}
+
+int inbatch_fwd_f32_body(const StepCtx& cx, const float* q, const float* c, dprhot_bf16* Qb, dprhot_bf16* Cb, int B, int Nc, int d, const int64_t* y,
+                         int64_t y_offset, const uint8_t* colmask, float inv_T, float grad_scale, float* S_out, float* row_loss, float* row_lse,
+                         float* loss_sum, dprhot_bf16* G, const StepPlan& p, char* ws, hipStream_t st) {
+  if (S_out == nullptr && B > 128 && (p.nl || (G != nullptr && p.nl128))) {  // cast once, then the no-logits forward on the bf16 copies
+    if (int rc = cast_operands(q, c, Qb, Cb, B, Nc, d, st)) return rc;
+    return inbatch_fwd_body(cx, Qb, B, Cb, Nc, d, y, y_offset, colmask, inv_T, grad_scale, nullptr, row_loss, row_lse, loss_sum, G, p, ws, st);
+  }
+  if (int rc = sim_stats_f32_body(cx.packed, q, c, Qb, Cb, B, Nc, d, y, y_offset, colmask, inv_T, S_out, p, ws, st)) return rc;
+  return softmax_finish_body(cx, S_out, B, Nc, d, y, y_offset, grad_scale, row_loss, row_lse, loss_sum, G, p, ws, st);
+}
+
+// The backward's plan: which launches form dC_part and dQ, and how many split-K slabs of dQ pass through the workspace (above one).
+// both: dQ and dC_part are wanted; stamp: the packed step's dC epilogue stamps the loss, which the units of skinny.h cannot.
+enum BwdKind { BWD_APART, BWD_FEW_ROWS, BWD_WIDE, BWD_PAIR128, BWD_PAIR256, BWD_PAIR };
+struct BwdPlan { BwdKind kind; int slabs; DqPlan dq; Pair128Plan pp; };
+BwdPlan bwd_plan(int B, int Nc, int d, const SkPlan& sk, bool both, bool stamp) {
+  BwdPlan b{};
+  b.dq = dq_plan(B, Nc, d);
+  b.slabs = b.dq.splits;
+  // (the long context axis under fewer than 512 rows: both GEMMs on the 128 x 128 engine -- see `long_axis` below; 256 x 65536 x 768:
+  //  146 us against 174 with the dQ units on the 256 x 256 kernel and 252 for the pair)
+  // (round 6, with the LDS-DMA 128 x 128 tile: also 512 <= B < 1024 from Nc >= 32 B on -- 512 x 16384 56 against 65 us with the dQ units on
+  //  the 256 x 256 kernel and 73 for the pair, 512 x 32768 90 / 100 / 116: profiles/r06_bwd_plan_ab.txt)
+  const bool long_axis_small = ((B < 512 && Nc >= 56 * 1024) || (B >= 512 && B < 1024 && (long)Nc >= 32L * B)) && !sk.ok &&
+                               !wide_bwd_ok(B, Nc, d) && big_bwd_ok(B, Nc, d) && !pair128_use(B, Nc, d);
+  b.kind = b.dq.big ? BWD_PAIR256 : BWD_PAIR;
+  if (!both || unfused_bwd() || force_tile() >= 0 || long_axis_small) b.kind = BWD_APART;  // dC and dQ in launches of their own
+  else if (!stamp && sk.ok) b.kind = BWD_FEW_ROWS, b.slabs = sk.nslices;
+  else if (!stamp && wide_bwd_ok(B, Nc, d)) b.kind = BWD_WIDE, b.slabs = 1;
+  else if (pair128_use(B, Nc, d)) b.kind = BWD_PAIR128, b.pp = pair128_plan(B, Nc, d), b.slabs = b.pp.splits;
+  return b;
+}
+
+int inbatch_bwd_body(const StepCtx& cx, const BwdPlan& bp, const dprhot_bf16* G, const dprhot_bf16* Q, const dprhot_bf16* C, int B, int Nc, int d,
+                     float h_scale, const float* d_scale, float* dQ, float* dC_part, const StepPlan& sp, char* ws, hipStream_t st) {
+  const WsLayout& wl = sp.wl;
+  if (bp.kind == BWD_APART) {
+    if (dC_part != nullptr)
+      if (int rc = dc_body(cx.packed, G, Q, B, Nc, d, h_scale, d_scale, dC_part, st)) return rc;
+    if (dQ != nullptr) return launch_dq(bp.dq, G, C, B, Nc, d, h_scale, d_scale, dQ, ws, wl, st, /*gemm_too=*/true, cx.defer);
+    return DPRHOT_OK;
+  }
+  if (bp.kind == BWD_FEW_ROWS) {
+    // Shapes of the few-rows plan: the same backward units as the one-call step (dC tiles and split-K dQ tiles side by side, then the
+    // slab reduction) for callers that run sim / loss / backward as separate calls (a subclass's own loss on sim_score's logits):
+    // 128 x 8192 x 768 23 -> ~15 us against the generic pair kernel.
+    const SkPlan& sk = sp.sk;
+    float* part = sk.nslices > 1 ? reinterpret_cast<float*>(ws + wl.dq_part) : nullptr;
+    const int ndq = sk.nslices * (d / SK_QN), ndq_pad = (ndq + 7) & ~7, ndc = sk.nt * (d / SK_DN);
+    SkBwdArgs b{G, Q, C, B, Nc, d, h_scale, d_scale, dC_part, nullptr, nullptr, 1.0f, 0, 0, 0, sk.ksteps, sk.nslices, part, dQ, ndq_pad,
+                opt(OPT_NT_STORES) ? 1 : 0};
+    if (int rc = launch_sk_bwd(b, ndq_pad + ndc, st)) return rc;
+    if (sk.nslices > 1) return launch_sk_dq_reduce(part, sk.nslices, B, d, h_scale, d_scale, dQ, st);
+    return DPRHOT_OK;
+  }
+  if (bp.kind == BWD_WIDE) {
+    // Vocabulary-wide vectors under few rows (CITADEL router: 128 x 1024 x 30528): every unit of either GEMM is a short K loop in front
+    // of a large store -- the unit shapes of skinny.h (whole operand footprint in flight by LDS-DMA, stores through LDS in whole
+    // lines), dC tiles and dQ tiles side by side in one launch; the contexts fit one dQ slice, so no partial sums and no reduction.
+    // The 141 MB of fp32 gradients leave with non-temporal stores: nobody re-reads them inside the step, and written normally they push
+    // the step's operands out of the 256 MB Infinity Cache (measured, scratch/router_ab.py: step 116 -> 99.5 us; the same policy on the
+    // 8192^2 launches -- stored logits, 256 x 256 backward -- LOST 5-10 % and is not used there: profiles/r03_nt_stores_ab.txt).
+    const int ksteps = cdiv(Nc, 64);
+    const int ndq = d / SK_QN, ndq_pad = (ndq + 7) & ~7, ndc = cdiv(Nc, SK_COLS) * cdiv(d, SK_DN);
+    SkBwdArgs b{G, Q, C, B, Nc, d, h_scale, d_scale, dC_part, nullptr, nullptr, 1.0f, 0, 0, 0, ksteps, 1, nullptr, dQ, ndq_pad, opt(OPT_NT_STORES) ? 1 : 0};
+    return launch_sk_bwd(b, ndq_pad + ndc, st);
+  }
+  if (bp.kind == BWD_PAIR128) {
+    // [dC tiles | dQ tiles x K slices] on the 128 x 128 LDS-DMA tile (round 6): the shapes under the 256 x 256 gate ran this pair on the
+    // register-staged tiles (2048 x 4096 x 768: 69.5 us for 26 GFLOP)
+    const Pair128Plan& pp = bp.pp;
+    GemmArgs a1{G, Q, Nc, d, B, Nc, d, B};
+    const EpiScaleF32 e1 = with_loss_stamp(cx.packed, EpiScaleF32{dC_part, Nc, d, h_scale, d_scale});
+    GemmArgs a2{G, C, B, d, Nc, Nc, d, pp.kchunk};
+    const EpiScaleF32 e2 = pp.splits == 1 ? EpiScaleF32{dQ, B, d, h_scale, d_scale}
+                                          : EpiScaleF32{reinterpret_cast<float*>(ws + wl.dq_part), B, d, 1.0f, nullptr};
+    const int nbx1 = cdiv(d, 128), nby1 = cdiv(Nc, 128), nbx2 = cdiv(d, 128), nby2 = cdiv(B, 128);
+    const long grid = (long)nbx1 * nby1 + (long)nbx2 * nby2 * pp.splits;
+    if (grid > 0x7fffffffL) return fail(DPRHOT_E_UNSUPPORTED, "grid too large");
+    if (int rc = launch<gemm128d_pair_kernel<EpiScaleF32>>(dim3((unsigned)grid), dim3(256), g1_lds_bytes, st, a1, e1, nbx1, nby1, a2, e2, nbx2, nby2, pp.splits))
+      return rc;
+    if (pp.splits > 1) return launch_slab_sum(reinterpret_cast<const float*>(ws + wl.dq_part), pp.splits, B, d, h_scale, d_scale, dQ, st, cx.defer);
+    return DPRHOT_OK;
+  }
+  const DqPlan& p = bp.dq;
+  // one launch: [dC tiles | dQ tiles x splits]
+  GemmArgs a1{G, Q, Nc, d, B, Nc, d, cdiv(B, 64) * 64};
+  const EpiScaleF32 e1 = with_loss_stamp(cx.packed, EpiScaleF32{dC_part, Nc, d, h_scale, d_scale});
+  GemmArgs a2{G, C, B, d, Nc, Nc, d, p.kchunk};
+  EpiScaleF32 e2 = p.splits == 1 ? EpiScaleF32{dQ, B, d, h_scale, d_scale}
+                                 : EpiScaleF32{reinterpret_cast<float*>(ws + wl.dq_part), B, d, 1.0f, nullptr};
+  if (bp.kind == BWD_PAIR256) {
+    // Few query rows against a long context axis (512 <= B <= 2048, Nc >= 32 B: e.g. 8192 global queries x 8 contexts seen from one
+    // of 8 ranks): the dC tiles of the pair launch are only K = B deep -- 8 to 32 K steps between a pipeline fill and a 256 KiB store
+    // -- next to dQ units several times as long (the K slices of dQ stop at 16), and the launch loses to dC on the 128 x 128 engine in a
+    // launch of its own (dc_body) followed by this launch with its dQ units only.  Measured, pair / dC apart, us (d = 768,
+    // scratch/bwd_hybrid_ab.py, profiles/r05_bwd_long_axis.txt): 1024 x 32768 181 / 154, 1024 x 49152 292 / 236, 1024 x 65536 482 / 299,
+    // 512 x 16384 73 / 70, 512 x 32768 117 / 112, 512 x 65536 356 / 202, 2048 x 65536 611 / 555, 1024 x 32768 x 1024 217 / 197; the
+    // pair stays where it wins: 1024 x 8192 43 / 71, 1024 x 16384 82 / 96, 2048 x 16384 122 / 146, 2048 x 32768 228 / 289, 512 x 8192 33 / 50.
+    const bool long_axis = B >= 512 && B <= 2048 && (long)Nc >= 32L * B;
+    const bool no8 = opt(OPT_NO_8PB) != 0;
+    // (round 6: B and Nc multiples of 64 suffice -- a unit with an odd number of K steps skips the MFMAs of its last half pair; the packed
+    //  multi-rank layout's column counts are multiples of 64, rarely of 128)
+    const bool ok8 = !no8 && B % 64 == 0 && Nc % 64 == 0 && p.kchunk % 128 == 0 && (double)B * Nc < 2.0e9 && (double)Nc * d < 2.0e9;
+    a1.kchunk = B;  // dC: one K range (B % 64 == 0)
+    // the same epilogues for the phase-interleaved kernel (gemm8pb.h)
+    const Epi8Scale s1{e1.out, e1.M, e1.N, e1.h_scale, e1.d_scale, e1.stamp_src, e1.stamp_period, e1.stamp_row};
+    const Epi8Scale s2{e2.out, e2.M, e2.N, e2.h_scale, e2.d_scale, e2.stamp_src, e2.stamp_period, e2.stamp_row};
+    if (long_axis && ok8 && (opt(OPT_DC_ALONE_8P) == 2 || (opt(OPT_DC_ALONE_8P) == 1 && ((size_t)Nc * 2) % ((size_t)128 << 10) == 0))) {
+      // (A/B, round 6) the dC tiles alone on the phase-interleaved kernel: no dQ units four times as long next to them
+      const int nbx1a = cdiv(d, G2_B), nby1a = cdiv(Nc, G2_B);
+      if (int rc = launch<gemm8p_bwd_kernel<Epi8Scale>>(dim3((unsigned)(nbx1a * nby1a)), dim3(G2_THREADS), g8_lds_total, st, a1, s1, nbx1a, nby1a, a2, s2,
+                                                        cdiv(d, G2_B), 0, p.splits))
+        return rc;
+    } else if (long_axis) {
+      if (int rc = dc_body(cx.packed, G, Q, B, Nc, d, h_scale, d_scale, dC_part, st)) return rc;
+    }
+    const int nbx1 = cdiv(d, G2_B), nby1 = long_axis ? 0 : cdiv(Nc, G2_B), nbx2 = cdiv(d, G2_B), nby2 = cdiv(B, G2_B);
+    const int grid = nbx1 * nby1 + nbx2 * nby2 * p.splits;
+    // ok8: the phase-interleaved schedule (gemm8pb.h): an even number of K steps per unit, byte offsets in 32 bits
+    const int rc = ok8 ? launch<gemm8p_bwd_kernel<Epi8Scale>>(dim3((unsigned)grid), dim3(G2_THREADS), g8_lds_total, st, a1, s1, nbx1, nby1, a2, s2, nbx2, nby2, p.splits)
+                       : launch<gemm256_bwd_kernel<EpiScaleF32>>(dim3((unsigned)grid), dim3(G2_THREADS), g2_lds_total, st, a1, e1, nbx1, nby1, a2, e2, nbx2, nby2, p.splits);
+    if (rc) return rc;
+    return launch_dq(p, G, C, B, Nc, d, h_scale, d_scale, dQ, ws, wl, st, /*gemm_too=*/false, cx.defer);
+  }
+  const int t1 = dc_tile(B, Nc, d);
+  const int rc = use_tr() ? launch_pair_tr<true>(t1, p.tile, a1, e1, a2, e2, p.splits, st)
+                          : launch_pair_tr<false>(t1, p.tile, a1, e1, a2, e2, p.splits, st);
+  if (rc) return rc;
+  return launch_dq(p, G, C, B, Nc, d, h_scale, d_scale, dQ, ws, wl, st, /*gemm_too=*/false, cx.defer);
+}
+
+// the second launch of the latency-bound step (step_small.h)
+int launch_step_small(const StepCtx& cx, dprhot_bf16* Qb, dprhot_bf16* Cb, int B, int Nc, int d, const int64_t* y, int64_t y_offset, float grad_scale,
+                      float h_scale, const float* d_scale, float* S_out, float* row_loss, float* row_lse, float* loss_sum, dprhot_bf16* G, float* dQ,
+                      float* dC_part, const StepPlan& p, char* ws, hipStream_t st) {
+  const FwdPlan& fp = p.fp;
+  const PackedSpec& pk = cx.packed;
+  StepSmallArgs a{reinterpret_cast<const float*>(ws + p.wl.logits), fp.splits, (size_t)B * Nc, B, Nc, d, y, y_offset, grad_scale,
+                  Qb, Cb, h_scale, d_scale, dQ, dC_part, S_out, row_loss, row_lse, loss_sum, G,
+                  pk.stamp_src != nullptr ? pk.rows_c : 0, pk.n_ctx, cx.loss_scale};
+  // 16 columns of d per workgroup: every workgroup repeats the softmax, the narrow tile only shortens the GEMM / store tail
+  constexpr int tw = 16;
+  const size_t lds = step_small_lds(Nc, tw);
+  const int ncp = (Nc + 31) / 32 * 32;
+  const dim3 grid(d / tw), block(1024);
+  if (lds > 160 * 1024) return fail(DPRHOT_E_UNSUPPORTED, "small step: Nc=%d needs %zu bytes of LDS", Nc, lds);
+  // (the LDS of all these kernels grows with Nc: launch() raises the limit again when a larger shape follows a smaller one)
+  // DPRHOT_BY_SLABS instantiates NS == max(fp.splits, 1): the role-split kernels read exactly NS slabs and add them all, with no
+  // run-time look at the slab count (step_small.h: ss_load_slabs), so a plan outside 0 .. 4 must never reach the macro
+  if (fp.splits < 0 || fp.splits > 4)
+    return fail(DPRHOT_E_UNSUPPORTED, "small step: the plan has %d slabs, the launch reads max(splits, 1) <= 4", fp.splits);
+#define DPRHOT_BY_SLABS(LAUNCH, CPT) \
+  (fp.splits <= 1 ? LAUNCH(CPT, 1) : fp.splits == 2 ? LAUNCH(CPT, 2) : fp.splits == 3 ? LAUNCH(CPT, 3) : LAUNCH(CPT, 4))
+  // the role-split forms (step_small_kernel_roles, step_small_kernel_out): one row block, the multi-slab plans up to 768 columns
+  if (const int roles = opt(OPT_SMALL_STEP_ROLES); roles != 0 && B <= SS_ROWS && ncp <= 768) {
+    const int qtw = roles >= 2 && d % 32 == 0 ? 32 : 16;
+    // Form 3 hands the lead's outputs to workgroups of their own (a loss block and two row-store blocks in front of the grid).  A stamping launch (the packed step) keeps form
+    // 2: the loss goes into dC[m][0], whose owner -- the dC workgroup of column 0 -- needs the finished sum, so there the lead stays.
+    const bool outwg = roles == 3 && pk.stamp_src == nullptr;
+    const size_t rlds = step_roles_lds(Nc, qtw);  // (the maximum over the roles, the output role included)
+    const dim3 rgrid(d / 16 + 2 * (d / qtw) + (outwg ? SS_OUT_BLOCKS : 0));
+#define DPRHOT_SR_LAUNCH_K(KERN, CPT, NS, QTW) launch<KERN<CPT, NS, QTW>>(rgrid, block, rlds, st, a)
+#define DPRHOT_SR_LAUNCH_Q(CPT, NS, QTW) \
+  (outwg ? DPRHOT_SR_LAUNCH_K(step_small_kernel_out, CPT, NS, QTW) : DPRHOT_SR_LAUNCH_K(step_small_kernel_roles, CPT, NS, QTW))
+#define DPRHOT_SR_LAUNCH(CPT, NS) (qtw == 16 ? DPRHOT_SR_LAUNCH_Q(CPT, NS, 16) : DPRHOT_SR_LAUNCH_Q(CPT, NS, 32))
+    if (ncp <= 256) return DPRHOT_BY_SLABS(DPRHOT_SR_LAUNCH, 1);
+    if (ncp <= 512) return DPRHOT_BY_SLABS(DPRHOT_SR_LAUNCH, 2);
+    return DPRHOT_BY_SLABS(DPRHOT_SR_LAUNCH, 3);
+#undef DPRHOT_SR_LAUNCH
+#undef DPRHOT_SR_LAUNCH_Q
+#undef DPRHOT_SR_LAUNCH_K
+  }
+#define DPRHOT_SS_LAUNCH_N(CPT, NS, NRB) launch<step_small_kernel<CPT, tw, NS, NRB>>(grid, block, lds, st, a)
+#define DPRHOT_SS_LAUNCH(CPT, NS) (B <= SS_ROWS ? DPRHOT_SS_LAUNCH_N(CPT, NS, 1) : DPRHOT_SS_LAUNCH_N(CPT, NS, 2))
+  if (ncp <= 256) return DPRHOT_BY_SLABS(DPRHOT_SS_LAUNCH, 1);
+  if (ncp <= 512) return DPRHOT_BY_SLABS(DPRHOT_SS_LAUNCH, 2);
+  if (ncp <= 768) return DPRHOT_BY_SLABS(DPRHOT_SS_LAUNCH, 3);
+  return DPRHOT_SS_LAUNCH_N(5, 1, 1);  // (B <= 32 only: small_step_ok; above 768 columns the sim launch writes one slab: fwd_plan)
+#undef DPRHOT_SS_LAUNCH
+#undef DPRHOT_SS_LAUNCH_N
+#undef DPRHOT_BY_SLABS
+}
+
+// A whole training step (forward AND backward).  At the latency-bound shapes (step_small.h) it is TWO launches: the sim GEMM
+// (partial-logit slabs) and one kernel that does softmax-CE, dScores and both backward GEMMs; few rows against many contexts run the
+// launches of skinny.h; every other shape runs the launches of inbatch_fwd_f32_body + inbatch_bwd_body.
+int inbatch_step_body(const StepCtx& cx, const float* q, const float* c, dprhot_bf16* Qb, dprhot_bf16* Cb, int B, int Nc, int d, const int64_t* y,
+                      int64_t y_offset, const uint8_t* colmask, float inv_T, float grad_scale, float h_scale, const float* d_scale, float* S_out,
+                      float* row_loss, float* row_lse, float* loss_sum, dprhot_bf16* G, float* dQ, float* dC_part, const StepPlan& p, char* ws,
+                      hipStream_t st) {
+  if (p.family == FAM_FEW_ROWS) {
+    if (c != nullptr)  // single rank: the contexts arrive as fp32 -- one cast, then they are the bf16 matrix of every launch
+      if (int rc = dprhot_cast_bf16(c, Cb, (size_t)Nc * d, st)) return rc;
+    return sk_step(cx, q, Cb, Qb, B, Nc, d, y, y_offset, colmask, inv_T, grad_scale, h_scale, d_scale, S_out, row_loss, row_lse, loss_sum, G, dQ,
+                   dC_part, ws, p.wl, p.sk, st);
+  }
+  if (p.family == FAM_SMALL_STEP) {
+    if (int rc = sim_stats_f32_body(cx.packed, q, c, Qb, Cb, B, Nc, d, y, y_offset, colmask, inv_T, nullptr, p, ws, st)) return rc;
+    return launch_step_small(cx, Qb, Cb, B, Nc, d, y, y_offset, grad_scale, h_scale, d_scale, S_out, row_loss, row_lse, loss_sum, G, dQ, dC_part, p,
+                             ws, st);
+  }
+  // the sum of the row losses may ride in the launch that combines the dQ slabs (LossDefer)
+  // (single rank only: the packed step's backward stamps the finished loss into dC_part, so it must exist before that launch)
+  LossDefer ld;
+  ld.armed = cx.packed.stamp_src == nullptr && opt(OPT_LOSS_WITH_DQ) != 0;
+  StepCtx dx = cx;
+  dx.defer = &ld;
+  int rc = inbatch_fwd_f32_body(dx, q, c, Qb, Cb, B, Nc, d, y, y_offset, colmask, inv_T, grad_scale, S_out, row_loss, row_lse, loss_sum, G, p, ws, st);
+  ld.armed = false;
+  if (rc == DPRHOT_OK)
+    rc = inbatch_bwd_body(dx, bwd_plan(B, Nc, d, p.sk, true, cx.packed.stamp_src != nullptr), G, Qb, Cb, B, Nc, d, h_scale, d_scale, dQ, dC_part, p, ws, st);
+  if (ld.pending) {  // a backward without a slab-combining launch (or one that failed): the loss launch after all
+    const int rc2 = launch_loss_sum(ld.src, ld.n, ld.scale, ld.out, st, nullptr);
+    if (rc == DPRHOT_OK) rc = rc2;
+  }
+  return rc;
+}
+
+// ---- the training step: argument checks; an outer entry point runs the checks of the ones it is made of ----
+int check_sim_stats(const dprhot_bf16* Q, const dprhot_bf16* C, const int64_t* y, const float* S_out, int B, int Nc, int d) {
+  REQUIRE(Q && C && y, "NULL pointer");
+  if (int rc = check_shape(B, Nc, d)) return rc;
+  REQUIRE(aligned16(Q) && aligned16(C) && aligned16(S_out), "pointers must be 16-byte aligned");
+  return DPRHOT_OK;
+}
+int check_sim_stats_f32(const float* q, const float* c, const dprhot_bf16* Qb, const dprhot_bf16* Cb, const int64_t* y, const float* S_out, int B,
+                        int Nc, int d) {
+  REQUIRE(q && Qb && Cb && y, "NULL pointer");
+  if (int rc = check_shape(B, Nc, d)) return rc;
+  REQUIRE(aligned16(q) && aligned16(Qb) && aligned16(Cb) && aligned16(c) && aligned16(S_out), "pointers must be 16-byte aligned");
+  return DPRHOT_OK;
+}
+int check_softmax_finish(const float* S_in, const int64_t* y, const float* loss_sum, const dprhot_bf16* G, int B, int Nc, int d) {
+  REQUIRE(y && loss_sum, "NULL pointer");
+  if (int rc = check_shape(B, Nc, d)) return rc;
+  REQUIRE(aligned16(G) && aligned16(S_in), "pointers must be 16-byte aligned");
+  return DPRHOT_OK;
+}
+
+// What dprhot_train_step_* asks of the shape's plan, before anything else is looked at (a plain step asks for neither): dC_part as bf16
+// only from the few-rows step, whose dC units have such an epilogue; dQ slabs only where the step leaves some.
+int step_admit(int dc_kind, const float* dq_part, int B, int Nc, int d, StepPlan* p) {
+  if (int rc = check_shape(B, Nc, d)) return rc;
+  *p = step_plan(B, Nc, d);
+  if (dc_kind != GC_FP32 && !(dc_kind == GC_BF16 && p->family == FAM_FEW_ROWS))
+    return fail(DPRHOT_E_UNSUPPORTED, "train_step: dc_kind=%d at B=%d Nc=%d d=%d: this shape's plan writes fp32 dC_part only (ask for dc_kind = 2)", dc_kind,
+                B, Nc, d);
+  if (dq_part == nullptr) return DPRHOT_OK;
+  REQUIRE(aligned16(dq_part), "dq_part must be 16-byte aligned");
+  if (p->dq_slabs() == 0)
+    return fail(DPRHOT_E_INVALID, "train_step: dq_part given but B=%d Nc=%d d=%d leaves no slabs (dprhot_train_dq_slabs = 0)", B, Nc, d);
+  return DPRHOT_OK;
+}
+
+// the packed layout of a multi-rank step: the gathered buffer carries the column mask, the loss numerator rides in dC_part
+int packed_spec(const float* q, const dprhot_bf16* gathered, const dprhot_bf16* Qb, const int64_t* y, const float* loss_sum, int W, int rank, int n_ctx,
+                int d, PackedSpec* ps, int* rows_c) {
+  REQUIRE(q && gathered && Qb && y && loss_sum, "NULL pointer");
+  REQUIRE(W > 0 && rank >= 0 && rank < W && n_ctx > 0 && d > 0 && d % 8 == 0, "bad argument W=%d rank=%d n_ctx=%d d=%d", W, rank, n_ctx, d);
+  if (int rc = dprhot_packed_rows(n_ctx, d, rows_c)) return rc;
+  ps->base = reinterpret_cast<const uint8_t*>(gathered);
+  ps->rows_c = *rows_c;
+  ps->n_ctx = n_ctx;
+  ps->row_bytes = d * 2;
+  ps->stamp_src = loss_sum;
+  return DPRHOT_OK;
+}
+
+// every public form of the one-call step ends here, its shape admitted and planned (step_admit)
+int run_step(const StepCtx& cx, const StepPlan& p, const float* q, const float* c, dprhot_bf16* Qb, dprhot_bf16* Cb, int B, int Nc, int d,
+             const int64_t* y, int64_t y_offset, const uint8_t* colmask, float inv_T, float grad_scale, float h_scale, const float* d_scale, float* S_out,
+             float* row_loss, float* row_lse, float* loss_sum, dprhot_bf16* G, float* dQ, float* dC_part, void* workspace, size_t workspace_bytes,
+             hipStream_t st) {
+  REQUIRE(loss_sum && dQ && dC_part, "NULL pointer (loss_sum, dQ and dC_part are required)");
+  REQUIRE(aligned16(G) && aligned16(dQ) && aligned16(dC_part), "pointers must be 16-byte aligned");
+  REQUIRE(G != nullptr || p.fz.ok, "G == NULL at B=%d Nc=%d d=%d: this shape's plan materialises the dScores (dprhot_step_wants_g = 1)", B, Nc, d);
+  if (int rc = check_sim_stats_f32(q, c, Qb, Cb, y, S_out, B, Nc, d)) return rc;
+  char* ws;
+  if (int rc = claim_ws("inbatch_step", p.wl, workspace, workspace_bytes, true, true, &ws)) return rc;
+  return inbatch_step_body(cx, q, c, Qb, Cb, B, Nc, d, y, y_offset, colmask, inv_T, grad_scale, h_scale, d_scale, S_out, row_loss, row_lse, loss_sum, G,
+                           dQ, dC_part, p, ws, st);
 }
 
 }  // namespace
@@ -1091,7 +1607,7 @@ int dprhot_get_option(const char* name, int* h_value) {
 int dprhot_workspace_bytes(int B, int Nc, int d, size_t* h_out) {
   REQUIRE(h_out != nullptr, "h_out is NULL");
   if (int rc = check_shape(B, Nc, d)) return rc;
-  *h_out = ws_layout(B, Nc, d).total;
+  *h_out = step_plan(B, Nc, d).wl.total;
   return DPRHOT_OK;
 }
 
@@ -1152,20 +1668,7 @@ int dprhot_sim_fwd(const dprhot_bf16* Q, int B, const dprhot_bf16* C, int Nc, in
   REQUIRE(Q && C && S, "NULL pointer");
   if (int rc = check_shape(B, Nc, d)) return rc;
   REQUIRE(aligned16(Q) && aligned16(C) && aligned16(S), "pointers must be 16-byte aligned");
-  if (g8_ok(B, Nc, d) && !opt(OPT_NO_8P_STORE)) {
-    // large score matrices (validation with the logits wanted, the head chunk of a retrieval): the phase-interleaved kernel with
-    // the store epilogue that writes whole rows (Epi8Store); the round-1 256 x 256 kernel stays behind the option
-    Epi8Store epi;
-    static_cast<Epi8Base&>(epi) = g8_base(Q, B, Nc, nullptr, 0, colmask, inv_T, nullptr);
-    epi.S = S;
-    GemmArgs a8{Q, C, B, Nc, d, d, d, d};
-    return launch_g8<Epi8Store, 2>(a8, epi, (hipStream_t)stream);
-  }
-  const int tile = (force_tile() < 0 && big_ok(B, Nc, d)) ? kBigTile : pick_tile(B, Nc, d, 1, 2 * kNumCU);
-  GemmArgs a{Q, C, B, Nc, d, d, d, cdiv(d, kTiles[tile].bk) * kTiles[tile].bk};
-  EpiSim epi{S, colmask, B, Nc, inv_T, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0};
-  epi = with_packed_mask(epi);
-  return launch_gemm<true, true>(tile, a, epi, 1, (hipStream_t)stream);
+  return sim_fwd_body(PackedSpec{}, Q, B, C, Nc, d, colmask, inv_T, S, (hipStream_t)stream);
 }
 
 int dprhot_softmax_ce_fwd_bwd(const float* S, int B, int Nc, const int64_t* y, int64_t y_offset, float grad_scale,
@@ -1190,13 +1693,11 @@ int dprhot_dq(const dprhot_bf16* G, const dprhot_bf16* C, int B, int Nc, int d, 
   REQUIRE(G && C && dQ, "NULL pointer");
   if (int rc = check_shape(B, Nc, d)) return rc;
   REQUIRE(aligned16(G) && aligned16(C) && aligned16(dQ), "pointers must be 16-byte aligned");
-  const WsLayout wl = ws_layout(B, Nc, d);
-  if (dq_plan(B, Nc, d).splits > 1) {
-    if (workspace == nullptr || workspace_bytes < wl.total)
-      return fail(DPRHOT_E_WORKSPACE, "dq needs %zu workspace bytes, got %zu", wl.total, workspace_bytes);
-    REQUIRE(aligned16(workspace), "workspace must be 16-byte aligned");
-  }
-  return launch_dq(G, C, B, Nc, d, h_scale, d_scale, dQ, static_cast<char*>(workspace), wl, (hipStream_t)stream, true);
+  const DqPlan dq = dq_plan(B, Nc, d);
+  const WsLayout wl = step_plan(B, Nc, d).wl;
+  char* ws;
+  if (int rc = claim_ws("dq", wl, workspace, workspace_bytes, dq.splits > 1, true, &ws)) return rc;
+  return launch_dq(dq, G, C, B, Nc, d, h_scale, d_scale, dQ, ws, wl, (hipStream_t)stream, /*gemm_too=*/true, nullptr);
 }
 
 int dprhot_dc(const dprhot_bf16* G, const dprhot_bf16* Q, int B, int Nc, int d, float h_scale, const float* d_scale,
@@ -1204,11 +1705,7 @@ int dprhot_dc(const dprhot_bf16* G, const dprhot_bf16* Q, int B, int Nc, int d, 
   REQUIRE(G && Q && dC_part, "NULL pointer");
   if (int rc = check_shape(B, Nc, d)) return rc;
   REQUIRE(aligned16(G) && aligned16(Q) && aligned16(dC_part), "pointers must be 16-byte aligned");
-  // A(m = ctx column, k = query row) = G[k][m]  (mn-major, lda = Nc);  B(k, n) = Q[k][n]  (mn-major, ldb = d)
-  GemmArgs a{G, Q, Nc, d, B, Nc, d, cdiv(B, 64) * 64};
-  const EpiScaleF32 epi = with_loss_stamp(EpiScaleF32{dC_part, Nc, d, h_scale, d_scale});
-  const int tile = force_tile() >= 0 && force_tile() <= 3 ? force_tile() : dc_tile(B, Nc, d);
-  return launch_gemm<false, false>(tile, a, epi, 1, (hipStream_t)stream);
+  return dc_body(PackedSpec{}, G, Q, B, Nc, d, h_scale, d_scale, dC_part, (hipStream_t)stream);
 }
 
 int dprhot_rank_of_gold(const float* S, int rows, int cols, const int64_t* y, int64_t y_offset, int64_t* rank, void* stream) {
@@ -1377,164 +1874,51 @@ int dprhot_search(const dprhot_bf16* Q, int nq, const dprhot_bf16* C, int64_t n_
   return DPRHOT_OK;
 }
 
-// launch 1 of the fused forward: logits + per-tile softmax statistics + gold logit (and clears the loss
-// accumulator words the next launch adds into)
+// ---- the training step: check the arguments, derive the plan once, claim the workspace, run the body with a default context ----
 int dprhot_sim_stats(const dprhot_bf16* Q, int B, const dprhot_bf16* C, int Nc, int d, const int64_t* y, int64_t y_offset,
                      const uint8_t* colmask, float inv_T, float* S_out, void* workspace, size_t workspace_bytes, void* stream) {
-  REQUIRE(Q && C && y, "NULL pointer");
-  if (int rc = check_shape(B, Nc, d)) return rc;
-  REQUIRE(aligned16(Q) && aligned16(C) && (S_out == nullptr || aligned16(S_out)), "pointers must be 16-byte aligned");
-  const WsLayout wl = ws_layout(B, Nc, d);
-  if (workspace == nullptr || workspace_bytes < wl.total)
-    return fail(DPRHOT_E_WORKSPACE, "sim_stats needs %zu workspace bytes, got %zu", wl.total, workspace_bytes);
-  REQUIRE(aligned16(workspace), "workspace must be 16-byte aligned");
-  char* ws = static_cast<char*>(workspace);
-  if (S_out == nullptr && nl_ok(B, Nc, d)) {
-    // no-logits plan: strip statistics + gold logit only; dprhot_softmax_finish turns them into logsumexp / loss and
-    // dprhot_dscores recomputes the logits into G
-    Epi8Stats epi;
-    static_cast<Epi8Base&>(epi) = g8_base(Q, B, Nc, y, y_offset, colmask, inv_T, reinterpret_cast<float*>(ws + wl.gold));
-    epi.part_m = reinterpret_cast<float*>(ws + wl.part_m);
-    epi.part_s = reinterpret_cast<float*>(ws + wl.part_s);
-    epi.npart = cdiv(Nc, G2_B) * 4;
-    GemmArgs a8{Q, C, B, Nc, d, d, d, d};
-    return launch_g8(a8, epi, (hipStream_t)stream);
-  }
-  const FwdPlan fp = fwd_plan(B, Nc, d);
-  GemmArgs a{Q, C, B, Nc, d, d, d, fp.kchunk};
-  if (fp.short_rows) {  // partial logits per K split; the softmax launch sums them (and fills S_out if asked)
-    EpiSim epi{reinterpret_cast<float*>(ws + wl.logits), colmask, B, Nc, inv_T, nullptr, nullptr, nullptr, 0, nullptr,
-               reinterpret_cast<unsigned long long*>(ws + wl.header), 2, (size_t)B * Nc};
-    epi = with_packed_mask(epi);
-    return launch_gemm<true, true>(fp.tile, a, epi, fp.splits, (hipStream_t)stream);
-  }
-  float* S = S_out ? S_out : reinterpret_cast<float*>(ws + wl.logits);
-  EpiSim epi{S, colmask, B, Nc, inv_T, reinterpret_cast<float*>(ws + wl.part_m), reinterpret_cast<float*>(ws + wl.part_s),
-             y, y_offset, reinterpret_cast<float*>(ws + wl.gold), reinterpret_cast<unsigned long long*>(ws + wl.header), 2};
-  epi = with_packed_mask(epi);
-  return launch_gemm<true, true>(fp.tile, a, epi, 1, (hipStream_t)stream);
+  if (int rc = check_sim_stats(Q, C, y, S_out, B, Nc, d)) return rc;
+  const StepPlan p = step_plan(B, Nc, d);
+  char* ws;
+  if (int rc = claim_ws("sim_stats", p.wl, workspace, workspace_bytes, true, true, &ws)) return rc;
+  return sim_stats_body(PackedSpec{}, Q, B, C, Nc, d, y, y_offset, colmask, inv_T, S_out, p, ws, (hipStream_t)stream);
 }
 
-// launch 1 with fp32 operands: q [B,d] fp32 always; c [Nc,d] fp32 when non-NULL (single rank: no gather), else
-// Cb is the (gathered) bf16 input.  Qb (and Cb when c is given) receive the bf16 copies the backward reads.
 int dprhot_sim_stats_f32(const float* q, const float* c, dprhot_bf16* Qb, dprhot_bf16* Cb, int B, int Nc, int d, const int64_t* y,
                          int64_t y_offset, const uint8_t* colmask, float inv_T, float* S_out, void* workspace,
                          size_t workspace_bytes, void* stream) {
-  REQUIRE(q && Qb && Cb && y, "NULL pointer");
-  if (int rc = check_shape(B, Nc, d)) return rc;
-  REQUIRE(aligned16(q) && aligned16(Qb) && aligned16(Cb) && (c == nullptr || aligned16(c)) && (S_out == nullptr || aligned16(S_out)),
-          "pointers must be 16-byte aligned");
-  const WsLayout wl = ws_layout(B, Nc, d);
-  if (workspace == nullptr || workspace_bytes < wl.total)
-    return fail(DPRHOT_E_WORKSPACE, "sim_stats needs %zu workspace bytes, got %zu", wl.total, workspace_bytes);
-  REQUIRE(aligned16(workspace), "workspace must be 16-byte aligned");
-  char* ws = static_cast<char*>(workspace);
-  if (B > 128) {
-    // Beyond the latency-bound sizes reading fp32 operands in the GEMM costs more than it saves (twice the staging
-    // registers and bytes per tile, measured 250 vs 580 TFLOP/s at 8192^2): cast once, then the bf16 kernels.
-    if (c != nullptr) {
-      if (int rc = dprhot_prep(q, (size_t)B * d, Qb, c, (size_t)Nc * d, Cb, stream)) return rc;
-    } else {
-      if (int rc = dprhot_cast_bf16(q, Qb, (size_t)B * d, stream)) return rc;
-    }
-    return dprhot_sim_stats(Qb, B, Cb, Nc, d, y, y_offset, colmask, inv_T, S_out, workspace, workspace_bytes, stream);
-  }
-  const FwdPlan fp = fwd_plan(B, Nc, d);
-  GemmArgs a{reinterpret_cast<const uint16_t*>(q), c ? reinterpret_cast<const uint16_t*>(c) : Cb, B, Nc, d, d, d, fp.kchunk};
-  a.Acopy = Qb;
-  a.Bcopy = c ? Cb : nullptr;
-  if (fp.short_rows) {
-    if (c != nullptr && wide_sim_ok(B, Nc, d, fp) && g_packed.base == nullptr) {
-      // vocabulary-wide fp32 operands: LDS-DMA ring of fp32 tiles, bf16 rounding on the fragment read (wide.h)
-      WideSimArgs wa{q, c, Qb, Cb, B, Nc, d, colmask, inv_T, reinterpret_cast<float*>(ws + wl.logits), (size_t)B * Nc, fp.kchunk,
-                     reinterpret_cast<unsigned long long*>(ws + wl.header), 2, opt(OPT_WIDE_NOCOPY), cdiv(Nc, WD_B), cdiv(B, WD_B)};
-      return launch<wide_sim_kernel>(dim3((unsigned)(wa.nbx * wa.nby * fp.splits)), dim3(WD_THREADS), wd_lds_bytes, (hipStream_t)stream, wa);
-    }
-    EpiSim epi{reinterpret_cast<float*>(ws + wl.logits), colmask, B, Nc, inv_T, nullptr, nullptr, nullptr, 0, nullptr,
-               reinterpret_cast<unsigned long long*>(ws + wl.header), 2, (size_t)B * Nc};
-    epi = with_packed_mask(epi);
-    if (small_sim_ok(B, Nc, d, fp)) return launch_sim_small(c != nullptr, a, epi, fp.splits, (hipStream_t)stream);
-    return c ? launch_sim_f32<true, true>(fp.tile, a, epi, fp.splits, (hipStream_t)stream)
-             : launch_sim_f32<true, false>(fp.tile, a, epi, fp.splits, (hipStream_t)stream);
-  }
-  float* S = S_out ? S_out : reinterpret_cast<float*>(ws + wl.logits);
-  EpiSim epi{S, colmask, B, Nc, inv_T, reinterpret_cast<float*>(ws + wl.part_m), reinterpret_cast<float*>(ws + wl.part_s),
-             y, y_offset, reinterpret_cast<float*>(ws + wl.gold), reinterpret_cast<unsigned long long*>(ws + wl.header), 2};
-  epi = with_packed_mask(epi);
-  return c ? launch_sim_f32<true, true>(fp.tile, a, epi, 1, (hipStream_t)stream)
-           : launch_sim_f32<true, false>(fp.tile, a, epi, 1, (hipStream_t)stream);
+  if (int rc = check_sim_stats_f32(q, c, Qb, Cb, y, S_out, B, Nc, d)) return rc;
+  const StepPlan p = step_plan(B, Nc, d);
+  char* ws;
+  if (int rc = claim_ws("sim_stats", p.wl, workspace, workspace_bytes, true, true, &ws)) return rc;
+  return sim_stats_f32_body(PackedSpec{}, q, c, Qb, Cb, B, Nc, d, y, y_offset, colmask, inv_T, S_out, p, ws, (hipStream_t)stream);
 }
 
-// launch 2 of the fused forward: logsumexp from the statistics, G in one pass over S, loss numerator
 int dprhot_softmax_finish(const float* S_in, int B, int Nc, int d, const int64_t* y, int64_t y_offset, float grad_scale,
                           float* row_loss, float* row_lse, float* loss_sum, dprhot_bf16* G, void* workspace,
                           size_t workspace_bytes, void* stream) {
-  REQUIRE(y && loss_sum, "NULL pointer");
-  if (int rc = check_shape(B, Nc, d)) return rc;
-  REQUIRE((G == nullptr || aligned16(G)) && (S_in == nullptr || aligned16(S_in)), "pointers must be 16-byte aligned");
-  const WsLayout wl = ws_layout(B, Nc, d);
-  if (workspace == nullptr || workspace_bytes < wl.total)
-    return fail(DPRHOT_E_WORKSPACE, "softmax_finish needs %zu workspace bytes, got %zu", wl.total, workspace_bytes);
-  char* ws = static_cast<char*>(workspace);
-  if (S_in == nullptr && nl_ok(B, Nc, d)) {
-    // no-logits plan (same test as dprhot_sim_stats): logsumexp and loss from the strip statistics; there are no logits to turn
-    // into G here -- dprhot_dscores recomputes them
-    if (G != nullptr) return fail(DPRHOT_E_UNSUPPORTED, "softmax_finish: no logits at B=%d Nc=%d d=%d (no-logits forward): G comes from dprhot_dscores", B, Nc, d);
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = launch<g8_lse_kernel>(dim3(cdiv(B, 4)), dim3(256), 0, st, reinterpret_cast<const float*>(ws + wl.part_m),
-                                       reinterpret_cast<const float*>(ws + wl.part_s), cdiv(Nc, G2_B) * 4, reinterpret_cast<const float*>(ws + wl.gold), B,
-                                       reinterpret_cast<float*>(ws + wl.lse), row_lse, row_loss, reinterpret_cast<float*>(ws + wl.rloss)))
-      return rc;
-    return launch_loss_sum(reinterpret_cast<const float*>(ws + wl.rloss), B, g_loss_scale, loss_sum, st);
-  }
-  const FwdPlan fp = fwd_plan(B, Nc, d);  // same plan as dprhot_sim_stats -> same intermediate layout
-  if (fp.short_rows) {
-    // S_in, when given, is where the caller wants the summed logits (the slabs always live in the workspace)
-    GShortArgs g{reinterpret_cast<const float*>(ws + wl.logits), fp.splits, (size_t)B * Nc, B, Nc, y, y_offset, grad_scale,
-                 const_cast<float*>(S_in), row_loss, row_lse, G, reinterpret_cast<unsigned long long*>(ws + wl.header), loss_sum, fp.tpr, g_loss_scale};
-    if (fp.blocks > 65535) return fail(DPRHOT_E_UNSUPPORTED, "softmax_finish: B=%d rows need %d workgroups (max 65535)", B, fp.blocks);
-    if (fp.cpt == 1) return launch<gfinal_short_kernel<1>>(dim3(fp.blocks), dim3(fp.threads), 0, (hipStream_t)stream, g);
-    return launch<gfinal_short_kernel<2>>(dim3(fp.blocks), dim3(fp.threads), 0, (hipStream_t)stream, g);
-  }
-  const float* S = S_in ? S_in : reinterpret_cast<const float*>(ws + wl.logits);
-  const int nt = fp.nt;
-  if (nt > kGfMaxPairs) return fail(DPRHOT_E_UNSUPPORTED, "Nc=%d too long for the statistics buffer (%d column tiles)", Nc, nt);
-  GFinalArgs g{S, B, Nc, y, y_offset, grad_scale, reinterpret_cast<const float*>(ws + wl.part_m),
-               reinterpret_cast<const float*>(ws + wl.part_s), nt, reinterpret_cast<const float*>(ws + wl.gold), row_loss, row_lse,
-               G, reinterpret_cast<unsigned long long*>(ws + wl.header), loss_sum, g_loss_scale};
-  const bool thin = (long)B * (Nc / 8) <= 1L << 18;  // latency-bound sizes: one chunk per thread, many small workgroups
-  int rpb, xblocks;
-  gfinal_geometry(Nc, thin ? 1 : 8, &rpb, &xblocks);
-  if (cdiv(B, rpb) > 65535)  // grid.y limit, and the arrival ticket of the loss accumulation is 16 bits wide
-    return fail(DPRHOT_E_UNSUPPORTED, "softmax_finish: B=%d rows need %d row blocks (max 65535)", B, cdiv(B, rpb));
-  dim3 grid(xblocks, cdiv(B, rpb));
-  if (thin) return launch<gfinal_kernel<1>>(grid, dim3(256), 0, (hipStream_t)stream, g);
-  return launch<gfinal_kernel<8>>(grid, dim3(256), 0, (hipStream_t)stream, g);
+  if (int rc = check_softmax_finish(S_in, y, loss_sum, G, B, Nc, d)) return rc;
+  const StepPlan p = step_plan(B, Nc, d);
+  char* ws;
+  if (int rc = claim_ws("softmax_finish", p.wl, workspace, workspace_bytes, true, false, &ws)) return rc;
+  if (S_in == nullptr && p.nl && G != nullptr)
+    return fail(DPRHOT_E_UNSUPPORTED, "softmax_finish: no logits at B=%d Nc=%d d=%d (no-logits forward): G comes from dprhot_dscores", B, Nc, d);
+  return softmax_finish_body(StepCtx{}, S_in, B, Nc, d, y, y_offset, grad_scale, row_loss, row_lse, loss_sum, G, p, ws, (hipStream_t)stream);
 }
 
-// dScores of the no-logits forward: G = (softmax(S) - onehot) * grad_scale with S recomputed tile by tile (the same GEMM as
-// dprhot_sim_stats, bit-identical accumulators).  row_lse: the rows' logsumexp, or NULL to use the values dprhot_softmax_finish
-// left in the workspace.
+// row_lse: the rows' logsumexp, or NULL to use the values dprhot_softmax_finish left in the workspace.
 int dprhot_dscores(const dprhot_bf16* Q, int B, const dprhot_bf16* C, int Nc, int d, const int64_t* y, int64_t y_offset,
                    const uint8_t* colmask, float inv_T, float grad_scale, const float* row_lse, dprhot_bf16* G, void* workspace,
                    size_t workspace_bytes, void* stream) {
   REQUIRE(Q && C && y && G, "NULL pointer");
   if (int rc = check_shape(B, Nc, d)) return rc;
   REQUIRE(aligned16(Q) && aligned16(C) && aligned16(G), "pointers must be 16-byte aligned");
-  if (!nl_ok(B, Nc, d)) return fail(DPRHOT_E_UNSUPPORTED, "dscores: B=%d Nc=%d d=%d is not a no-logits shape (use dprhot_softmax_finish)", B, Nc, d);
-  const WsLayout wl = ws_layout(B, Nc, d);
-  if (row_lse == nullptr) {
-    if (workspace == nullptr || workspace_bytes < wl.total)
-      return fail(DPRHOT_E_WORKSPACE, "dscores needs %zu workspace bytes, got %zu", wl.total, workspace_bytes);
-    row_lse = reinterpret_cast<const float*>(static_cast<char*>(workspace) + wl.lse);
-  }
-  Epi8G epi;
-  static_cast<Epi8Base&>(epi) = g8_base(Q, B, Nc, y, y_offset, colmask, inv_T, nullptr);
-  epi.row_lse = row_lse;
-  epi.G = G;
-  epi.grad_scale = grad_scale;
-  GemmArgs a8{Q, C, B, Nc, d, d, d, d};
-  return launch_g8<Epi8G, 2>(a8, epi, (hipStream_t)stream);
+  const StepPlan p = step_plan(B, Nc, d);
+  if (!p.nl) return fail(DPRHOT_E_UNSUPPORTED, "dscores: B=%d Nc=%d d=%d is not a no-logits shape (use dprhot_softmax_finish)", B, Nc, d);
+  char* ws;
+  if (int rc = claim_ws("dscores", p.wl, workspace, workspace_bytes, row_lse == nullptr, false, &ws)) return rc;
+  if (row_lse == nullptr) row_lse = reinterpret_cast<const float*>(ws + p.wl.lse);
+  return dscores_body(PackedSpec{}, Q, B, C, Nc, d, y, y_offset, colmask, inv_T, grad_scale, row_lse, G, (hipStream_t)stream);
 }
 
 // Rank of every row's gold column in the stable descending order of its scores (dpr_task.py:235-246) straight from the
@@ -1545,11 +1929,9 @@ int dprhot_sim_rank(const dprhot_bf16* Q, int B, const dprhot_bf16* C, int Nc, i
   REQUIRE(Q && C && y && rank, "NULL pointer");
   if (int rc = check_shape(B, Nc, d)) return rc;
   REQUIRE(aligned16(Q) && aligned16(C), "pointers must be 16-byte aligned");
-  const WsLayout wl = ws_layout(B, Nc, d);
-  if (workspace == nullptr || workspace_bytes < wl.total)
-    return fail(DPRHOT_E_WORKSPACE, "sim_rank needs %zu workspace bytes, got %zu", wl.total, workspace_bytes);
-  REQUIRE(aligned16(workspace), "workspace must be 16-byte aligned");
-  char* ws = static_cast<char*>(workspace);
+  const WsLayout wl = step_plan(B, Nc, d).wl;
+  char* ws;
+  if (int rc = claim_ws("sim_rank", wl, workspace, workspace_bytes, true, true, &ws)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (!nl_ok(B, Nc, d)) {
     float* S = reinterpret_cast<float*>(ws + wl.logits);
@@ -1559,7 +1941,7 @@ int dprhot_sim_rank(const dprhot_bf16* Q, int B, const dprhot_bf16* C, int Nc, i
   float* gold = reinterpret_cast<float*>(ws + wl.lse);
   int* count = reinterpret_cast<int*>(ws + wl.rloss);
   Epi8Count epi;
-  static_cast<Epi8Base&>(epi) = g8_base(Q, B, Nc, y, y_offset, colmask, inv_T, nullptr);
+  static_cast<Epi8Base&>(epi) = g8_base(PackedSpec{}, Q, B, Nc, y, y_offset, colmask, inv_T, nullptr);
   epi.gold_val = gold;
   epi.count = count;
   if (int rc = launch<g8_gold_kernel>(dim3(cdiv(B, 32)), dim3(64), 0, st, Q, C, B, Nc, d, y, y_offset, epi.sim, inv_T, gold)) return rc;
@@ -1578,11 +1960,9 @@ int dprhot_sim_rank_loss(const dprhot_bf16* Q, int B, const dprhot_bf16* C, int 
   REQUIRE(Q && C && y && rank && loss_sum, "NULL pointer");
   if (int rc = check_shape(B, Nc, d)) return rc;
   REQUIRE(aligned16(Q) && aligned16(C), "pointers must be 16-byte aligned");
-  const WsLayout wl = ws_layout(B, Nc, d);
-  if (workspace == nullptr || workspace_bytes < wl.total)
-    return fail(DPRHOT_E_WORKSPACE, "sim_rank_loss needs %zu workspace bytes, got %zu", wl.total, workspace_bytes);
-  REQUIRE(aligned16(workspace), "workspace must be 16-byte aligned");
-  char* ws = static_cast<char*>(workspace);
+  const WsLayout wl = step_plan(B, Nc, d).wl;
+  char* ws;
+  if (int rc = claim_ws("sim_rank_loss", wl, workspace, workspace_bytes, true, true, &ws)) return rc;
   hipStream_t st = (hipStream_t)stream;
   if (!nl_ok(B, Nc, d)) {
     if (int rc = dprhot_sim_rank(Q, B, C, Nc, d, y, y_offset, colmask, inv_T, rank, workspace, workspace_bytes, stream)) return rc;
@@ -1592,7 +1972,7 @@ int dprhot_sim_rank_loss(const dprhot_bf16* Q, int B, const dprhot_bf16* C, int 
   float* gold = reinterpret_cast<float*>(ws + wl.gold);
   int* count = reinterpret_cast<int*>(ws + wl.rloss);  // (the row losses take this place once the ranks have been read out of it)
   Epi8CountStats epi;
-  static_cast<Epi8Base&>(epi) = g8_base(Q, B, Nc, y, y_offset, colmask, inv_T, nullptr);
+  static_cast<Epi8Base&>(epi) = g8_base(PackedSpec{}, Q, B, Nc, y, y_offset, colmask, inv_T, nullptr);
   epi.gold_val = gold;
   epi.count = count;
   epi.part_m = reinterpret_cast<float*>(ws + wl.part_m);
@@ -1606,250 +1986,74 @@ int dprhot_sim_rank_loss(const dprhot_bf16* Q, int B, const dprhot_bf16* C, int 
   if (int rc = launch<g8_lse_kernel>(dim3(cdiv(B, 4)), dim3(256), 0, st, epi.part_m, epi.part_s, epi.npart, gold, B, reinterpret_cast<float*>(ws + wl.lse),
                                      row_lse, row_loss, reinterpret_cast<float*>(ws + wl.rloss)))
     return rc;
-  return launch_loss_sum(reinterpret_cast<const float*>(ws + wl.rloss), B, g_loss_scale, loss_sum, st);
+  return launch_loss_sum(reinterpret_cast<const float*>(ws + wl.rloss), B, 1.0f, loss_sum, st, nullptr);
 }
 
 int dprhot_inbatch_fwd(const dprhot_bf16* Q, int B, const dprhot_bf16* C, int Nc, int d, const int64_t* y, int64_t y_offset,
                        const uint8_t* colmask, float inv_T, float grad_scale, float* S_out, float* row_loss, float* row_lse,
                        float* loss_sum, dprhot_bf16* G, void* workspace, size_t workspace_bytes, void* stream) {
-  if (S_out == nullptr && G != nullptr && nl128_ok(B, Nc, d)) {
-    // the same one-pass forward on the 128 x 128 LDS-DMA tile (round 6): the shapes whose 256-wide tiles cannot fill the chip
-    REQUIRE(Q && C && y && loss_sum, "NULL pointer");
-    if (int rc = check_shape(B, Nc, d)) return rc;
-    REQUIRE(aligned16(Q) && aligned16(C) && aligned16(G), "pointers must be 16-byte aligned");
-    const WsLayout wl = ws_layout(B, Nc, d);
-    if (workspace == nullptr || workspace_bytes < wl.total)
-      return fail(DPRHOT_E_WORKSPACE, "inbatch_fwd needs %zu workspace bytes, got %zu", wl.total, workspace_bytes);
-    REQUIRE(aligned16(workspace), "workspace must be 16-byte aligned");
-    char* ws = static_cast<char*>(workspace);
-    hipStream_t st = (hipStream_t)stream;
-    EpiSimP epi;
-    static_cast<EpiSim&>(epi) = with_packed_mask(EpiSim{nullptr, colmask, B, Nc, inv_T, reinterpret_cast<float*>(ws + wl.part_m),
-                                                        reinterpret_cast<float*>(ws + wl.part_s), y, y_offset,
-                                                        reinterpret_cast<float*>(ws + wl.gold), nullptr, 0});
-    epi.P = G;
-    epi.npart = cdiv(Nc, 64);
-    GemmArgs a{Q, C, B, Nc, d, d, d, d};
-    if (int rc = launch<gemm128d_kernel<true, true, EpiSimP, false>>(dim3(cdiv(Nc, 128), cdiv(B, 128), 1), dim3(256), g1_lds_bytes, st, a, epi)) return rc;
-    if (int rc = launch_lse_p2g(epi.part_m, epi.part_s, epi.npart, B, Nc, y, y_offset, grad_scale, row_lse, row_loss, G, ws, wl, st)) return rc;
-    return launch_loss_sum(reinterpret_cast<const float*>(ws + wl.rloss), B, g_loss_scale, loss_sum, st);
-  }
-  if (S_out == nullptr && G != nullptr && nl_ok(B, Nc, d) && opt(OPT_NL_P16) != 0) {
-    // no-logits forward in ONE pass of the GEMM (round 6): strip statistics + fp16 softmax numerators into the G buffer (Epi8StatsP),
-    // then one row kernel: logsumexp / loss, and the numerators rescaled into the bf16 dScores in place
-    REQUIRE(Q && C && y && loss_sum, "NULL pointer");
-    if (int rc = check_shape(B, Nc, d)) return rc;
-    REQUIRE(aligned16(Q) && aligned16(C) && aligned16(G), "pointers must be 16-byte aligned");
-    const WsLayout wl = ws_layout(B, Nc, d);
-    if (workspace == nullptr || workspace_bytes < wl.total)
-      return fail(DPRHOT_E_WORKSPACE, "inbatch_fwd needs %zu workspace bytes, got %zu", wl.total, workspace_bytes);
-    REQUIRE(aligned16(workspace), "workspace must be 16-byte aligned");
-    char* ws = static_cast<char*>(workspace);
-    hipStream_t st = (hipStream_t)stream;
-    Epi8StatsP epi;
-    static_cast<Epi8Base&>(epi) = g8_base(Q, B, Nc, y, y_offset, colmask, inv_T, reinterpret_cast<float*>(ws + wl.gold));
-    epi.part_m = reinterpret_cast<float*>(ws + wl.part_m);
-    epi.part_s = reinterpret_cast<float*>(ws + wl.part_s);
-    epi.npart = cdiv(Nc, G2_B) * 4;
-    epi.P = G;
-    GemmArgs a8{Q, C, B, Nc, d, d, d, d};
-    if (opt(OPT_P16_STAGED) == 2 || (opt(OPT_P16_STAGED) == 1 && ((size_t)Nc * 2) % ((size_t)128 << 10) != 0)) {
-      Epi8StatsPS es;
-      static_cast<Epi8Stats&>(es) = static_cast<const Epi8Stats&>(epi);
-      es.P = G;
-      if (int rc = launch_g8<Epi8StatsPS, 2>(a8, es, st)) return rc;
-    } else if (int rc = launch_g8<Epi8StatsP, 2>(a8, epi, st)) return rc;  // (two-phase schedule, as every storing epilogue; the four-phase instantiation spilled two registers)
-    if (int rc = launch_lse_p2g(epi.part_m, epi.part_s, epi.npart, B, Nc, y, y_offset, grad_scale, row_lse, row_loss, G, ws, wl, st)) return rc;
-    return launch_loss_sum(reinterpret_cast<const float*>(ws + wl.rloss), B, g_loss_scale, loss_sum, st);
-  }
-  if (S_out == nullptr && nl_ok(B, Nc, d)) {
-    // no-logits forward: statistics pass -> logsumexp / loss -> dScores pass (logits recomputed); S is never in memory
-    if (int rc = dprhot_sim_stats(Q, B, C, Nc, d, y, y_offset, colmask, inv_T, nullptr, workspace, workspace_bytes, stream)) return rc;
-    if (int rc = dprhot_softmax_finish(nullptr, B, Nc, d, y, y_offset, grad_scale, row_loss, row_lse, loss_sum, nullptr, workspace,
-                                       workspace_bytes, stream))
-      return rc;
-    if (G == nullptr) return DPRHOT_OK;
-    return dprhot_dscores(Q, B, C, Nc, d, y, y_offset, colmask, inv_T, grad_scale, nullptr, G, workspace, workspace_bytes, stream);
-  }
-  if (int rc = dprhot_sim_stats(Q, B, C, Nc, d, y, y_offset, colmask, inv_T, S_out, workspace, workspace_bytes, stream)) return rc;
-  return dprhot_softmax_finish(S_out, B, Nc, d, y, y_offset, grad_scale, row_loss, row_lse, loss_sum, G, workspace, workspace_bytes,
-                               stream);
+  if (int rc = check_sim_stats(Q, C, y, S_out, B, Nc, d)) return rc;
+  if (int rc = check_softmax_finish(S_out, y, loss_sum, G, B, Nc, d)) return rc;
+  const StepPlan p = step_plan(B, Nc, d);
+  char* ws;
+  if (int rc = claim_ws("inbatch_fwd", p.wl, workspace, workspace_bytes, true, true, &ws)) return rc;
+  return inbatch_fwd_body(StepCtx{}, Q, B, C, Nc, d, y, y_offset, colmask, inv_T, grad_scale, S_out, row_loss, row_lse, loss_sum, G, p, ws,
+                          (hipStream_t)stream);
 }
 
 int dprhot_inbatch_fwd_f32(const float* q, const float* c, dprhot_bf16* Qb, dprhot_bf16* Cb, int B, int Nc, int d, const int64_t* y,
                            int64_t y_offset, const uint8_t* colmask, float inv_T, float grad_scale, float* S_out, float* row_loss,
                            float* row_lse, float* loss_sum, dprhot_bf16* G, void* workspace, size_t workspace_bytes, void* stream) {
-  if (S_out == nullptr && B > 128 && (nl_ok(B, Nc, d) || (G != nullptr && nl128_ok(B, Nc, d)))) {  // cast once, then the no-logits forward on the bf16 copies
-    REQUIRE(q && Qb && Cb && y, "NULL pointer");
-    if (c != nullptr) {
-      if (int rc = dprhot_prep(q, (size_t)B * d, Qb, c, (size_t)Nc * d, Cb, stream)) return rc;
-    } else {
-      if (int rc = dprhot_cast_bf16(q, Qb, (size_t)B * d, stream)) return rc;
-    }
-    return dprhot_inbatch_fwd(Qb, B, Cb, Nc, d, y, y_offset, colmask, inv_T, grad_scale, nullptr, row_loss, row_lse, loss_sum, G, workspace,
-                              workspace_bytes, stream);
-  }
-  if (int rc = dprhot_sim_stats_f32(q, c, Qb, Cb, B, Nc, d, y, y_offset, colmask, inv_T, S_out, workspace, workspace_bytes, stream))
-    return rc;
-  return dprhot_softmax_finish(S_out, B, Nc, d, y, y_offset, grad_scale, row_loss, row_lse, loss_sum, G, workspace, workspace_bytes,
-                               stream);
+  if (int rc = check_sim_stats_f32(q, c, Qb, Cb, y, S_out, B, Nc, d)) return rc;
+  if (int rc = check_softmax_finish(S_out, y, loss_sum, G, B, Nc, d)) return rc;
+  const StepPlan p = step_plan(B, Nc, d);
+  char* ws;
+  if (int rc = claim_ws("inbatch_fwd", p.wl, workspace, workspace_bytes, true, true, &ws)) return rc;
+  return inbatch_fwd_f32_body(StepCtx{}, q, c, Qb, Cb, B, Nc, d, y, y_offset, colmask, inv_T, grad_scale, S_out, row_loss, row_lse, loss_sum, G, p,
+                              ws, (hipStream_t)stream);
 }
 
 int dprhot_inbatch_bwd(const dprhot_bf16* G, const dprhot_bf16* Q, const dprhot_bf16* C, int B, int Nc, int d, float h_scale,
                        const float* d_scale, float* dQ, float* dC_part, void* workspace, size_t workspace_bytes, void* stream) {
   REQUIRE(G && Q && C, "NULL pointer");
   if (int rc = check_shape(B, Nc, d)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  // (the long context axis under fewer than 512 rows: both GEMMs on the 128 x 128 engine -- see `long_axis` below; 256 x 65536 x 768:
-  //  146 us against 174 with the dQ units on the 256 x 256 kernel and 252 for the pair)
-  // (round 6, with the LDS-DMA 128 x 128 tile: also 512 <= B < 1024 from Nc >= 32 B on -- 512 x 16384 56 against 65 us with the dQ units on
-  //  the 256 x 256 kernel and 73 for the pair, 512 x 32768 90 / 100 / 116: profiles/r06_bwd_plan_ab.txt)
-  const bool long_axis_small = ((B < 512 && Nc >= 56 * 1024) || (B >= 512 && B < 1024 && (long)Nc >= 32L * B)) && !sk_plan(B, Nc, d).ok &&
-                               !wide_bwd_ok(B, Nc, d) && big_bwd_ok(B, Nc, d) && !pair128_use(B, Nc, d);
-  if (dQ == nullptr || dC_part == nullptr || unfused_bwd() || force_tile() >= 0 || long_axis_small) {
-    if (dC_part != nullptr)
-      if (int rc = dprhot_dc(G, Q, B, Nc, d, h_scale, d_scale, dC_part, stream)) return rc;
-    if (dQ != nullptr)
-      if (int rc = dprhot_dq(G, C, B, Nc, d, h_scale, d_scale, dQ, workspace, workspace_bytes, stream)) return rc;
-    return DPRHOT_OK;
-  }
-  REQUIRE(aligned16(G) && aligned16(Q) && aligned16(C) && aligned16(dQ) && aligned16(dC_part), "pointers must be 16-byte aligned");
-  if (g_packed.stamp_src == nullptr) {
-    // Shapes of the few-rows plan: the same backward units as the one-call step (dC tiles and split-K dQ tiles side by side, then the
-    // slab reduction) for callers that run sim / loss / backward as separate calls (a subclass's own loss on sim_score's logits):
-    // 128 x 8192 x 768 23 -> ~15 us against the generic pair kernel.
-    const SkPlan sk = sk_plan(B, Nc, d);
-    if (sk.ok) {
-      const WsLayout wl = ws_layout(B, Nc, d);
-      char* ws = static_cast<char*>(workspace);
-      if (sk.nslices > 1 && (ws == nullptr || workspace_bytes < wl.total))
-        return fail(DPRHOT_E_WORKSPACE, "inbatch_bwd needs %zu workspace bytes, got %zu", wl.total, workspace_bytes);
-      float* part = sk.nslices > 1 ? reinterpret_cast<float*>(ws + wl.dq_part) : nullptr;
-      const int ndq = sk.nslices * (d / SK_QN), ndq_pad = (ndq + 7) & ~7, ndc = sk.nt * (d / SK_DN);
-      SkBwdArgs b{G, Q, C, B, Nc, d, h_scale, d_scale, dC_part, nullptr, nullptr, 1.0f, 0, 0, 0, sk.ksteps, sk.nslices, part, dQ, ndq_pad,
-                  opt(OPT_NT_STORES) ? 1 : 0};
-      if (int rc = launch_sk_bwd(b, ndq_pad + ndc, st)) return rc;
-      if (sk.nslices > 1) return launch_sk_dq_reduce(part, sk.nslices, B, d, h_scale, d_scale, dQ, st);
-      return DPRHOT_OK;
-    }
-  }
-  if (wide_bwd_ok(B, Nc, d) && g_packed.stamp_src == nullptr) {
-    // Vocabulary-wide vectors under few rows (CITADEL router: 128 x 1024 x 30528): every unit of either GEMM is a short K loop in front
-    // of a large store -- the unit shapes of skinny.h (whole operand footprint in flight by LDS-DMA, stores through LDS in whole
-    // lines), dC tiles and dQ tiles side by side in one launch; the contexts fit one dQ slice, so no partial sums and no reduction.
-    // The 141 MB of fp32 gradients leave with non-temporal stores: nobody re-reads them inside the step, and written normally they push
-    // the step's operands out of the 256 MB Infinity Cache (measured, scratch/router_ab.py: step 116 -> 99.5 us; the same policy on the
-    // 8192^2 launches -- stored logits, 256 x 256 backward -- LOST 5-10 % and is not used there: profiles/r03_nt_stores_ab.txt).
-    const int ksteps = cdiv(Nc, 64);
-    const int ndq = d / SK_QN, ndq_pad = (ndq + 7) & ~7, ndc = cdiv(Nc, SK_COLS) * cdiv(d, SK_DN);
-    SkBwdArgs b{G, Q, C, B, Nc, d, h_scale, d_scale, dC_part, nullptr, nullptr, 1.0f, 0, 0, 0, ksteps, 1, nullptr, dQ, ndq_pad, opt(OPT_NT_STORES) ? 1 : 0};
-    return launch_sk_bwd(b, ndq_pad + ndc, st);
-  }
-  const WsLayout wl = ws_layout(B, Nc, d);
-  if (pair128_use(B, Nc, d)) {
-    // [dC tiles | dQ tiles x K slices] on the 128 x 128 LDS-DMA tile (round 6): the shapes under the 256 x 256 gate ran this pair on the
-    // register-staged tiles (2048 x 4096 x 768: 69.5 us for 26 GFLOP)
-    const Pair128Plan pp = pair128_plan(B, Nc, d);
-    char* ws = static_cast<char*>(workspace);
-    if (pp.splits > 1 && (ws == nullptr || workspace_bytes < wl.total))
-      return fail(DPRHOT_E_WORKSPACE, "inbatch_bwd needs %zu workspace bytes, got %zu", wl.total, workspace_bytes);
-    GemmArgs a1{G, Q, Nc, d, B, Nc, d, B};
-    const EpiScaleF32 e1 = with_loss_stamp(EpiScaleF32{dC_part, Nc, d, h_scale, d_scale});
-    GemmArgs a2{G, C, B, d, Nc, Nc, d, pp.kchunk};
-    const EpiScaleF32 e2 = pp.splits == 1 ? EpiScaleF32{dQ, B, d, h_scale, d_scale}
-                                          : EpiScaleF32{reinterpret_cast<float*>(ws + wl.dq_part), B, d, 1.0f, nullptr};
-    const int nbx1 = cdiv(d, 128), nby1 = cdiv(Nc, 128), nbx2 = cdiv(d, 128), nby2 = cdiv(B, 128);
-    const long grid = (long)nbx1 * nby1 + (long)nbx2 * nby2 * pp.splits;
-    if (grid > 0x7fffffffL) return fail(DPRHOT_E_UNSUPPORTED, "grid too large");
-    if (int rc = launch<gemm128d_pair_kernel<EpiScaleF32>>(dim3((unsigned)grid), dim3(256), g1_lds_bytes, st, a1, e1, nbx1, nby1, a2, e2, nbx2, nby2, pp.splits))
-      return rc;
-    if (pp.splits > 1) return launch_slab_sum(reinterpret_cast<const float*>(ws + wl.dq_part), pp.splits, B, d, h_scale, d_scale, dQ, st);
-    return DPRHOT_OK;
-  }
-  const DqPlan p = dq_plan(B, Nc, d);
-  char* ws = static_cast<char*>(workspace);
-  if (p.splits > 1 && (ws == nullptr || workspace_bytes < wl.total))
-    return fail(DPRHOT_E_WORKSPACE, "inbatch_bwd needs %zu workspace bytes, got %zu", wl.total, workspace_bytes);
-  // one launch: [dC tiles | dQ tiles x splits]
-  GemmArgs a1{G, Q, Nc, d, B, Nc, d, cdiv(B, 64) * 64};
-  const EpiScaleF32 e1 = with_loss_stamp(EpiScaleF32{dC_part, Nc, d, h_scale, d_scale});
-  GemmArgs a2{G, C, B, d, Nc, Nc, d, p.kchunk};
-  EpiScaleF32 e2 = p.splits == 1 ? EpiScaleF32{dQ, B, d, h_scale, d_scale}
-                                 : EpiScaleF32{reinterpret_cast<float*>(ws + wl.dq_part), B, d, 1.0f, nullptr};
-  if (p.big) {
-    // Few query rows against a long context axis (512 <= B <= 2048, Nc >= 32 B: e.g. 8192 global queries x 8 contexts seen from one
-    // of 8 ranks): the dC tiles of the pair launch are only K = B deep -- 8 to 32 K steps between a pipeline fill and a 256 KiB store
-    // -- next to dQ units several times as long (the K slices of dQ stop at 16), and the launch loses to dC on the 128 x 128 engine in a
-    // launch of its own (dprhot_dc) followed by this launch with its dQ units only.  Measured, pair / dC apart, us (d = 768,
-    // scratch/bwd_hybrid_ab.py, profiles/r05_bwd_long_axis.txt): 1024 x 32768 181 / 154, 1024 x 49152 292 / 236, 1024 x 65536 482 / 299,
-    // 512 x 16384 73 / 70, 512 x 32768 117 / 112, 512 x 65536 356 / 202, 2048 x 65536 611 / 555, 1024 x 32768 x 1024 217 / 197; the
-    // pair stays where it wins: 1024 x 8192 43 / 71, 1024 x 16384 82 / 96, 2048 x 16384 122 / 146, 2048 x 32768 228 / 289, 512 x 8192 33 / 50.
-    const bool long_axis = B >= 512 && B <= 2048 && (long)Nc >= 32L * B;
-    const bool no8 = opt(OPT_NO_8PB) != 0;
-    // (round 6: B and Nc multiples of 64 suffice -- a unit with an odd number of K steps skips the MFMAs of its last half pair; the packed
-    //  multi-rank layout's column counts are multiples of 64, rarely of 128)
-    const bool ok8 = !no8 && B % 64 == 0 && Nc % 64 == 0 && p.kchunk % 128 == 0 && (double)B * Nc < 2.0e9 && (double)Nc * d < 2.0e9;
-    a1.kchunk = B;  // dC: one K range (B % 64 == 0)
-    // the same epilogues for the phase-interleaved kernel (gemm8pb.h)
-    const Epi8Scale s1{e1.out, e1.M, e1.N, e1.h_scale, e1.d_scale, e1.stamp_src, e1.stamp_period, e1.stamp_row};
-    const Epi8Scale s2{e2.out, e2.M, e2.N, e2.h_scale, e2.d_scale, e2.stamp_src, e2.stamp_period, e2.stamp_row};
-    if (long_axis && ok8 && (opt(OPT_DC_ALONE_8P) == 2 || (opt(OPT_DC_ALONE_8P) == 1 && ((size_t)Nc * 2) % ((size_t)128 << 10) == 0))) {
-      // (A/B, round 6) the dC tiles alone on the phase-interleaved kernel: no dQ units four times as long next to them
-      const int nbx1a = cdiv(d, G2_B), nby1a = cdiv(Nc, G2_B);
-      if (int rc = launch<gemm8p_bwd_kernel<Epi8Scale>>(dim3((unsigned)(nbx1a * nby1a)), dim3(G2_THREADS), g8_lds_total, st, a1, s1, nbx1a, nby1a, a2, s2,
-                                                        cdiv(d, G2_B), 0, p.splits))
-        return rc;
-    } else if (long_axis) {
-      if (int rc = dprhot_dc(G, Q, B, Nc, d, h_scale, d_scale, dC_part, stream)) return rc;
-    }
-    const int nbx1 = cdiv(d, G2_B), nby1 = long_axis ? 0 : cdiv(Nc, G2_B), nbx2 = cdiv(d, G2_B), nby2 = cdiv(B, G2_B);
-    const int grid = nbx1 * nby1 + nbx2 * nby2 * p.splits;
-    // ok8: the phase-interleaved schedule (gemm8pb.h): an even number of K steps per unit, byte offsets in 32 bits
-    const int rc = ok8 ? launch<gemm8p_bwd_kernel<Epi8Scale>>(dim3((unsigned)grid), dim3(G2_THREADS), g8_lds_total, st, a1, s1, nbx1, nby1, a2, s2, nbx2, nby2, p.splits)
-                       : launch<gemm256_bwd_kernel<EpiScaleF32>>(dim3((unsigned)grid), dim3(G2_THREADS), g2_lds_total, st, a1, e1, nbx1, nby1, a2, e2, nbx2, nby2, p.splits);
-    if (rc) return rc;
-    return launch_dq(G, C, B, Nc, d, h_scale, d_scale, dQ, ws, wl, st, /*gemm_too=*/false);
-  }
-  const int t1 = dc_tile(B, Nc, d);
-  const int rc = use_tr() ? launch_pair_tr<true>(t1, p.tile, a1, e1, a2, e2, p.splits, st)
-                          : launch_pair_tr<false>(t1, p.tile, a1, e1, a2, e2, p.splits, st);
-  if (rc) return rc;
-  return launch_dq(G, C, B, Nc, d, h_scale, d_scale, dQ, ws, wl, st, /*gemm_too=*/false);
-}
-
-// A whole training step (forward AND backward) in one call.  At the latency-bound shapes (step_small.h) it is TWO
-// launches: the sim GEMM (partial-logit slabs) and one kernel that does softmax-CE, dScores and both backward GEMMs;
-// every other shape runs the three launches of dprhot_inbatch_fwd_f32 + dprhot_inbatch_bwd.
-static bool small_step_ok(int B, int Nc, int d) {
-  const FwdPlan fp = fwd_plan(B, Nc, d);
-  // two row blocks (32 < B <= 64) up to 256 columns only -- measured (scratch/rb_probe.py, two launches against three): 64 x 256 x 768
-  // 13.3 against 16.2 us, 64 x 128 x 1024 13.5 / 14.0, but 64 x 512 18.6 / 17.5 and 64 x 768 24.0 / 22.8: every workgroup repeats
-  // BOTH blocks' softmax, and beyond 256 columns that second helping costs more than the launch it saves
-  return !opt(OPT_NO_SMALL_STEP) && B <= SS_MAXB && Nc <= (B <= SS_ROWS ? SS_MAXNC : 256) && d % 16 == 0 && fp.short_rows && fp.splits <= 4 &&
-         !unfused_bwd();
+  // (an operand is read only by the product it belongs to: Q by dC, C by dQ)
+  REQUIRE((dQ == nullptr && dC_part == nullptr) ||
+              (aligned16(G) && aligned16(dQ) && aligned16(dC_part) && (dC_part == nullptr || aligned16(Q)) && (dQ == nullptr || aligned16(C))),
+          "pointers must be 16-byte aligned");
+  const StepPlan p = step_plan(B, Nc, d);
+  const BwdPlan bp = bwd_plan(B, Nc, d, p.sk, dQ != nullptr && dC_part != nullptr, false);
+  char* ws;
+  if (int rc = claim_ws("inbatch_bwd", p.wl, workspace, workspace_bytes, dQ != nullptr && bp.slabs > 1, bp.kind == BWD_APART, &ws)) return rc;
+  return inbatch_bwd_body(StepCtx{}, bp, G, Q, C, B, Nc, d, h_scale, d_scale, dQ, dC_part, p, ws, (hipStream_t)stream);
 }
 
 int dprhot_step_wants_g(int B, int Nc, int d, int* h_wants) {
   REQUIRE(h_wants != nullptr, "NULL pointer");
   if (int rc = check_shape(B, Nc, d)) return rc;
-  // 0 where the few-rows plan takes the fused-dScores form -- judged on the plain column tiling: the packed layout's remapped tiles
-  // are never more and their slices never longer.  A pure function of the shape, like every plan here.
-  const SkPlan sk = sk_plan(B, Nc, d);
-  *h_wants = sk_fused_plan(sk, cdiv(Nc, SK_COLS), cdiv(Nc, 64), B, Nc, d).ok ? 0 : 1;
+  *h_wants = step_plan(B, Nc, d).fz.ok ? 0 : 1;  // 0 where the few-rows plan takes the fused-dScores form
   return DPRHOT_OK;
 }
 
 int dprhot_fwd_one_pass(int B, int Nc, int d, int* h_kind) {
   REQUIRE(h_kind != nullptr, "NULL pointer");
   if (int rc = check_shape(B, Nc, d)) return rc;
-  *h_kind = nl128_ok(B, Nc, d) ? 2 : (nl_ok(B, Nc, d) && opt(OPT_NL_P16) != 0 ? 1 : 0);
+  const FwdKind k = step_plan(B, Nc, d).fwd(false, true);
+  *h_kind = k == FWD_ONE_PASS_128 ? 2 : (k == FWD_ONE_PASS_256 ? 1 : 0);
   return DPRHOT_OK;
 }
 
 int dprhot_fwd_no_logits(int B, int Nc, int d, int* h_nl) {
   REQUIRE(h_nl != nullptr, "NULL pointer");
   if (int rc = check_shape(B, Nc, d)) return rc;
-  *h_nl = nl_ok(B, Nc, d) ? 1 : 0;
+  *h_nl = step_plan(B, Nc, d).nl ? 1 : 0;
+  return DPRHOT_OK;
+}
+
+int dprhot_train_dq_slabs(int B, int Nc, int d, int* h_nslabs) {
+  REQUIRE(h_nslabs != nullptr, "NULL pointer");
+  if (int rc = check_shape(B, Nc, d)) return rc;
+  *h_nslabs = step_plan(B, Nc, d).dq_slabs();
   return DPRHOT_OK;
 }
 
@@ -1857,95 +2061,10 @@ int dprhot_inbatch_step_f32(const float* q, const float* c, dprhot_bf16* Qb, dpr
                             int64_t y_offset, const uint8_t* colmask, float inv_T, float grad_scale, float h_scale, const float* d_scale,
                             float* S_out, float* row_loss, float* row_lse, float* loss_sum, dprhot_bf16* G, float* dQ, float* dC_part,
                             void* workspace, size_t workspace_bytes, void* stream) {
-  REQUIRE(loss_sum && dQ && dC_part, "NULL pointer (loss_sum, dQ and dC_part are required)");
-  REQUIRE(aligned16(G) && aligned16(dQ) && aligned16(dC_part), "pointers must be 16-byte aligned");
-  if (int rc = check_shape(B, Nc, d)) return rc;
-  if (G == nullptr) {
-    int wants = 1;
-    if (int rc = dprhot_step_wants_g(B, Nc, d, &wants)) return rc;
-    REQUIRE(wants == 0, "G == NULL at B=%d Nc=%d d=%d: this shape's plan materialises the dScores (dprhot_step_wants_g = 1)", B, Nc, d);
-  }
-  {
-    const SkPlan sk = sk_plan(B, Nc, d);
-    if (sk.ok) {
-      REQUIRE(q && Qb && Cb && y, "NULL pointer");
-      REQUIRE(aligned16(q) && aligned16(Qb) && aligned16(Cb) && (c == nullptr || aligned16(c)) && (S_out == nullptr || aligned16(S_out)),
-              "pointers must be 16-byte aligned");
-      const WsLayout wl = ws_layout(B, Nc, d);
-      if (workspace == nullptr || workspace_bytes < wl.total)
-        return fail(DPRHOT_E_WORKSPACE, "inbatch_step needs %zu workspace bytes, got %zu", wl.total, workspace_bytes);
-      REQUIRE(aligned16(workspace), "workspace must be 16-byte aligned");
-      if (c != nullptr)  // single rank: the contexts arrive as fp32 -- one cast, then they are the bf16 matrix of every launch
-        if (int rc = dprhot_cast_bf16(c, Cb, (size_t)Nc * d, stream)) return rc;
-      return sk_step(q, Cb, Qb, B, Nc, d, y, y_offset, colmask, inv_T, grad_scale, h_scale, d_scale, S_out, row_loss, row_lse, loss_sum, G,
-                     dQ, dC_part, static_cast<char*>(workspace), wl, sk, (hipStream_t)stream);
-    }
-  }
-  if (!small_step_ok(B, Nc, d)) {
-    // (single rank only: the packed step's backward stamps the finished loss into dC_part, so it must exist before that launch)
-    g_loss_defer.armed = g_packed.stamp_src == nullptr && opt(OPT_LOSS_WITH_DQ) != 0;
-    g_loss_defer.pending = false;
-    int rc = dprhot_inbatch_fwd_f32(q, c, Qb, Cb, B, Nc, d, y, y_offset, colmask, inv_T, grad_scale, S_out, row_loss, row_lse, loss_sum, G,
-                                    workspace, workspace_bytes, stream);
-    g_loss_defer.armed = false;
-    if (rc == DPRHOT_OK) rc = dprhot_inbatch_bwd(G, Qb, Cb, B, Nc, d, h_scale, d_scale, dQ, dC_part, workspace, workspace_bytes, stream);
-    if (g_loss_defer.pending) {  // a backward without a slab-combining launch (or one that failed): the loss launch after all
-      g_loss_defer.pending = false;
-      const int rc2 = launch_loss_sum(g_loss_defer.src, g_loss_defer.n, g_loss_defer.scale, g_loss_defer.out, (hipStream_t)stream);
-      if (rc == DPRHOT_OK) rc = rc2;
-    }
-    return rc;
-  }
-  if (int rc = dprhot_sim_stats_f32(q, c, Qb, Cb, B, Nc, d, y, y_offset, colmask, inv_T, nullptr, workspace, workspace_bytes, stream))
-    return rc;
-  const WsLayout wl = ws_layout(B, Nc, d);
-  const FwdPlan fp = fwd_plan(B, Nc, d);
-  char* ws = static_cast<char*>(workspace);
-  StepSmallArgs a{reinterpret_cast<const float*>(ws + wl.logits), fp.splits, (size_t)B * Nc, B, Nc, d, y, y_offset, grad_scale,
-                  Qb, Cb, h_scale, d_scale, dQ, dC_part, S_out, row_loss, row_lse, loss_sum, G,
-                  g_packed.stamp_src != nullptr ? g_packed.rows_c : 0, g_packed.n_ctx, g_loss_scale};
-  // 16 columns of d per workgroup: every workgroup repeats the softmax, the narrow tile only shortens the GEMM / store tail
-  constexpr int tw = 16;
-  const size_t lds = step_small_lds(Nc, tw);
-  const int ncp = (Nc + 31) / 32 * 32;
-  const dim3 grid(d / tw), block(1024);
-  hipStream_t st = (hipStream_t)stream;
-  if (lds > 160 * 1024) return fail(DPRHOT_E_UNSUPPORTED, "small step: Nc=%d needs %zu bytes of LDS", Nc, lds);
-  // (the LDS of all these kernels grows with Nc: launch() raises the limit again when a larger shape follows a smaller one)
-  // DPRHOT_BY_SLABS instantiates NS == max(fp.splits, 1): the role-split kernels read exactly NS slabs and add them all, with no
-  // run-time look at the slab count (step_small.h: ss_load_slabs), so a plan outside 0 .. 4 must never reach the macro
-  if (fp.splits < 0 || fp.splits > 4)
-    return fail(DPRHOT_E_UNSUPPORTED, "small step: the plan has %d slabs, the launch reads max(splits, 1) <= 4", fp.splits);
-#define DPRHOT_BY_SLABS(LAUNCH, CPT) \
-  (fp.splits <= 1 ? LAUNCH(CPT, 1) : fp.splits == 2 ? LAUNCH(CPT, 2) : fp.splits == 3 ? LAUNCH(CPT, 3) : LAUNCH(CPT, 4))
-  // the role-split forms (step_small_kernel_roles, step_small_kernel_out): one row block, the multi-slab plans up to 768 columns
-  if (const int roles = opt(OPT_SMALL_STEP_ROLES); roles != 0 && B <= SS_ROWS && ncp <= 768) {
-    const int qtw = roles >= 2 && d % 32 == 0 ? 32 : 16;
-    // Form 3 hands the lead's outputs to workgroups of their own (a loss block and two row-store blocks in front of the grid).  A stamping launch (the packed step) keeps form
-    // 2: the loss goes into dC[m][0], whose owner -- the dC workgroup of column 0 -- needs the finished sum, so there the lead stays.
-    const bool outwg = roles == 3 && g_packed.stamp_src == nullptr;
-    const size_t rlds = step_roles_lds(Nc, qtw);  // (the maximum over the roles, the output role included)
-    const dim3 rgrid(d / 16 + 2 * (d / qtw) + (outwg ? SS_OUT_BLOCKS : 0));
-#define DPRHOT_SR_LAUNCH_K(KERN, CPT, NS, QTW) launch<KERN<CPT, NS, QTW>>(rgrid, block, rlds, st, a)
-#define DPRHOT_SR_LAUNCH_Q(CPT, NS, QTW) \
-  (outwg ? DPRHOT_SR_LAUNCH_K(step_small_kernel_out, CPT, NS, QTW) : DPRHOT_SR_LAUNCH_K(step_small_kernel_roles, CPT, NS, QTW))
-#define DPRHOT_SR_LAUNCH(CPT, NS) (qtw == 16 ? DPRHOT_SR_LAUNCH_Q(CPT, NS, 16) : DPRHOT_SR_LAUNCH_Q(CPT, NS, 32))
-    if (ncp <= 256) return DPRHOT_BY_SLABS(DPRHOT_SR_LAUNCH, 1);
-    if (ncp <= 512) return DPRHOT_BY_SLABS(DPRHOT_SR_LAUNCH, 2);
-    return DPRHOT_BY_SLABS(DPRHOT_SR_LAUNCH, 3);
-#undef DPRHOT_SR_LAUNCH
-#undef DPRHOT_SR_LAUNCH_Q
-#undef DPRHOT_SR_LAUNCH_K
-  }
-#define DPRHOT_SS_LAUNCH_N(CPT, NS, NRB) launch<step_small_kernel<CPT, tw, NS, NRB>>(grid, block, lds, st, a)
-#define DPRHOT_SS_LAUNCH(CPT, NS) (B <= SS_ROWS ? DPRHOT_SS_LAUNCH_N(CPT, NS, 1) : DPRHOT_SS_LAUNCH_N(CPT, NS, 2))
-  if (ncp <= 256) return DPRHOT_BY_SLABS(DPRHOT_SS_LAUNCH, 1);
-  if (ncp <= 512) return DPRHOT_BY_SLABS(DPRHOT_SS_LAUNCH, 2);
-  if (ncp <= 768) return DPRHOT_BY_SLABS(DPRHOT_SS_LAUNCH, 3);
-  return DPRHOT_SS_LAUNCH_N(5, 1, 1);  // (B <= 32 only: small_step_ok; above 768 columns the sim launch writes one slab: fwd_plan)
-#undef DPRHOT_SS_LAUNCH
-#undef DPRHOT_SS_LAUNCH_N
-#undef DPRHOT_BY_SLABS
+  StepPlan p;
+  if (int rc = step_admit(GC_FP32, nullptr, B, Nc, d, &p)) return rc;
+  return run_step(StepCtx{}, p, q, c, Qb, Cb, B, Nc, d, y, y_offset, colmask, inv_T, grad_scale, h_scale, d_scale, S_out, row_loss, row_lse, loss_sum,
+                  G, dQ, dC_part, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // World size > 1, everything after the all-gather in ONE call: the column mask is read from the packed buffer (no
@@ -1954,21 +2073,14 @@ int dprhot_inbatch_step_packed_f32(const float* q, const dprhot_bf16* gathered, 
                                    int d, const int64_t* y, float inv_T, float grad_scale, float h_scale, const float* d_scale,
                                    float* row_loss, float* row_lse, float* loss_sum, dprhot_bf16* G, float* dQ, float* dC_part,
                                    void* workspace, size_t workspace_bytes, void* stream) {
-  REQUIRE(q && gathered && Qb && y && loss_sum, "NULL pointer");
-  REQUIRE(W > 0 && rank >= 0 && rank < W && n_ctx > 0 && d > 0 && d % 8 == 0, "bad argument W=%d rank=%d n_ctx=%d d=%d", W, rank, n_ctx, d);
+  StepCtx cx;
   int rows_c = 0;
-  if (int rc = dprhot_packed_rows(n_ctx, d, &rows_c)) return rc;
-  PackedSpec ps;
-  ps.base = reinterpret_cast<const uint8_t*>(gathered);
-  ps.rows_c = rows_c;
-  ps.n_ctx = n_ctx;
-  ps.row_bytes = d * 2;
-  ps.stamp_src = loss_sum;
-  PackedScope scope(ps);
+  if (int rc = packed_spec(q, gathered, Qb, y, loss_sum, W, rank, n_ctx, d, &cx.packed, &rows_c)) return rc;
+  StepPlan p;
+  if (int rc = step_admit(GC_FP32, nullptr, B, W * rows_c, d, &p)) return rc;
   // the gathered buffer IS the context matrix: [W * rows_c, d] bf16, mask rows = always-masked columns
-  return dprhot_inbatch_step_f32(q, nullptr, Qb, const_cast<dprhot_bf16*>(gathered), B, W * rows_c, d, y, (int64_t)rank * rows_c,
-                                 nullptr, inv_T, grad_scale, h_scale, d_scale, nullptr, row_loss, row_lse, loss_sum, G, dQ, dC_part,
-                                 workspace, workspace_bytes, stream);
+  return run_step(cx, p, q, nullptr, Qb, const_cast<dprhot_bf16*>(gathered), B, W * rows_c, d, y, (int64_t)rank * rows_c, nullptr, inv_T, grad_scale,
+                  h_scale, d_scale, nullptr, row_loss, row_lse, loss_sum, G, dQ, dC_part, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- gradient all-reduce of the towers (reference hook: dpr_task.py:90-92) -------------------------------
@@ -1978,45 +2090,15 @@ static int gc_blocks(size_t groups) {
 }
 
 // ---- the step as the autograd operator runs it ----------------------------------------------------------------------------------
-static int train_dc_kind_ok(int dc_kind, int B, int Nc, int d) {
-  if (dc_kind == GC_FP32) return DPRHOT_OK;
-  if (dc_kind == GC_BF16 && sk_plan(B, Nc, d).ok) return DPRHOT_OK;  // the skinny step's dC units have a bf16 epilogue
-  return fail(DPRHOT_E_UNSUPPORTED, "train_step: dc_kind=%d at B=%d Nc=%d d=%d: this shape's plan writes fp32 dC_part only (ask for dc_kind = 2)", dc_kind,
-              B, Nc, d);
-}
-
-int dprhot_train_dq_slabs(int B, int Nc, int d, int* h_nslabs) {
-  REQUIRE(h_nslabs != nullptr, "NULL pointer");
-  if (int rc = check_shape(B, Nc, d)) return rc;
-  const SkPlan sk = sk_plan(B, Nc, d);
-  *h_nslabs = sk.ok && sk.nslices > 1 ? sk.nslices : 0;  // the other plans (and a one-slice few-rows plan) do not split dQ or combine it themselves
-  // where the step can run without the dScores (dprhot_step_wants_g = 0) its slabs are slice-normalised and need the row statistics to
-  // be combined: the step's own finishing launch does that, nothing is left to the caller
-  if (sk_fused_plan(sk, cdiv(Nc, SK_COLS), cdiv(Nc, 64), B, Nc, d).ok) *h_nslabs = 0;
-  return DPRHOT_OK;
-}
-
-static int train_dq_part_ok(const float* dq_part, int B, int Nc, int d) {
-  if (dq_part == nullptr) return DPRHOT_OK;
-  REQUIRE(aligned16(dq_part), "dq_part must be 16-byte aligned");
-  int n = 0;
-  if (int rc = dprhot_train_dq_slabs(B, Nc, d, &n)) return rc;
-  if (n == 0) return fail(DPRHOT_E_INVALID, "train_step: dq_part given but B=%d Nc=%d d=%d leaves no slabs (dprhot_train_dq_slabs = 0)", B, Nc, d);
-  return DPRHOT_OK;
-}
-
 int dprhot_train_step_f32(const float* q, const float* c, dprhot_bf16* Qb, dprhot_bf16* Cb, int B, int Nc, int d, const int64_t* y,
                           int64_t y_offset, const uint8_t* colmask, float inv_T, float grad_scale, float loss_scale, const float* d_scale,
                           float* row_loss, float* row_lse, float* loss_out, dprhot_bf16* G, float* dQ, float* dq_part, void* dC_part,
                           int dc_kind, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = check_shape(B, Nc, d)) return rc;
-  if (int rc = train_dc_kind_ok(dc_kind, B, Nc, d)) return rc;
-  if (int rc = train_dq_part_ok(dq_part, B, Nc, d)) return rc;
-  LossScaleScope ls(loss_scale);
-  DcKindScope dk(dc_kind == GC_BF16);
-  DqPartScope dp(dq_part);
-  return dprhot_inbatch_step_f32(q, c, Qb, Cb, B, Nc, d, y, y_offset, colmask, inv_T, grad_scale, 1.0f, d_scale, nullptr, row_loss, row_lse,
-                                 loss_out, G, dQ, static_cast<float*>(dC_part), workspace, workspace_bytes, stream);
+  StepPlan p;
+  if (int rc = step_admit(dc_kind, dq_part, B, Nc, d, &p)) return rc;
+  StepCtx cx{PackedSpec{}, loss_scale, dc_kind == GC_BF16, dq_part};
+  return run_step(cx, p, q, c, Qb, Cb, B, Nc, d, y, y_offset, colmask, inv_T, grad_scale, 1.0f, d_scale, nullptr, row_loss, row_lse, loss_out, G, dQ,
+                  static_cast<float*>(dC_part), workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int dprhot_train_step_packed_f32(const float* q, const dprhot_bf16* gathered, dprhot_bf16* Qb, int B, int W, int rank, int n_ctx, int d,
@@ -2026,13 +2108,13 @@ int dprhot_train_step_packed_f32(const float* q, const dprhot_bf16* gathered, dp
   REQUIRE(W > 0 && n_ctx > 0 && d > 0 && d % 8 == 0, "bad argument W=%d n_ctx=%d d=%d", W, n_ctx, d);
   int rows_c = 0;
   if (int rc = dprhot_packed_rows(n_ctx, d, &rows_c)) return rc;
-  if (int rc = train_dc_kind_ok(dc_kind, B, W * rows_c, d)) return rc;
-  if (int rc = train_dq_part_ok(dq_part, B, W * rows_c, d)) return rc;
-  LossScaleScope ls(loss_scale);
-  DcKindScope dk(dc_kind == GC_BF16);
-  DqPartScope dp(dq_part);
-  return dprhot_inbatch_step_packed_f32(q, gathered, Qb, B, W, rank, n_ctx, d, y, inv_T, grad_scale, 1.0f, d_scale, row_loss, row_lse, loss_out,
-                                        G, dQ, static_cast<float*>(dC_part), workspace, workspace_bytes, stream);
+  StepPlan p;
+  if (int rc = step_admit(dc_kind, dq_part, B, W * rows_c, d, &p)) return rc;
+  StepCtx cx{PackedSpec{}, loss_scale, dc_kind == GC_BF16, dq_part};
+  if (int rc = packed_spec(q, gathered, Qb, y, loss_out, W, rank, n_ctx, d, &cx.packed, &rows_c)) return rc;
+  return run_step(cx, p, q, nullptr, Qb, const_cast<dprhot_bf16*>(gathered), B, W * rows_c, d, y, (int64_t)rank * rows_c, nullptr, inv_T, grad_scale,
+                  1.0f, d_scale, nullptr, row_loss, row_lse, loss_out, G, dQ, static_cast<float*>(dC_part), workspace, workspace_bytes,
+                  (hipStream_t)stream);
 }
 
 int dprhot_rescale_grads(float* dQ, size_t n_dq, const float* dq_part, int nslabs, void* dC, size_t n_dc, int dc_kind, const float* go,

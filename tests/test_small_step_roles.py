@@ -145,7 +145,7 @@ def test_step_same_bits_as_unsplit_kernel(B, Nc, d, T, mask_frac, dev, roles):
 @pytest.mark.parametrize("d", [768, 1024])
 def test_packed_step_same_bits_with_loss_stamp(d, dev, roles):
     """dprhot_inbatch_step_packed_f32 with W = 1 at a shape of the small step: the lead workgroup stamps the finished loss into
-    dC[n_ctx][0] (g_packed.stamp_src set), behind the one barrier only that workgroup keeps."""
+    dC[n_ctx][0] (the packed step: StepCtx::packed.stamp_src set), behind the one barrier only that workgroup keeps."""
     import numpy as np
     import torch
 
