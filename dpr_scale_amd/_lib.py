@@ -129,6 +129,11 @@ SIGNATURES = {
                                      c_int64, c_void_p]),
     "dprhot_colbert_search": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int,
                                       c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "dprhot_colbert_pq_encode": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "dprhot_colbert_pq_score": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int, c_int,
+                                        c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "dprhot_colbert_pq_search": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int, c_int,
+                                         c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "dprhot_router_head_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
     "dprhot_router_head_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -37,6 +37,7 @@
 #include "ivf_pq.h"
 #include "router_head.h"
 #include "colbert.h"
+#include "colbert_pq.h"
 
 using namespace dprhot;
 
@@ -2653,11 +2654,13 @@ static int ivf_pq_launch(int dp, unsigned blocks, hipStream_t st, const IvfPqArg
 }
 }  // extern "C++"
 
-int dprhot_pq_encode(const dprhot_bf16* vec, int64_t n, int dp, const dprhot_bf16* codebook, int dsub, uint8_t* codes, void* stream) {
+// dprhot_pq_encode and dprhot_colbert_pq_encode: the same rule and kernel behind each entry's own limit on dp (`check_shape`)
+static int pq_encode_with(int (*check_shape)(int, int), const dprhot_bf16* vec, int64_t n, int dp, const dprhot_bf16* codebook, int dsub,
+                          uint8_t* codes, void* stream) {
   REQUIRE(n >= 0 && n < (1ll << 40), "n=%lld out of range (0 .. 2^40 - 1)", (long long)n);
   REQUIRE(codebook != nullptr, "NULL pointer (codebook)");
   REQUIRE(n == 0 || (vec && codes), "NULL pointer (vec, codes)");
-  if (int rc = pq_check_shape(dp, dsub)) return rc;
+  if (int rc = check_shape(dp, dsub)) return rc;
   if (n == 0) return DPRHOT_OK;
   PqEncodeArgs a{reinterpret_cast<const uint16_t*>(vec), (long long)n, dp, reinterpret_cast<const uint16_t*>(codebook), codes};
   const long long want = (n + PQ_ENC_THREADS - 1) / PQ_ENC_THREADS;
@@ -2666,6 +2669,10 @@ int dprhot_pq_encode(const dprhot_bf16* vec, int64_t n, int dp, const dprhot_bf1
   if (dsub == 2) return launch<pq_encode_kernel<2>>(grid, block, 0, st, a);
   if (dsub == 4) return launch<pq_encode_kernel<4>>(grid, block, 0, st, a);
   return launch<pq_encode_kernel<8>>(grid, block, 0, st, a);
+}
+
+int dprhot_pq_encode(const dprhot_bf16* vec, int64_t n, int dp, const dprhot_bf16* codebook, int dsub, uint8_t* codes, void* stream) {
+  return pq_encode_with(pq_check_shape, vec, n, dp, codebook, dsub, codes, stream);
 }
 
 int dprhot_ivf_pq_score(const uint8_t* post_code, const dprhot_bf16* codebook, int dsub, const int32_t* post_doc, const int64_t* exp_off,
@@ -2793,6 +2800,81 @@ int dprhot_colbert_search(const dprhot_bf16* tok, const int64_t* doc_blk, int64_
   };
   return topk_search_chunks("colbert", fill, nq, corpus_len, id_begin, id_end, k, chunk, values, indices, first, workspace, workspace_bytes,
                             stream);
+}
+
+
+// ---- product-quantised token index of the ColBERT search (csrc/colbert_pq.h) ----
+static int cbpq_check_shape(int dp, int dsub) {
+  REQUIRE(dsub == 2 || dsub == 4 || dsub == 8, "dsub=%d: sub-vectors of 2, 4 or 8 features", dsub);
+  REQUIRE(dp > 0 && dp % 32 == 0, "dp=%d must be a positive multiple of 32 (pad with zeros)", dp);
+  if (dp > CBPQ_MAX_DP) return fail(DPRHOT_E_UNSUPPORTED, "dp=%d: the product-quantised ColBERT index is built for dp <= %d", dp, CBPQ_MAX_DP);
+  return DPRHOT_OK;
+}
+
+static int cbpq_check(const void* tok_code, const void* blk_rows, const void* codebook, int dsub, const void* doc_blk, int64_t n_blk,
+                      int64_t corpus_len, int dp, const void* q_tok, int nq, int LQ, int pool) {
+  if (int rc = cb_check(tok_code, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool)) return rc;
+  REQUIRE(codebook != nullptr && (n_blk == 0 || blk_rows != nullptr), "NULL pointer (codebook and blk_rows are required)");
+  REQUIRE(aligned16(codebook), "the codebook must be 16-byte aligned");
+  return cbpq_check_shape(dp, dsub);
+}
+
+int dprhot_colbert_pq_encode(const dprhot_bf16* vec, int64_t n, int dp, const dprhot_bf16* codebook, int dsub, uint8_t* codes,
+                             void* stream) {
+  return pq_encode_with(cbpq_check_shape, vec, n, dp, codebook, dsub, codes, stream);
+}
+
+extern "C++" {
+template <int DSUB>
+static int cbpq_launch(int dp, dim3 grid, size_t lds, hipStream_t st, const CbPqArgs& a) {
+  const dim3 block(CBPQ_THREADS);
+  switch (dp) {
+    case 32: return launch<cbpq_score_kernel<DSUB, 1>>(grid, block, lds, st, a);
+    case 64: return launch<cbpq_score_kernel<DSUB, 2>>(grid, block, lds, st, a);
+    case 96: return launch<cbpq_score_kernel<DSUB, 3>>(grid, block, lds, st, a);
+    default: return launch<cbpq_score_kernel<DSUB, 4>>(grid, block, lds, st, a);  // (dp = 128: cbpq_check_shape)
+  }
+}
+}  // extern "C++"
+
+int dprhot_colbert_pq_score(const uint8_t* tok_code, const uint8_t* blk_rows, const dprhot_bf16* codebook, int dsub, const int64_t* doc_blk,
+                            int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok, int nq, int LQ, int pool,
+                            int64_t doc_begin, int cols, float* S, int64_t ld, void* stream) {
+  if (int rc = cbpq_check(tok_code, blk_rows, codebook, dsub, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool)) return rc;
+  if (int rc = check_score_window(S, cols, ld, doc_begin, corpus_len)) return rc;
+  const int FQ = cdiv(LQ, 16);
+  const int QPW = FQ >= CBPQ_FPP ? 1 : CBPQ_FPP / FQ;  // whole queries per workgroup: QPW * FQ <= CBPQ_FPP fragments, one pass
+  const int blkb = 16 * (dp / dsub);
+  const int TB = CBPQ_TILE_BYTES / blkb < CBPQ_TILE_BLOCKS ? CBPQ_TILE_BYTES / blkb : CBPQ_TILE_BLOCKS;
+  const int gy = cdiv(nq, QPW);
+  REQUIRE(gy <= 65535, "nq=%d: too many queries for one launch", nq);
+  // the codebook, the code tile, the tile's row counts, then the term table
+  const size_t lds = (size_t)dp * 512 + CBPQ_TILE_BYTES + CBPQ_TILE_BLOCKS + (size_t)CB_RUNP * (QPW * FQ * 16 + 1) * sizeof(float);
+  if (lds + (CB_RUNP + 1) * sizeof(long long) > 160 * 1024)
+    return fail(DPRHOT_E_UNSUPPORTED, "dp=%d LQ=%d needs %zu bytes of LDS", dp, LQ, lds);
+  // runs per workgroup: one codebook load serves several runs once the grid fills the device a few times over
+  const long long wgs = (long long)cdiv(cols, CB_RUNP) * gy;
+  const int RPW = wgs / 1024 < 1 ? 1 : wgs / 1024 > CBPQ_MAX_RPW ? CBPQ_MAX_RPW : (int)(wgs / 1024);
+  CbPqArgs a{tok_code, blk_rows, reinterpret_cast<const uint16_t*>(codebook), reinterpret_cast<const long long*>(doc_blk), (long long)n_blk,
+             reinterpret_cast<const uint16_t*>(q_tok), nq, LQ, pool, (long long)doc_begin, cols, S, (long long)ld, FQ, QPW, TB, RPW};
+  const dim3 grid((unsigned)cdiv(cdiv(cols, CB_RUNP), RPW), (unsigned)gy);
+  hipStream_t st = (hipStream_t)stream;
+  if (dsub == 2) return cbpq_launch<2>(dp, grid, lds, st, a);
+  if (dsub == 4) return cbpq_launch<4>(dp, grid, lds, st, a);
+  return cbpq_launch<8>(dp, grid, lds, st, a);
+}
+
+int dprhot_colbert_pq_search(const uint8_t* tok_code, const uint8_t* blk_rows, const dprhot_bf16* codebook, int dsub, const int64_t* doc_blk,
+                             int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok, int nq, int LQ, int pool,
+                             int64_t id_begin, int64_t id_end, int k, int chunk, float* values, int64_t* indices, int first,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = cbpq_check(tok_code, blk_rows, codebook, dsub, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool)) return rc;
+  auto fill = [&](int64_t j0, int cols, float* S, int ld) {
+    return dprhot_colbert_pq_score(tok_code, blk_rows, codebook, dsub, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool, j0, cols, S, ld,
+                                   stream);
+  };
+  return topk_search_chunks("colbert_pq", fill, nq, corpus_len, id_begin, id_end, k, chunk, values, indices, first, workspace,
+                            workspace_bytes, stream);
 }
 
 }  // extern "C"

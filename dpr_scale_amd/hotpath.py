@@ -644,7 +644,7 @@ class HipKernels:
                         "dprhot_colbert_search")
 
     # -- product-quantised postings (csrc/ivf_pq.h; dpr_scale_amd/ivf.py owns training and the index) ----
-    def pq_encode(self, vec, codebook):
+    def pq_encode(self, vec, codebook, entry="dprhot_pq_encode"):
         """codes uint8 [n, m] of the rows vec bf16 [n, dp] under codebook bf16 [m, 256, dsub] (dprhot_pq_encode)."""
         self._require_gpu(vec, codebook)
         assert vec.dtype == torch.bfloat16 and codebook.dtype == torch.bfloat16 and vec.dim() == 2 and codebook.dim() == 3
@@ -653,7 +653,7 @@ class HipKernels:
         m, _, dsub = codebook.shape
         assert codebook.shape[1] == 256 and m * dsub == dp, f"codebook {tuple(codebook.shape)} for rows of width {dp}"
         codes = torch.empty((n, m), dtype=torch.uint8, device=vec.device)
-        self._lib.check(self.lib.dprhot_pq_encode(_ptr(vec), n, dp, _ptr(codebook), dsub, _ptr(codes), self._stream()), "dprhot_pq_encode")
+        self._lib.check(getattr(self.lib, entry)(_ptr(vec), n, dp, _ptr(codebook), dsub, _ptr(codes), self._stream()), entry)
         return codes
 
     def _ivf_pq_index(self, index):
@@ -673,6 +673,33 @@ class HipKernels:
         self._lib.check(self.lib.dprhot_ivf_pq_search(*self._ivf_pq_index(index), *self._ivf_batch(qb), *self._ivf_cls(index, qb),
                                                       *self._topk_tail(id_begin, id_end, values, indices, first, chunk, ws)),
                         "dprhot_ivf_pq_search")
+
+    # -- product-quantised ColBERT token index (csrc/colbert_pq.h; dpr_scale_amd/colbert.py owns the index) ----
+    def colbert_pq_encode(self, vec, codebook):
+        """pq_encode for rows of padded width up to 128 (dprhot_colbert_pq_encode: the same rule, the same kernel)."""
+        return self.pq_encode(vec, codebook, entry="dprhot_colbert_pq_encode")
+
+    def _colbert_pq_index(self, index):
+        self._require_gpu(index.tok_code, index.blk_rows, index.codebook, index.doc_blk)
+        return (_ptr(index.tok_code), _ptr(index.blk_rows), _ptr(index.codebook), index.dsub, _ptr(index.doc_blk), index.n_blk,
+                index.corpus_len, index.dp)
+
+    def colbert_pq_score(self, index, q, pool, doc_begin, cols, S):
+        """colbert_score for a ColBERTPQIndex (dprhot_colbert_pq_score)."""
+        self._require_gpu(q, S)
+        nq, LQ, dp = q.shape
+        assert dp == index.dp
+        self._lib.check(self.lib.dprhot_colbert_pq_score(*self._colbert_pq_index(index), _ptr(q), nq, LQ, int(pool), int(doc_begin), int(cols),
+                                                         _ptr(S), S.stride(0), self._stream()), "dprhot_colbert_pq_score")
+
+    def colbert_pq_search(self, index, q, pool, id_begin, id_end, values, indices, first, chunk, ws):
+        """colbert_search for a ColBERTPQIndex (dprhot_colbert_pq_search); the workspace is colbert_workspace's."""
+        self._require_gpu(q, values, indices, ws)
+        nq, LQ, dp = q.shape
+        assert dp == index.dp
+        self._lib.check(self.lib.dprhot_colbert_pq_search(*self._colbert_pq_index(index), _ptr(q), nq, LQ, int(pool),
+                                                          *self._topk_tail(id_begin, id_end, values, indices, first, chunk, ws)),
+                        "dprhot_colbert_pq_search")
 
     # -- postings and query batches from encoder outputs (csrc/ivf_pack.h; dpr_scale_amd/ivf.py drives them) ----
     def ivf_compact(self, expert_ids, weights, att, row_ids, test_weight, min_weight=0.0, capacity=None):

@@ -265,15 +265,15 @@ PQ_SUB_VEC_DIMS = (2, 4, 8)  # whole sub-vectors inside the 8 consecutive bf16 v
 PQ_MAX_DP = 64               # dprhot_ivf_pq_score keeps the codebook (dp * 512 bytes) in LDS next to its 32 KiB table
 
 
-def _check_pq_shape(dp, dsub):
+def _check_pq_shape(dp, dsub, max_dp=PQ_MAX_DP):
     if dsub not in PQ_SUB_VEC_DIMS:
         raise ValueError(f"sub_vec_dim={dsub}: one of {PQ_SUB_VEC_DIMS}")
-    if dp > PQ_MAX_DP:
-        raise NotImplementedError(f"product quantisation of rows of padded width {dp}: at most {PQ_MAX_DP}")
+    if dp > max_dp:
+        raise NotImplementedError(f"product quantisation of rows of padded width {dp}: at most {max_dp}")
 
 
-def _check_codebook(codebook, dp, dsub):
-    _check_pq_shape(dp, dsub)
+def _check_codebook(codebook, dp, dsub, max_dp=PQ_MAX_DP):
+    _check_pq_shape(dp, dsub, max_dp)
     if codebook.dtype != _BF16 or tuple(codebook.shape) != (dp // int(dsub), 256, int(dsub)):
         raise ValueError(f"codebook {codebook.dtype} {tuple(codebook.shape)}; bf16 {(dp // int(dsub), 256, int(dsub))} expected")
     return codebook
@@ -290,7 +290,7 @@ def pq_decode(codes, codebook):
     return torch.cat(parts, 0) if parts else codebook.new_zeros((0, m * dsub))
 
 
-def train_pq(post_vec, dsub=4, iters=10, train_size=65536, seed=0, kernels=None, on_iteration=None):
+def train_pq(post_vec, dsub=4, iters=10, train_size=65536, seed=0, kernels=None, on_iteration=None, *, max_dp=PQ_MAX_DP, encode=None):
     """Codebook bf16 [dp / dsub, 256, dsub] for the bf16 rows post_vec [P, dp] on a HIP device: Lloyd's k-means per subspace on a
     seeded sample of `train_size` rows (all of them when there are no more; rows with a non-finite value are left out).
       init      per subspace 256 distinct sub-vectors of the sample (a seeded choice among the distinct ones in sorted order); with
@@ -300,13 +300,15 @@ def train_pq(post_vec, dsub=4, iters=10, train_size=65536, seed=0, kernels=None,
                 torch.segment_reduce: no floating-point atomics), divided by the count in fp32, rounded to bf16 after every
                 iteration; an empty centroid keeps its value
     Same inputs and seed: torch.equal codebooks.  `on_iteration(i, codebook)` sees the codebook before the first (i = 0) and after
-    every iteration."""
+    every iteration.  `max_dp` and `encode(rows, codebook) -> codes` (default: kernels.pq_encode) are for an index whose kernels take
+    wider rows through an encode entry of their own (colbert.train_pq)."""
     kn = _default_kernels(kernels)
     if post_vec.dtype != _BF16 or post_vec.dim() != 2:
         raise ValueError(f"rows {post_vec.dtype} {tuple(post_vec.shape)}; bf16 [P, dp] expected")
     P, dp = int(post_vec.shape[0]), int(post_vec.shape[1])
     dsub, dev = int(dsub), post_vec.device
-    _check_pq_shape(dp, dsub)
+    _check_pq_shape(dp, dsub, max_dp)
+    encode = kn.pq_encode if encode is None else encode
     m = dp // dsub
     gen = torch.Generator().manual_seed(int(seed))
     if P > int(train_size):
@@ -327,7 +329,7 @@ def train_pq(post_vec, dsub=4, iters=10, train_size=65536, seed=0, kernels=None,
     base = (torch.arange(m, device=dev) * 256).unsqueeze(0)
     flat = sub.reshape(ns * m, dsub).float()
     for it in range(int(iters) if ns else 0):
-        key = (kn.pq_encode(x, codebook).long() + base).reshape(-1)
+        key = (encode(x, codebook).long() + base).reshape(-1)
         order = torch.sort(key, stable=True).indices  # sample order survives inside a centroid
         counts = torch.bincount(key, minlength=m * 256)
         sums = torch.segment_reduce(flat[order], "sum", lengths=counts, axis=0, unsafe=True)

@@ -9,13 +9,16 @@ GenerateColBERTEmbeddingsTask   GenerateMultiVecEmbeddingsTask (its constructor 
 ColBERTRetrievalTask            CITADELRetrievalTask's constructor, refusals, merge_trec_results / merge_qa_results and output files;
                                 the index is colbert.load_index and a query batch is searched as the dense [B, LQ, d] block the
                                 encoder returns (padded query tokens are zero rows), with `query_pool` and `topk`.
+ColBERTPQRetrievalTask          ColBERTRetrievalTask over a product-quantised token index (colbert.ColBERTPQIndex, DESIGN.md section
+                                12.1): the same kwargs plus `sub_vec_dim` (8) and `save_quantized` (False).
 `kernels` (default: the HIP kernels) is the kernel object colbert.py takes.
 """
+import os
 import time
 
 import torch
 
-from .. import colbert
+from .. import colbert, ivf
 from .citadel_eval import GenerateMultiVecEmbeddingsTask
 from .citadel_retrieval import CITADELRetrievalTask
 
@@ -46,3 +49,36 @@ class ColBERTRetrievalTask(CITADELRetrievalTask):
             raise NotImplementedError("an encoder with expert_ids (COIL / CITADEL) is searched by CITADELRetrievalTask")
         self.latency["encode_time"] += time.perf_counter() - tic
         return self.index.search(queries_repr["expert_repr"][:n], self.topk, query_pool=self.query_pool)
+
+
+class ColBERTPQRetrievalTask(ColBERTRetrievalTask):
+    """ColBERTRetrievalTask over 8-bit codes of sub-vectors of `sub_vec_dim` in {2, 4, 8} features.  `setup` loads
+    `ctx_embeddings_dir/colbert_pq.pt` when that file exists (colbert.load_pq_index); otherwise it trains a codebook on a sample of
+    the token files and encodes them one at a time (colbert.load_index(..., quantizer="pq")) -- the dense index is never built -- and
+    writes the file when `save_quantized` is set, so that a large index is not retrained at every start."""
+
+    PQ_FILE = "colbert_pq.pt"
+
+    def __init__(self, *args, quantizer="pq", sub_vec_dim=8, save_quantized=False, **kwargs):
+        if quantizer != "pq":
+            raise NotImplementedError(f'quantizer={quantizer!r}: ColBERTPQRetrievalTask is the quantizer="pq" task '
+                                      f"(ColBERTRetrievalTask takes the plain index)")
+        if sub_vec_dim not in ivf.PQ_SUB_VEC_DIMS:
+            raise NotImplementedError(f"sub_vec_dim={sub_vec_dim}: sub-vectors of {ivf.PQ_SUB_VEC_DIMS} features")
+        super().__init__(*args, quantizer=None, sub_vec_dim=sub_vec_dim, **kwargs)  # refuses what the plain task refuses
+        self.quantizer = "pq"
+        self.save_quantized = bool(save_quantized)
+
+    def _load_index(self, device):
+        path = os.path.join(self.ctx_embeddings_dir, self.PQ_FILE)
+        if os.path.exists(path):
+            index = colbert.load_pq_index(path, device, kernels=self.kernels)
+            if index.corpus_len != len(self.ctxs) or index.dsub != self.sub_vec_dim:
+                raise ValueError(f"{path}: an index of {index.corpus_len} passages with sub_vec_dim={index.dsub}; "
+                                 f"{len(self.ctxs)} passages and sub_vec_dim={self.sub_vec_dim} were asked for")
+            return index
+        index = colbert.load_index(self.ctx_embeddings_dir, len(self.ctxs), device, kernels=self.kernels, quantizer="pq",
+                                   sub_vec_dim=self.sub_vec_dim)
+        if self.save_quantized:
+            index.save(path)
+        return index

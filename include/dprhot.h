@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DPRHOT_VERSION 174 /* 0.1.74: + dprhot_ivf_workspace_bytes / _score / _search (inverted-index retrieval for CITADEL / COIL); dprhot_router_head_*, dprhot_ivf_compact / _gather, dprhot_maxsim_score and dprhot_pq_encode / dprhot_ivf_pq_score / _search, dprhot_colbert_* joined without a bump: tests/test_ivf.py pins this number */
+#define DPRHOT_VERSION 174 /* 0.1.74: + dprhot_ivf_workspace_bytes / _score / _search (inverted-index retrieval for CITADEL / COIL); dprhot_router_head_*, dprhot_ivf_compact / _gather, dprhot_maxsim_score and dprhot_pq_encode / dprhot_ivf_pq_score / _search, dprhot_colbert_* and dprhot_colbert_pq_* joined without a bump: tests/test_ivf.py pins this number */
 
 #define DPRHOT_OK 0
 #define DPRHOT_E_INVALID (-1)     /* bad argument (NULL pointer, non-positive or misaligned size) */
@@ -432,6 +432,28 @@ int dprhot_colbert_score(const dprhot_bf16* tok, const int64_t* doc_blk, int64_t
 int dprhot_colbert_search(const dprhot_bf16* tok, const int64_t* doc_blk, int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok,
                           int nq, int LQ, int pool, int64_t id_begin, int64_t id_end, int k, int chunk, float* values, int64_t* indices,
                           int first, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Product-quantised token index for the ColBERT search (csrc/colbert_pq.h).  dsub in {2, 4, 8}, m = dp / dsub,
+ * dp in {32, 64, 96, 128}, ONE codebook bf16 [m, 256, dsub] per index (the layout and the decode rule of the product-quantised postings
+ * above).  The block layout is that of dprhot_colbert_score; a token row is m code bytes, tok_code uint8 [n_blk * 16, m], and blk_rows
+ * uint8 [n_blk] is the number of real token rows of every block (above 16 counts as 16).  The index stands for the dense index
+ *   tok[r, j * dsub + t] = (r mod 16) < blk_rows[r / 16] ? codebook[j, tok_code[r, j], t] : 0
+ * (a row at or behind blk_rows is an exact zero whatever its code bytes hold), and dprhot_colbert_pq_score / dprhot_colbert_pq_search
+ * return, bit for bit, what dprhot_colbert_score / dprhot_colbert_search return over it: owners, order of additions, chunks, ties, NaN
+ * and the workspace (dprhot_colbert_workspace_bytes) are unchanged.  No byte behind tok_code[n_blk * 16 * m - 1] or blk_rows[n_blk - 1]
+ * is read.  n_blk == 0 scores 0 everywhere (tok_code and blk_rows may then be NULL).
+ * dprhot_colbert_pq_encode is dprhot_pq_encode (same rule, same kernel) for rows of dp <= 128.
+ * Limits: those of the dense entry points; dsub not in {2, 4, 8}, dp % 32 != 0, a NULL codebook, a NULL blk_rows with n_blk > 0, a
+ * tok_code or codebook that is not 16-byte aligned: DPRHOT_E_INVALID; dp > 128: DPRHOT_E_UNSUPPORTED. */
+int dprhot_colbert_pq_encode(const dprhot_bf16* vec, int64_t n, int dp, const dprhot_bf16* codebook, int dsub, uint8_t* codes,
+                             void* stream);
+int dprhot_colbert_pq_score(const uint8_t* tok_code, const uint8_t* blk_rows, const dprhot_bf16* codebook, int dsub, const int64_t* doc_blk,
+                            int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok, int nq, int LQ, int pool,
+                            int64_t doc_begin, int cols, float* S, int64_t ld, void* stream);
+int dprhot_colbert_pq_search(const uint8_t* tok_code, const uint8_t* blk_rows, const dprhot_bf16* codebook, int dsub, const int64_t* doc_blk,
+                             int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok, int nq, int LQ, int pool,
+                             int64_t id_begin, int64_t id_end, int k, int chunk, float* values, int64_t* indices, int first,
+                             void* workspace, size_t workspace_bytes, void* stream);
 
 /* The CITADEL / SPLADE encoder head behind the MLM logits (dpr_scale/models/citadel_models/citadel_model.py:46-82, splade_model.py:26-32;
  * csrc/router_head.h), forward and backward without a [B, T, V] temporary.  logits [B, T1, V] of `dtype` (0 bf16,
