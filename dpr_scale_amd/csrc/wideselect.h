@@ -43,16 +43,19 @@ struct WselArgs {
   int64_t* out_i;
 };
 
-// candidate e of a row: e < nstate -> state slot e, else chunk column e - nstate; returns false for an unfilled state slot
+// candidate e of a row: e < nstate -> state slot e, else chunk column e - nstate; returns false for an unfilled state slot and for
+// a NaN score of either sign (NaN never qualifies, as in rowwise.h: wsel_key would rank +NaN above +inf and -NaN below -inf, and
+// tk_before is no total order with a NaN in it) -- so NaN reaches no histogram, no collecting pass and no sort, and the counts
+// (s_total, kprime) are those of the real candidates: a row with fewer than k of them leaves its tail unfilled
 __device__ __forceinline__ bool wsel_cand(const WselArgs& p, int row, int nstate, int e, float& v, long long& id) {
   if (e < nstate) {
     id = p.idx[(size_t)row * p.k + e];
     v = p.vals[(size_t)row * p.k + e];
-    return id >= 0;
+    return id >= 0 && v == v;
   }
   v = p.S[(size_t)row * p.ld + (e - nstate)];
   id = p.col_offset + (e - nstate);
-  return true;
+  return v == v;
 }
 
 __global__ __launch_bounds__(WSEL_THREADS) void wsel_select_kernel(WselArgs p) {

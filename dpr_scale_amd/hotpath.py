@@ -1438,15 +1438,19 @@ class CorpusSearch:
 
     def _fold_rows_torch(self, rows, S, first_col):
         """Exact fold of one chunk into the state of `rows` (None: all) with torch's stable sorts, in the same total order (score desc,
-        id asc): the library's escape for degenerate rows, and the whole path for stand-in kernels."""
+        id asc): the library's escape for degenerate rows, and the whole path for stand-in kernels.  A NaN score is never selected
+        (include/dprhot.h): it enters as an unfilled slot (-inf / -1), which ranks behind every real candidate."""
         sel = slice(None) if rows is None else rows
         S = S[sel]
         vals, idx = self.values[sel], self.indices[sel]
         cols = S.shape[1]
         kk = min(self.k, cols)
-        order = torch.sort(S, dim=1, descending=True, stable=True).indices[:, :kk]  # ties: lower column first
+        nan = torch.isnan(S)
+        S = S.masked_fill(nan, float("-inf"))
+        order = torch.sort(S, dim=1, descending=True, stable=True).indices  # ties: lower column first
+        order = torch.gather(order, 1, torch.sort(torch.gather(nan, 1, order).to(torch.uint8), dim=1, stable=True).indices)[:, :kk]  # NaN last
         v = torch.gather(S, 1, order)
-        ids = order + first_col
+        ids = torch.where(torch.gather(nan, 1, order), torch.full_like(order, -1), order + first_col)
         allv, alli = torch.cat([vals, v], 1), torch.cat([idx, ids], 1)
         alli_key = torch.where(alli < 0, torch.full_like(alli, torch.iinfo(torch.int64).max), alli)  # empty slots last
         o1 = torch.sort(alli_key, dim=1, stable=True).indices

@@ -255,7 +255,9 @@ int dprhot_inbatch_step_packed_f32(const float* q, const dprhot_bf16* gathered, 
 
 /* Brute-force retrieval epilogue (run_retrieval_pytorch.py:149-150): per row, the k largest scores and
  * their column indices, descending, ties by lower column index.  k <= 4096 (the reference's recipes use --topk 100 and 1000; up to
- * 256 and up to 1024 run on 12 / 48 KB of LDS per row, beyond that on 96 KB: 8192 sort slots), k <= cols. */
+ * 256 and up to 1024 run on 12 / 48 KB of LDS per row, beyond that on 96 KB: 8192 sort slots), k <= cols.  A NaN score (either
+ * sign, any payload) is never selected: a row with fewer than k other scores leaves its tail unfilled (-inf / -1).  +0 and -0 tie
+ * (the column decides); a selected value keeps its bit pattern. */
 int dprhot_topk(const float* S, int rows, int cols, int k, float* values, int64_t* indices, void* stream);
 
 /* The same as a streaming update, for a corpus that is scored in pieces (the shard loop of
@@ -263,13 +265,16 @@ int dprhot_topk(const float* S, int rows, int cols, int k, float* values, int64_
  * folds the scores S[rows][0..cols) (row stride ld, global column index = col_offset + j) into the running
  * per-row top-k state values/indices [rows,k] (sorted; total order score desc, column asc).  first != 0 starts
  * from an empty state (slots not yet filled hold -inf / -1).  The result after any sequence of updates equals
- * dprhot_topk of the concatenated score matrix. */
+ * dprhot_topk of the concatenated score matrix.  A NaN score is never selected, here as there: a row that has seen fewer than k
+ * other candidates keeps an unfilled tail (-inf / -1), however many NaN scores it has seen. */
 int dprhot_topk_update(const float* S, int rows, int cols, int64_t ld, int64_t col_offset, int k, float* values,
                        int64_t* indices, int first, void* stream);
 
 /* The same update for ANY k (run_retrieval_pytorch.py:69 takes any --topk): the state lives in HBM, nothing has to fit in LDS
  * (csrc/wideselect.h: exact radix select over state + chunk, then only the k winners are sorted -- blocks of 4096 in LDS, merge
- * passes over HBM; ties exact at any multiplicity: the select continues over the ids).  workspace:
+ * passes over HBM; ties exact at any multiplicity: the select continues over the ids).  The same contract at every k, bit for bit
+ * what dprhot_topk_update leaves where both take the k: a NaN score is never selected (it is no candidate: it reaches neither the
+ * select's counts nor the sorts), and a row with fewer than k other candidates leaves its tail unfilled (-inf / -1).  workspace:
  * dprhot_topk_wide_workspace_bytes(rows, k) bytes; its first rows * 8 32-bit words are one record per row whose word 5 is an error
  * word -- a row with a non-zero one keeps its old state (no such condition is defined at present: always 0). */
 int dprhot_topk_wide_workspace_bytes(int rows, int k, size_t* h_bytes);

@@ -148,7 +148,8 @@ def topk_merge(state, S, col_offset, k):
     """The shard loop of run_retrieval_pytorch.py:196-243 with the re-merge of :272-277 restated as a fold:
     state = (values [rows,k], ids [rows,k]) of everything scored so far (or None), S = scores of the next
     piece whose columns carry the ids col_offset + j.  Same frozen order (score desc, id asc); unfilled slots
-    are (-inf, -1).  Folding pieces in increasing id order equals topk_stable of the concatenation."""
+    are (-inf, -1).  Folding pieces in increasing id order equals topk_stable of the concatenation.  A NaN score is never
+    selected (include/dprhot.h): it is dropped like an unfilled slot, so a row with fewer than k other candidates keeps an unfilled tail."""
     S = np.asarray(S, dtype=np.float32)
     rows = S.shape[0]
     ids = np.broadcast_to(col_offset + np.arange(S.shape[1], dtype=np.int64), S.shape)
@@ -157,6 +158,9 @@ def topk_merge(state, S, col_offset, k):
         keep = np.asarray(i0) >= 0
         S = np.concatenate([np.where(keep, v0, -np.inf).astype(np.float32), S], axis=1)
         ids = np.concatenate([np.where(keep, i0, np.iinfo(np.int64).max), ids], axis=1)
+    nan = np.isnan(S)
+    S = np.where(nan, np.float32(-np.inf), S)
+    ids = np.where(nan, np.iinfo(np.int64).max, ids)
     order = np.lexsort((ids, -S), axis=1)[:, :k]  # primary key -S (desc score), secondary id asc
     v = np.take_along_axis(S, order, axis=1)
     i = np.take_along_axis(ids, order, axis=1)

@@ -81,7 +81,8 @@ def test_dq_slices_of_the_plan_without_the_dscores_launch_cover_every_step_once(
 # k-th best by four radix passes over an order-preserving 32-bit key (most significant byte first, each pass counting only the
 # entries that share the prefix found so far), then -- when only some of the entries AT T are taken -- the id of the last one
 # taken by the same radix select over the ties' ids (smallest first: run_retrieval_pytorch.py's order is value descending, ties by
-# lower id).  An entry is selected iff key > T, or key == T and id <= id_cut.
+# lower id).  An entry is selected iff key > T, or key == T and id <= id_cut.  A NaN score is no candidate (wsel_cand): its key would
+# rank above +inf (positive NaN) or below -inf (negative NaN), so it is left out before any count is taken.
 # ---------------------------------------------------------------------------------------------------------------------
 def _wsel_key(v):
     u = np.asarray(v, dtype=np.float32).view(np.uint32).copy()
@@ -91,10 +92,16 @@ def _wsel_key(v):
 
 
 def _wsel_select(values, ids, k):
+    cand = ~np.isnan(np.asarray(values, dtype=np.float32))  # wsel_cand
+    sel = np.zeros(len(cand), dtype=bool)
+    if cand.any():
+        sel[cand] = _wsel_select_candidates(np.asarray(values, dtype=np.float32)[cand], ids[cand], k)
+    return sel
+
+
+def _wsel_select_candidates(values, ids, k):
     keys = _wsel_key(values)
     need = min(len(keys), k)
-    if need == 0:
-        return np.zeros(len(keys), dtype=bool)
     prefix, ngt = np.uint32(0), 0
     for p in range(4):
         shift = 24 - 8 * p
@@ -143,13 +150,24 @@ def test_wide_selection_key_is_order_preserving_and_ties_zeroes():
     assert np.all(np.diff(_wsel_key(x[order]).astype(np.int64)) >= 0)
 
 
+def test_wide_selection_never_takes_a_nan_of_either_sign():
+    """Without the candidate filter the key of +NaN (0xffc00000) lies above +inf's and is selected first; the key of -NaN (0x003fffff)
+    lies below -inf's and is selected whenever fewer than k other candidates exist."""
+    pos, neg = np.array([0x7FC00000, 0xFFC00000], dtype=np.uint32).view(np.float32)
+    assert _wsel_key([pos])[0] > _wsel_key([np.inf])[0] and _wsel_key([neg])[0] < _wsel_key([-np.inf])[0]
+    ids = np.arange(5, dtype=np.int64)
+    assert _wsel_select(np.array([1, pos, 3, -np.inf, 2], dtype=np.float32), ids, 2).tolist() == [False, False, True, False, True]
+    assert _wsel_select(np.array([1, neg, 3, -np.inf, 2], dtype=np.float32), ids, 5).tolist() == [True, False, True, True, True]
+    assert not _wsel_select(np.array([pos, neg, pos], dtype=np.float32), ids[:3], 2).any()
+
+
 @pytest.mark.parametrize("seed", range(6))
 def test_wide_selection_rule_equals_the_stable_sort_prefix(seed):
     rng = np.random.default_rng(seed)
     for case in range(40):
         n = int(rng.integers(1, 4000))
         k = int(rng.integers(1, 5000))
-        mode = case % 5
+        mode = case % 6
         if mode == 0:
             v = rng.standard_normal(n).astype(np.float32)
         elif mode == 1:
@@ -158,12 +176,19 @@ def test_wide_selection_rule_equals_the_stable_sort_prefix(seed):
             v = np.where(rng.random(n) < 0.5, -np.inf, rng.standard_normal(n)).astype(np.float32)
         elif mode == 3:
             v = np.where(rng.random(n) < 0.5, 0.0, -0.0).astype(np.float32)
-        else:
+        elif mode == 4:
             v = np.full(n, 7.0, dtype=np.float32)
+        else:  # NaN of both signs (never selected: fewer than k real candidates select them all and nothing else), +-inf beside them
+            v = rng.standard_normal(n).astype(np.float32).view(np.uint32)
+            pick = rng.integers(0, 8, n)
+            for j, bits in enumerate((0x7FC00000, 0xFFC00000, 0x7F800001, 0xFFFFFFFF, 0x7F800000, 0xFF800000)):
+                v[pick == j] = bits
+            v = v.view(np.float32)
         # ids as the kernel meets them: distinct, not in order, some beyond 2^32 (passage ids of a sharded corpus)
         ids = rng.permutation(n).astype(np.int64) * int(rng.integers(1, 5)) + int(rng.choice([0, 1 << 20, (1 << 33) + 5]))
         sel = _wsel_select(v, ids, k)
-        order = np.lexsort((ids, -v.astype(np.float64)))  # value descending (+0 == -0), then id ascending
+        real = np.flatnonzero(~np.isnan(v))
+        order = real[np.lexsort((ids[real], -v[real].astype(np.float64)))]  # value descending (+0 == -0), then id ascending
         want = np.zeros(n, dtype=bool)
         want[order[:k]] = True
         assert np.array_equal(sel, want), (seed, case, n, k, mode)
