@@ -9,6 +9,7 @@ HIP dQ / dC GEMMs | RCCL reduce-scatter of dC.  All device work goes through the
 layout, label offsets, reduce-scatter, loss all-reduce) on gloo with a stand-in; the default -- and the only
 thing the product ever passes -- is the HIP library.
 """
+import collections
 import ctypes
 import os
 
@@ -119,14 +120,6 @@ class HipKernels:
     def empty(self, shape, dtype, like):
         return torch.empty(shape, dtype=dtype, device=like.device)
 
-    def _g_buffer(self, want_G, B, Nc, d, dev):
-        """The dScores buffer of the one-call steps: True -> always (the plan then materialises G); "auto" -> only where the shape's
-        plan needs one (dprhot_step_wants_g; elsewhere the step never writes the dScores: one launch less at cfg3 per rank);
-        False -> none (raises at shapes that need it)."""
-        if want_G is True or (want_G == "auto" and self._wants_g(B, Nc, d)):
-            return torch.empty((B, Nc), dtype=_BF16, device=dev)
-        return None
-
     def _wants_g(self, B, Nc, d):
         key = (B, Nc, d, self._lib.options_epoch())
         w = self._wg.get(key)
@@ -180,68 +173,69 @@ class HipKernels:
         self._lib.check(self.lib.dprhot_unpack_mask(_ptr(gathered), W, n_ctx, d, _ptr(colmask), self._stream()),
                         "dprhot_unpack_mask")
 
+    def _step_outputs(self, B, Nc, d, dev, want_G, want_S=False, grads=False, loss_len=1, dc_dtype=torch.float32, defer_dq=False):
+        """What the six step entry points allocate, in the order they always have, and the workspace -> (row_loss, row_lse, loss, G, S,
+        dQ, dC, part, ws).  grads False, a forward: G by truth value, S when want_S.  grads True, a step: G as want_G says, dQ, dC in
+        dc_dtype, the split-K slabs (`part`) when defer_dq and the plan leaves some.  (Plain addresses go on: _lib's argtypes make pointers.)"""
+        f32 = torch.float32
+        row_loss = torch.empty(B, dtype=f32, device=dev)
+        row_lse = torch.empty(B, dtype=f32, device=dev)
+        loss = torch.empty(loss_len, dtype=f32, device=dev)
+        S = dQ = dC = part = None
+        if grads:
+            # the dScores buffer: True -> always (the plan then materialises G); "auto" -> only where the shape's plan needs one
+            # (dprhot_step_wants_g; elsewhere the step never writes the dScores: one launch less at cfg3 per rank); False -> none
+            G = torch.empty((B, Nc), dtype=_BF16, device=dev) if want_G is True or (want_G == "auto" and self._wants_g(B, Nc, d)) else None
+            dQ = torch.empty((B, d), dtype=f32, device=dev)
+            dC = torch.empty((Nc, d), dtype=dc_dtype, device=dev)
+            if defer_dq:  # caller-owned buffer for the split-K partial sums of dQ, where this shape's plan leaves any
+                key = (B, Nc, d, self._lib.options_epoch())  # the plan depends on process-wide options (dprhot_set_option)
+                n = self._nslabs.get(key)
+                if n is None:
+                    n = self._nslabs[key] = self._lib.train_dq_slabs(B, Nc, d)
+                if n > 0:
+                    part = torch.empty((n, B, d), dtype=f32, device=dev)
+        else:
+            G = torch.empty((B, Nc), dtype=_BF16, device=dev) if want_G else None
+            S = torch.empty((B, Nc), dtype=f32, device=dev) if want_S else None
+        return row_loss, row_lse, loss, G, S, dQ, dC, part, self._workspace(dev, self._lib.workspace_bytes(B, Nc, d))
+
     def inbatch_fwd(self, Qb, Cb, y, y_offset, colmask, inv_T, grad_scale, want_logits=False, want_G=True):
         self._require_gpu(Qb, Cb, y, colmask)
-        B, d = Qb.shape
-        Nc = Cb.shape[0]
-        dev = Qb.device
-        row_loss = torch.empty(B, dtype=torch.float32, device=dev)
-        row_lse = torch.empty(B, dtype=torch.float32, device=dev)
-        loss_sum = torch.empty(1, dtype=torch.float32, device=dev)
-        G = torch.empty((B, Nc), dtype=_BF16, device=dev) if want_G else None
-        S = torch.empty((B, Nc), dtype=torch.float32, device=dev) if want_logits else None
-        nbytes = self._lib.workspace_bytes(B, Nc, d)
-        ws = self._workspace(dev, nbytes)
+        (B, d), Nc = Qb.shape, Cb.shape[0]
+        row_loss, row_lse, loss_sum, G, S, _, _, _, ws = self._step_outputs(B, Nc, d, Qb.device, want_G, want_S=want_logits)
         self._lib.check(self.lib.dprhot_inbatch_fwd(
-            _ptr(Qb), B, _ptr(Cb), Nc, d, _ptr(y), int(y_offset), _ptr(colmask), float(inv_T), float(grad_scale),
-            _ptr(S), _ptr(row_loss), _ptr(row_lse), _ptr(loss_sum), _ptr(G), _ptr(ws), ws.numel(), self._stream()),
-            "dprhot_inbatch_fwd")
+            Qb.data_ptr(), B, Cb.data_ptr(), Nc, d, _ptr(y), int(y_offset), _ptr(colmask), float(inv_T), float(grad_scale), _ptr(S), row_loss.data_ptr(),
+            row_lse.data_ptr(), loss_sum.data_ptr(), _ptr(G), ws.data_ptr(), ws.numel(), self._stream()), "dprhot_inbatch_fwd")
         return row_loss, row_lse, loss_sum, G, S
 
     def inbatch_fwd_f32(self, q, c, Qb, Cb, y, y_offset, colmask, inv_T, grad_scale, want_logits=False, want_G=True):
         """Forward straight from the fp32 encoder outputs: q [B,d] fp32; c [Nc,d] fp32 or None (Cb already holds
         the gathered bf16 rows).  Fills Qb (and Cb when c is given) with the bf16 images the backward reads."""
         self._require_gpu(q, c, Qb, Cb, y, colmask)
-        B, d = Qb.shape
-        Nc = Cb.shape[0]
-        dev = Qb.device
+        (B, d), Nc = Qb.shape, Cb.shape[0]
         q = q.detach().contiguous()
         c = c.detach().contiguous() if c is not None else None
         assert q.dtype == torch.float32 and (c is None or (c.dtype == torch.float32 and c.shape[0] == Nc))
-        row_loss = torch.empty(B, dtype=torch.float32, device=dev)
-        row_lse = torch.empty(B, dtype=torch.float32, device=dev)
-        loss_sum = torch.empty(1, dtype=torch.float32, device=dev)
-        G = torch.empty((B, Nc), dtype=_BF16, device=dev) if want_G else None
-        S = torch.empty((B, Nc), dtype=torch.float32, device=dev) if want_logits else None
-        ws = self._workspace(dev, self._lib.workspace_bytes(B, Nc, d))
+        row_loss, row_lse, loss_sum, G, S, _, _, _, ws = self._step_outputs(B, Nc, d, Qb.device, want_G, want_S=want_logits)
         self._lib.check(self.lib.dprhot_inbatch_fwd_f32(
-            _ptr(q), _ptr(c), _ptr(Qb), _ptr(Cb), B, Nc, d, _ptr(y), int(y_offset), _ptr(colmask), float(inv_T),
-            float(grad_scale), _ptr(S), _ptr(row_loss), _ptr(row_lse), _ptr(loss_sum), _ptr(G), _ptr(ws), ws.numel(),
-            self._stream()), "dprhot_inbatch_fwd_f32")
+            q.data_ptr(), _ptr(c), Qb.data_ptr(), Cb.data_ptr(), B, Nc, d, _ptr(y), int(y_offset), _ptr(colmask), float(inv_T), float(grad_scale), _ptr(S),
+            row_loss.data_ptr(), row_lse.data_ptr(), loss_sum.data_ptr(), _ptr(G), ws.data_ptr(), ws.numel(), self._stream()), "dprhot_inbatch_fwd_f32")
         return row_loss, row_lse, loss_sum, G, S
 
     def inbatch_step_f32(self, q, c, Qb, Cb, y, y_offset, colmask, inv_T, grad_scale, want_G=True):
         """Forward AND backward in one library call (dprhot_inbatch_step_f32; two launches at the BASELINE training
         shapes).  Gradients come back for grad_output = 1: returns (row_loss, row_lse, loss_sum, G, dQ, dC_part)."""
         self._require_gpu(q, c, Qb, Cb, y, colmask)
-        B, d = Qb.shape
-        Nc = Cb.shape[0]
-        dev = Qb.device
+        (B, d), Nc = Qb.shape, Cb.shape[0]
         q = q.detach().contiguous()
         c = c.detach().contiguous() if c is not None else None
         assert q.dtype == torch.float32 and (c is None or (c.dtype == torch.float32 and c.shape[0] == Nc))
-        f32 = torch.float32
-        row_loss = torch.empty(B, dtype=f32, device=dev)
-        row_lse = torch.empty(B, dtype=f32, device=dev)
-        loss_sum = torch.empty(1, dtype=f32, device=dev)
-        G = self._g_buffer(want_G, B, Nc, d, dev)
-        dQ = torch.empty((B, d), dtype=f32, device=dev)
-        dC = torch.empty((Nc, d), dtype=f32, device=dev)
-        ws = self._workspace(dev, self._lib.workspace_bytes(B, Nc, d))
+        row_loss, row_lse, loss_sum, G, _, dQ, dC, _, ws = self._step_outputs(B, Nc, d, Qb.device, want_G, grads=True)
         self._lib.check(self.lib.dprhot_inbatch_step_f32(
-            _ptr(q), _ptr(c), _ptr(Qb), _ptr(Cb), B, Nc, d, _ptr(y), int(y_offset), _ptr(colmask), float(inv_T),
-            float(grad_scale), 1.0, None, None, _ptr(row_loss), _ptr(row_lse), _ptr(loss_sum), _ptr(G), _ptr(dQ), _ptr(dC),
-            _ptr(ws), ws.numel(), self._stream()), "dprhot_inbatch_step_f32")
+            q.data_ptr(), _ptr(c), Qb.data_ptr(), Cb.data_ptr(), B, Nc, d, _ptr(y), int(y_offset), _ptr(colmask), float(inv_T), float(grad_scale), 1.0,
+            None, None, row_loss.data_ptr(), row_lse.data_ptr(), loss_sum.data_ptr(), _ptr(G), dQ.data_ptr(), dC.data_ptr(), ws.data_ptr(), ws.numel(),
+            self._stream()), "dprhot_inbatch_step_f32")
         return row_loss, row_lse, loss_sum, G, dQ, dC
 
     def inbatch_step_packed_f32(self, q, gathered, Qb, W, rank, n_ctx, y, inv_T, grad_scale, want_G=True):
@@ -250,32 +244,15 @@ class HipKernels:
         [k * rows_c + n_ctx][0] of every chunk k (see include/dprhot.h).  Returns (row_loss, row_lse, loss_sum, G, dQ,
         dC_part)."""
         self._require_gpu(q, gathered, Qb, y)
-        B, d = Qb.shape
-        Nc = gathered.shape[0]
-        dev = Qb.device
+        (B, d), Nc = Qb.shape, gathered.shape[0]
         q = q.detach().contiguous()
         assert q.dtype == torch.float32 and gathered.dtype == _BF16 and Nc == W * self.packed_rows(n_ctx, d)
-        f32 = torch.float32
-        row_loss = torch.empty(B, dtype=f32, device=dev)
-        row_lse = torch.empty(B, dtype=f32, device=dev)
-        loss_sum = torch.empty(1, dtype=f32, device=dev)
-        G = self._g_buffer(want_G, B, Nc, d, dev)
-        dQ = torch.empty((B, d), dtype=f32, device=dev)
-        dC = torch.empty((Nc, d), dtype=f32, device=dev)
-        ws = self._workspace(dev, self._lib.workspace_bytes(B, Nc, d))
+        row_loss, row_lse, loss_sum, G, _, dQ, dC, _, ws = self._step_outputs(B, Nc, d, Qb.device, want_G, grads=True)
         self._lib.check(self.lib.dprhot_inbatch_step_packed_f32(
-            _ptr(q), _ptr(gathered), _ptr(Qb), B, int(W), int(rank), int(n_ctx), d, _ptr(y), float(inv_T), float(grad_scale),
-            1.0, None, _ptr(row_loss), _ptr(row_lse), _ptr(loss_sum), _ptr(G), _ptr(dQ), _ptr(dC), _ptr(ws), ws.numel(),
+            q.data_ptr(), gathered.data_ptr(), Qb.data_ptr(), B, int(W), int(rank), int(n_ctx), d, _ptr(y), float(inv_T), float(grad_scale), 1.0, None,
+            row_loss.data_ptr(), row_lse.data_ptr(), loss_sum.data_ptr(), _ptr(G), dQ.data_ptr(), dC.data_ptr(), ws.data_ptr(), ws.numel(),
             self._stream()), "dprhot_inbatch_step_packed_f32")
         return row_loss, row_lse, loss_sum, G, dQ, dC
-
-    def _dq_slabs(self, B, Nc, d, dev):
-        """Caller-owned buffer for the split-K partial sums of dQ, or None when this shape's plan leaves none."""
-        key = (B, Nc, d, self._lib.options_epoch())  # the plan depends on process-wide options (dprhot_set_option)
-        n = self._nslabs.get(key)
-        if n is None:
-            n = self._nslabs[key] = self._lib.train_dq_slabs(B, Nc, d)
-        return torch.empty((n, B, d), dtype=torch.float32, device=dev) if n > 0 else None
 
     def train_step_f32(self, q, c, Qb, Cb, y, y_offset, colmask, inv_T, grad_scale, loss_scale, d_scale, dc_dtype=torch.float32,
                        defer_dq=False, want_G=True):
@@ -284,49 +261,31 @@ class HipKernels:
         Returns (row_loss, row_lse, loss_out [2], G, dQ, dC_part); loss_out[0] is the loss.  defer_dq: where the plan splits dQ over
         the contexts, dQ comes back as (dQ buffer, slabs) and rescale_grads() adds the slabs up (one launch less in the step)."""
         self._require_gpu(q, c, Qb, Cb, y, colmask, d_scale)
-        B, d = Qb.shape
-        Nc = Cb.shape[0]
-        dev = Qb.device
+        (B, d), Nc = Qb.shape, Cb.shape[0]
         q = q.detach().contiguous()
         c = c.detach().contiguous() if c is not None else None
         assert q.dtype == torch.float32 and (c is None or (c.dtype == torch.float32 and c.shape[0] == Nc))
-        f32 = torch.float32
-        row_loss = torch.empty(B, dtype=f32, device=dev)
-        row_lse = torch.empty(B, dtype=f32, device=dev)
-        loss_out = torch.empty(2, dtype=f32, device=dev)
-        G = self._g_buffer(want_G, B, Nc, d, dev)
-        dQ = torch.empty((B, d), dtype=f32, device=dev)
-        dC = torch.empty((Nc, d), dtype=dc_dtype, device=dev)
-        part = self._dq_slabs(B, Nc, d, dev) if defer_dq else None
-        ws = self._workspace(dev, self._lib.workspace_bytes(B, Nc, d))
+        outs = self._step_outputs(B, Nc, d, Qb.device, want_G, grads=True, loss_len=2, dc_dtype=dc_dtype, defer_dq=defer_dq)
+        row_loss, row_lse, loss_out, G, _, dQ, dC, part, ws = outs
         self._lib.check(self.lib.dprhot_train_step_f32(
-            _ptr(q), _ptr(c), _ptr(Qb), _ptr(Cb), B, Nc, d, _ptr(y), int(y_offset), _ptr(colmask), float(inv_T), float(grad_scale),
-            float(loss_scale), _ptr(d_scale), _ptr(row_loss), _ptr(row_lse), _ptr(loss_out), _ptr(G), _ptr(dQ), _ptr(part), _ptr(dC),
-            _KIND[dc_dtype], _ptr(ws), ws.numel(), self._stream()), "dprhot_train_step_f32")
+            q.data_ptr(), _ptr(c), Qb.data_ptr(), Cb.data_ptr(), B, Nc, d, _ptr(y), int(y_offset), _ptr(colmask), float(inv_T), float(grad_scale),
+            float(loss_scale), _ptr(d_scale), row_loss.data_ptr(), row_lse.data_ptr(), loss_out.data_ptr(), _ptr(G), dQ.data_ptr(), _ptr(part),
+            dC.data_ptr(), _KIND[dc_dtype], ws.data_ptr(), ws.numel(), self._stream()), "dprhot_train_step_f32")
         return row_loss, row_lse, loss_out, G, (dQ if part is None else (dQ, part)), dC
 
     def train_step_packed_f32(self, q, gathered, Qb, W, rank, n_ctx, y, inv_T, grad_scale, loss_scale, d_scale, dc_dtype=torch.float32,
                               defer_dq=False, want_G=True):
         """World size > 1 (dprhot_train_step_packed_f32): as train_step_f32 on the all-gathered packed buffer."""
         self._require_gpu(q, gathered, Qb, y, d_scale)
-        B, d = Qb.shape
-        Nc = gathered.shape[0]
-        dev = Qb.device
+        (B, d), Nc = Qb.shape, gathered.shape[0]
         q = q.detach().contiguous()
         assert q.dtype == torch.float32 and gathered.dtype == _BF16 and Nc == W * self.packed_rows(n_ctx, d)
-        f32 = torch.float32
-        row_loss = torch.empty(B, dtype=f32, device=dev)
-        row_lse = torch.empty(B, dtype=f32, device=dev)
-        loss_out = torch.empty(2, dtype=f32, device=dev)
-        G = self._g_buffer(want_G, B, Nc, d, dev)
-        dQ = torch.empty((B, d), dtype=f32, device=dev)
-        dC = torch.empty((Nc, d), dtype=dc_dtype, device=dev)
-        part = self._dq_slabs(B, Nc, d, dev) if defer_dq else None
-        ws = self._workspace(dev, self._lib.workspace_bytes(B, Nc, d))
+        outs = self._step_outputs(B, Nc, d, Qb.device, want_G, grads=True, loss_len=2, dc_dtype=dc_dtype, defer_dq=defer_dq)
+        row_loss, row_lse, loss_out, G, _, dQ, dC, part, ws = outs
         self._lib.check(self.lib.dprhot_train_step_packed_f32(
-            _ptr(q), _ptr(gathered), _ptr(Qb), B, int(W), int(rank), int(n_ctx), d, _ptr(y), float(inv_T), float(grad_scale),
-            float(loss_scale), _ptr(d_scale), _ptr(row_loss), _ptr(row_lse), _ptr(loss_out), _ptr(G), _ptr(dQ), _ptr(part), _ptr(dC),
-            _KIND[dc_dtype], _ptr(ws), ws.numel(), self._stream()), "dprhot_train_step_packed_f32")
+            q.data_ptr(), gathered.data_ptr(), Qb.data_ptr(), B, int(W), int(rank), int(n_ctx), d, _ptr(y), float(inv_T), float(grad_scale),
+            float(loss_scale), _ptr(d_scale), row_loss.data_ptr(), row_lse.data_ptr(), loss_out.data_ptr(), _ptr(G), dQ.data_ptr(), _ptr(part),
+            dC.data_ptr(), _KIND[dc_dtype], ws.data_ptr(), ws.numel(), self._stream()), "dprhot_train_step_packed_f32")
         return row_loss, row_lse, loss_out, G, (dQ if part is None else (dQ, part)), dC
 
     def rescale_grads(self, dQ, dC, go, used):
@@ -790,6 +749,16 @@ def _pad_cols(n):
     return (n + 7) // 8 * 8
 
 
+def _mask_u8(mask):
+    """The mask as bytes: a bool mask viewed in place, any other mask converted."""
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask.to(torch.uint8)
+
+
+def _mask_bytes(mask):
+    """A bool mask viewed as bytes in place, any other mask as it is (it already is one byte per element)."""
+    return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+
+
 class ContextGather:
     """The forward collective, started as soon as the context tower has produced its rows:
     pack (bf16 rows + mask bytes) on the compute stream, then ONE all-gather with async_op=True -- it runs on RCCL's
@@ -808,7 +777,7 @@ class ContextGather:
         W, r = D.world(group)
         assert W > 1 or D.force_dist(), "ContextGather is for world size > 1"
         n_ctx, d = c.shape
-        m8 = ctx_mask.view(torch.uint8) if ctx_mask.dtype == torch.bool else ctx_mask.to(torch.uint8)
+        m8 = _mask_u8(ctx_mask)
         self.rows_c = kn.packed_rows(n_ctx, d)
         self.send = kn.empty((self.rows_c, d), _BF16, c)
         kn.pack_ctx(c.detach(), m8, self.send)
@@ -859,6 +828,218 @@ def defer_context_grad(c):
     return _DeferContextGrad.apply(c, pending), pending
 
 
+# ---- the operator's parts.  What the kernel set provides is read once per call, by attribute, into a _Caps; the staged operands and the
+# step's result travel as plain tuples and _Bwd takes attribute stores (a constructor call per step shows in the eager step's host time).
+_Caps = collections.namedtuple("_Caps", "inbatch_fwd_f32 inbatch_step_f32 inbatch_step_packed_f32 train_step_f32 train_step_packed_f32 widen")
+_HIP_CAPS = _Caps(*[hasattr(HipKernels, n) for n in _Caps._fields])  # (the library's own kernel set: read once, here)
+FAST = "FAST"                # the single-rank step of csrc/opx.cpp: gradients computed in forward, scaled by the predicted grad_output
+PRESCALED = "PRESCALED"      # the same from a train_step_* entry point of the kernel set (opx_packed: its host side in csrc/opx.cpp)
+UNIT = "UNIT"                # gradients computed in forward for grad_output = 1 (stand-in kernels); backward applies the scale
+SAVED = "SAVED"              # forward only: Qb, Cb, G saved for the backward GEMMs
+FP32G_DEBUG = "FP32G_DEBUG"  # DPRHOT_FP32_G=1: the logits kept, dScores rebuilt in fp32 and sent through the GEMMs as a bf16 pair
+REGEN = "REGEN"              # what FAST / PRESCALED turn into once they have given their tensors away: the backward GEMMs again
+
+
+class _Bwd:
+    """The one record forward leaves on ctx: kind, row_lse and that kind's fields -- FAST / PRESCALED: grads, used, site + REGEN's;
+    REGEN: Qb, Cb, G, pos_idx, y_off, mask (None: still packed in Cb), inv_T, grad_scale;  UNIT: grads;  FP32G_DEBUG: S, labels, gs
+    (SAVED and FP32G_DEBUG keep Qb, Cb, G in ctx.saved_tensors).  All but FAST and the REGEN it turns into (`fast`) also carry
+    what the general backward needs: kn, group, W, n_ctx, rows_c, d, multi, direct_ctx_grad, in_dtypes, pending, can_widen."""
+
+    __slots__ = ("kind", "fast", "row_lse", "grads", "used", "site", "opx_packed", "Qb", "Cb", "G", "pos_idx", "y_off", "mask", "inv_T", "grad_scale",
+                 "S", "labels", "gs", "kn", "group", "W", "n_ctx", "rows_c", "d", "multi", "direct_ctx_grad", "in_dtypes", "pending", "can_widen")
+
+
+def _plain_single_rank(q, group, kernels):
+    """Both C++ short cuts (the step below, inbatch_contrastive_loss's node) ask first: own kernels, a device, one rank, no debug mode."""
+    return kernels is None and q.is_cuda and (group is False or D.world(group)[0] == 1) and not _fp32_g_mode() and not (D.force_dist() and group is not False)
+
+
+def _opx_step_eligible(q, c, pos_idx, ctx_mask, group, kernels, wants_grad):
+    """The step a single-GPU run issues every iteration (dpr_task.py:197-212) has its host side in C++ (csrc/opx.cpp).  Taken when
+    nothing needs the general code: fp32 contiguous encoder outputs, a whole number of 8-column groups, a byte mask."""
+    if not wants_grad or not c.is_cuda or not _plain_single_rank(q, group, kernels):
+        return False
+    n_ctx, d = c.shape
+    return (q.dtype == torch.float32 and c.dtype == torch.float32 and q.is_contiguous() and c.is_contiguous() and n_ctx % 8 == 0 and d % 8 == 0
+            and q.shape[1] == d and ctx_mask.is_contiguous() and ctx_mask.element_size() == 1 and pos_idx.dtype == torch.int64 and pos_idx.is_contiguous())
+
+
+def _stage_single(kn, q, c, m8, Qb, q_f32):
+    """One rank: columns = this rank's contexts (padded to 8 with masked zero rows).  -> (Qb, Cb, colmask, rows_c, Nc, c_direct, q_f32, packed_step)"""
+    n_ctx, d = c.shape
+    Nc = _pad_cols(n_ctx)
+    Cb = kn.empty((Nc, d), _BF16, c)
+    if Nc == n_ctx:
+        colmask = m8 if m8.is_contiguous() else m8.contiguous()  # the batch's own bool mask, read in place
+    else:
+        colmask = kn.empty((Nc,), torch.uint8, c)
+        colmask[:n_ctx].copy_(m8)
+        Cb[n_ctx:].zero_()
+        colmask[n_ctx:].fill_(1)
+    # fp32 encoder outputs are consumed as they are by the sim kernel (it rounds to bf16 while staging and leaves the bf16 images in Qb / Cb)
+    c_direct = q_f32 and c.dtype == torch.float32 and Nc == n_ctx
+    if not c_direct:
+        kn.prep(q, Qb, c, Cb[:n_ctx])
+        q_f32 = False
+    return Qb, Cb, colmask, Nc, Nc, c_direct, q_f32, False
+
+
+def _stage_multi(kn, caps, q, c, m8, Qb, q_f32, W, group, gather, wants_grad):
+    """Several ranks.  ONE all-gather: context rows (bf16) + mask bytes in trailing rows of the same buffer; the trailing
+    rows become always-masked extra columns (the reference issues 4 fp32 all_gathers, :169-176).  -> as _stage_single"""
+    n_ctx, d = c.shape
+    rows_c = kn.packed_rows(n_ctx, d)
+    Nc = W * rows_c
+    if gather is not None:  # started under the query tower (ContextGather): only wait here
+        assert gather.shape == (n_ctx, d)
+        Cb = gather.wait()
+    else:
+        send = kn.empty((rows_c, d), _BF16, c)
+        kn.pack_ctx(c, m8, send)
+        Cb = kn.empty((Nc, d), _BF16, c)
+        D.all_gather_rows(send, Cb, group)
+    # with a backward to follow, the one-call step reads the mask straight from the gathered buffer: no unpack launch
+    packed_step = q_f32 and wants_grad and (caps.train_step_packed_f32 or caps.inbatch_step_packed_f32)
+    colmask = None
+    if not packed_step:
+        colmask = kn.empty((Nc,), torch.uint8, c)
+        kn.unpack_mask(Cb, W, n_ctx, colmask)
+    if not q_f32:
+        kn.cast_bf16(q, Qb)
+    return Qb, Cb, colmask, rows_c, Nc, False, q_f32, packed_step
+
+
+def _run_step(kn, caps, q, c32, Qb, Cb, colmask, Nc, q_f32, packed_step, pos_idx, W, r, n_ctx, inv_T, grad_scale, y_off, multi, wants_grad, dc_dtype, kernels):
+    """Choose the step's route and run it.  -> (bw, loss_sum, loss_is_mean, saved): the _Bwd with its kind, row_lse and that kind's own
+    fields; the loss numerator (already the mean when loss_is_mean: the kernel multiplied it by 1 / Nq); the tensors for forward to save."""
+    B, d = q.shape
+    Nq = W * B
+    bw = _Bwd()
+    if not multi and _fp32_g_mode() and wants_grad:
+        _, bw.row_lse, loss_sum, G, bw.S = (kn.inbatch_fwd_f32(q, c32, Qb, Cb, pos_idx, y_off, colmask, inv_T, grad_scale, want_logits=True) if q_f32
+                                            else kn.inbatch_fwd(Qb, Cb, pos_idx, y_off, colmask, inv_T, grad_scale, want_logits=True))
+        bw.kind, bw.gs = FP32G_DEBUG, grad_scale  # (forward adds the labels)
+        return bw, loss_sum, False, (Qb, Cb, G)
+    used, bw.opx_packed = None, False
+    if multi and packed_step and caps.train_step_packed_f32:
+        # forward and backward of this rank's rows in ONE library call; gradients scaled by the grad_output the last backward saw
+        bw.used = used = _ExpectedGradScale.get(q.device, (B, Nc, d))
+        if _OPX_PACKED and kernels is None and q.is_contiguous() and pos_idx.dtype == torch.int64 and pos_idx.is_contiguous() \
+                and dc_dtype in (torch.float32, _BF16):
+            # host side in C++ (csrc/opx.cpp: packed_train_step): the allocations, the library call and its fall-back to fp32
+            # partials in one function; backward's counterpart is packed_backward
+            loss_sum, bw.row_lse, dQ, dC_part, Qb, G, part = _OPX.packed_train_step(q.detach(), Cb, pos_idx, W, r, n_ctx, inv_T, grad_scale,
+                                                                                    1.0 / Nq, used, 0 if dc_dtype == _BF16 else 2)
+            G = G if (G is not None and G.numel() > 0) else None  # (an undefined at::Tensor arrives as None)
+            if part is not None and part.numel() > 0:
+                dQ = (dQ, part)
+            bw.opx_packed = True
+        else:
+            try:
+                _, bw.row_lse, loss_sum, G, dQ, dC_part = kn.train_step_packed_f32(q, Cb, Qb, W, r, n_ctx, pos_idx, inv_T, grad_scale, 1.0 / Nq,
+                                                                                   used, dc_dtype, defer_dq=True, want_G="auto")
+            except Exception as e:  # a plan without a bf16 dC epilogue: fp32 partials, rounded to the wire format in backward
+                if dc_dtype == torch.float32 or "dc_kind" not in str(e):
+                    raise
+                _, bw.row_lse, loss_sum, G, dQ, dC_part = kn.train_step_packed_f32(q, Cb, Qb, W, r, n_ctx, pos_idx, inv_T, grad_scale, 1.0 / Nq,
+                                                                                   used, torch.float32, defer_dq=True, want_G="auto")
+    elif multi and packed_step:  # (stand-in kernels of the CPU tests)
+        _, bw.row_lse, loss_sum, _, dQ, dC_part = kn.inbatch_step_packed_f32(q, Cb, Qb, W, r, n_ctx, pos_idx, inv_T, grad_scale)
+    elif q_f32 and wants_grad and caps.train_step_f32:
+        # a backward will follow: forward and backward in ONE library call (two launches at the BASELINE shapes);
+        # backward() only checks the grad_output it was given against the one the gradients were scaled by
+        bw.used = used = _ExpectedGradScale.get(q.device, (B, Nc, d))
+        _, bw.row_lse, loss_sum, G, dQ, dC_part = kn.train_step_f32(q, c32, Qb, Cb, pos_idx, y_off, colmask, inv_T, grad_scale, 1.0 / Nq, used,
+                                                                    defer_dq=True, want_G="auto")
+    elif q_f32 and wants_grad and caps.inbatch_step_f32:  # (stand-in kernels of the CPU tests)
+        _, bw.row_lse, loss_sum, _, dQ, dC_part = kn.inbatch_step_f32(q, c32, Qb, Cb, pos_idx, y_off, colmask, inv_T, grad_scale)
+    else:
+        _, bw.row_lse, loss_sum, G, _ = (kn.inbatch_fwd_f32(q, c32, Qb, Cb, pos_idx, y_off, colmask, inv_T, grad_scale) if q_f32
+                                         else kn.inbatch_fwd(Qb, Cb, pos_idx, y_off, colmask, inv_T, grad_scale))
+        bw.kind = SAVED
+        return bw, loss_sum, False, (Qb, Cb, G)
+    bw.grads, bw.kind = (dQ, dC_part), (UNIT if used is None else PRESCALED)
+    if bw.kind is PRESCALED:  # (what REGEN will need; mask None: still packed in Cb)
+        bw.Qb, bw.Cb, bw.G, bw.pos_idx, bw.y_off, bw.mask, bw.inv_T, bw.grad_scale = Qb, Cb, G, pos_idx, y_off, colmask, inv_T, grad_scale
+    return bw, loss_sum, bw.kind is PRESCALED, None
+
+
+def _regen_grads(kn, Qb, Cb, G, pos_idx, y_off, mask, inv_T, grad_scale, go, need_dq, need_dc, packed=None):
+    """A second backward through a retained graph: the first one gave its gradient tensors away; the backward GEMMs run again on the
+    operands the step left behind (exact, rare).  The dScores are recomputed first where the step never materialised them (G is None),
+    the mask unpacked from the gathered buffer where the step read it there (mask None; packed = (W, n_ctx)).  -> (dQ, dC, G to keep)."""
+    if G is None:
+        if mask is None:
+            mask = kn.empty((Cb.shape[0],), torch.uint8, Cb)
+            kn.unpack_mask(Cb, packed[0], packed[1], mask)
+        G = kn.inbatch_fwd(Qb, Cb, pos_idx, y_off, _mask_bytes(mask), inv_T, grad_scale)[3]
+    dQ, dC = kn.inbatch_bwd(G, Qb, Cb, 1.0, go, need_dq, need_dc)
+    return dQ, dC, G
+
+
+def _local_grads(ctx, st, go, need_dq, need_dc):
+    """This rank's gradients for every kind but the per-step ones (FAST and PRESCALED: in backward itself) -> (dQ, dC_part, the
+    grad_output still to apply (None: it is in them already))."""
+    kn, kind = st.kn, st.kind
+    if kind is REGEN:
+        dQ, dC_part, st.G = _regen_grads(kn, st.Qb, st.Cb, st.G, st.pos_idx, st.y_off, st.mask, st.inv_T, st.grad_scale, go, need_dq, need_dc,
+                                         (st.W, st.n_ctx))
+        return dQ, dC_part, None
+    if kind is UNIT:  # computed in forward for grad_output = 1 (stand-in kernels); the caller applies the scale
+        return st.grads[0], st.grads[1], go
+    Qb, Cb, G = ctx.saved_tensors
+    if kind is FP32G_DEBUG:
+        # fp32-G debug mode: G = (exp(S - lse) - onehot) * scale recomputed in fp32, split into a bf16 pair, two GEMM passes
+        S = st.S
+        G32 = torch.exp(S - st.row_lse[:, None])
+        G32[torch.arange(S.shape[0], device=S.device), st.labels] -= 1.0
+        G32 *= st.gs
+        hi = G32.to(_BF16)
+        lo = (G32 - hi.float()).to(_BF16)
+        dQ1, dC1 = kn.inbatch_bwd(hi, Qb, Cb, 1.0, go, need_dq, need_dc)
+        dQ2, dC2 = kn.inbatch_bwd(lo, Qb, Cb, 1.0, go, need_dq, need_dc)
+        return (dQ1 + dQ2 if need_dq else None), (dC1 + dC2 if need_dc else None), None
+    dQ, dC_part = kn.inbatch_bwd(G, Qb, Cb, 1.0, go, need_dq, need_dc)
+    return dQ, dC_part, None
+
+
+def _reduce_context_grads(st, dC_part, go, mine_ready):
+    """Several ranks: dc = this rank's rows of the sum over ranks of the dC partials, in the dtype c came in."""
+    kn, group, n_ctx, d, c_dtype = st.kn, st.group, st.n_ctx, st.d, st.in_dtypes[1]
+    wire = _dc_wire_dtype(group)
+    mine = mine_ready if mine_ready is not None else kn.empty((st.rows_c, d), wire, dC_part)
+    if go is not None:
+        dC_part = dC_part * go  # scale before the collective: nothing is left to do after it
+    if dC_part.dtype != wire:
+        dC_part = dC_part.to(wire)  # half the bytes on the links (and in RCCL's reduction)
+    widen = wire != c_dtype and c_dtype == torch.float32 and st.can_widen
+    if st.pending is not None and st.direct_ctx_grad and (wire == c_dtype or widen):
+        # reduce-scatter on RCCL's stream; whoever consumes dc (defer_context_grad, after the query-tower backward has
+        # been enqueued) waits for it -- and, on a half-width wire, widens the result into the fp32 gradient there.
+        # Only in the task's own flow (c IS the output of defer_context_grad: `gather` given), where autograd hands this
+        # very tensor to that node.  Should anything still sit in between (another consumer of c, a hook), the tensor that
+        # arrives there is a different one: the half-width wire therefore returns ZEROS here (whatever autograd adds to
+        # them stays right) and post() adds the widened rows to whatever arrives instead of overwriting it.
+        st.pending.work = D.reduce_scatter_rows(dC_part, mine, group, async_op=True)
+        if not widen:
+            return mine[:n_ctx]
+        # nothing to return yet: a gradient of zeros that costs no launch (one cached zero, expanded).  post() hands
+        # the widened rows on in its place, or adds them to whatever autograd made of it (zeros + somebody else's term)
+        dc = _zeros_view((n_ctx, d), mine.device)
+
+        def post(g, kn=kn, mine=mine, zptr=dc.data_ptr(), shape=(n_ctx, d)):
+            if g.data_ptr() == zptr and g.stride() == (0, 0):
+                return kn.widen(mine, kn.empty(shape, torch.float32, mine))
+            g.add_(kn.widen(mine, kn.empty(shape, torch.float32, mine)).to(g.dtype))
+            return g
+
+        st.pending.post = post
+        return dc
+    D.reduce_scatter_rows(dC_part, mine, group)  # sum over ranks of the partials of MY columns
+    return kn.widen(mine, kn.empty((n_ctx, d), torch.float32, mine)) if widen else mine[:n_ctx].to(c_dtype)
+
+
 class InBatchContrastive(torch.autograd.Function):
     """loss = InBatchContrastive.apply(q_local, c_local, pos_idx, ctx_mask, temperature, group, kernels)
 
@@ -871,26 +1052,18 @@ class InBatchContrastive(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, q, c, pos_idx, ctx_mask, temperature, group, kernels, gather=None, pending=None):
-        ctx.fast = None
-        ctx.opx_packed = False
-        if _OPX is not None and kernels is None and gather is None and q.is_cuda and c.is_cuda and (group is False or D.world(group)[0] == 1):
-            # The step a single-GPU run issues every iteration (dpr_task.py:197-212): host side in C++ (csrc/opx.cpp).  Taken when
-            # nothing needs the general code below: fp32 contiguous encoder outputs, a whole number of 8-column groups, a byte mask.
-            n_ctx, d = c.shape
-            if (q.dtype == torch.float32 and c.dtype == torch.float32 and q.is_contiguous() and c.is_contiguous() and n_ctx % 8 == 0 and d % 8 == 0
-                    and q.shape[1] == d and ctx_mask.is_contiguous() and ctx_mask.element_size() == 1 and pos_idx.dtype == torch.int64
-                    and pos_idx.is_contiguous() and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]) and not _fp32_g_mode()
-                    and not (D.force_dist() and group is not False)):
-                B = q.shape[0]
-                inv_T = 1.0 / float(temperature)
-                site = (B, n_ctx, d)
-                used = _ExpectedGradScale.get(q.device, site)
-                loss_out, row_lse, dQ, dC, Qb, Cb, G, part = _OPX.train_step(q, c, pos_idx, ctx_mask, inv_T, inv_T / B, 1.0 / B, used,
-                                                                             default_kernels()._lib.options_epoch())
-                ctx.fast = (dQ, dC, part, used, site)
-                ctx.regen = (Qb, Cb, G, pos_idx, ctx_mask, inv_T, inv_T / B)
-                ctx.row_lse = row_lse
-                return loss_out[0]
+        wants_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        inv_T = 1.0 / float(temperature)
+        if _OPX is not None and kernels is None and gather is None and _opx_step_eligible(q, c, pos_idx, ctx_mask, group, kernels, wants_grad):
+            B, (n_ctx, d) = q.shape[0], c.shape
+            ctx.state = bw = _Bwd()
+            bw.kind, bw.fast, bw.site, bw.pos_idx, bw.y_off = FAST, True, (B, n_ctx, d), pos_idx, 0
+            bw.mask, bw.inv_T, bw.grad_scale = ctx_mask, inv_T, inv_T / B
+            bw.used = used = _ExpectedGradScale.get(q.device, bw.site)
+            loss_out, bw.row_lse, dQ, dC, bw.Qb, bw.Cb, bw.G, part = _OPX.train_step(q, c, pos_idx, ctx_mask, inv_T, inv_T / B, 1.0 / B, used,
+                                                                                     default_kernels()._lib.options_epoch())
+            bw.grads = (dQ, dC, part)
+            return loss_out[0]
         kn = kernels if kernels is not None else default_kernels()
         W, r = (1, 0) if group is False else D.world(group)  # group=False: single-device strategy, never gather
         B, d = q.shape
@@ -899,254 +1072,77 @@ class InBatchContrastive(torch.autograd.Function):
         assert pos_idx.shape[0] == B and ctx_mask.shape[0] == n_ctx
         if d % 8 != 0:
             raise ValueError(f"hidden size {d} must be a multiple of 8")
-        m8 = ctx_mask.view(torch.uint8) if ctx_mask.dtype == torch.bool else ctx_mask.to(torch.uint8)
-        q_f32 = q.dtype == torch.float32 and hasattr(kn, "inbatch_fwd_f32")
-        Qb = kn.empty((B, d), _BF16, q)
-
-        wants_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        caps = _HIP_CAPS if type(kn) is HipKernels else _Caps(*[hasattr(kn, n) for n in _Caps._fields])
         multi = W > 1 or (group is not False and D.force_dist())  # (forced: the multi-rank code path on a one-rank world, for timelines)
-        if not multi:
-            # columns = this rank's contexts (padded to a multiple of 8 with masked zero rows)
-            rows_c = _pad_cols(n_ctx)
-            Nc = rows_c
-            Cb = kn.empty((Nc, d), _BF16, c)
-            if Nc == n_ctx:
-                colmask = m8 if m8.is_contiguous() else m8.contiguous()  # the batch's own bool mask, read in place
-            else:
-                colmask = kn.empty((Nc,), torch.uint8, c)
-                colmask[:n_ctx].copy_(m8)
-                Cb[n_ctx:].zero_()
-                colmask[n_ctx:].fill_(1)
-            # fp32 encoder outputs are consumed as they are by the sim kernel (it rounds to bf16 while staging
-            # and leaves the bf16 images in Qb / Cb)
-            c_direct = q_f32 and c.dtype == torch.float32 and Nc == n_ctx
-            if not c_direct:
-                kn.prep(q, Qb, c, Cb[:n_ctx])
-                q_f32 = False
-        else:
-            # ONE all-gather: context rows (bf16) + mask bytes in trailing rows of the same buffer; the trailing
-            # rows become always-masked extra columns (the reference issues 4 fp32 all_gathers, :169-176)
-            rows_c = kn.packed_rows(n_ctx, d)
-            Nc = W * rows_c
-            if gather is not None:  # started under the query tower (ContextGather): only wait here
-                assert gather.shape == (n_ctx, d)
-                Cb = gather.wait()
-            else:
-                send = kn.empty((rows_c, d), _BF16, c)
-                kn.pack_ctx(c, m8, send)
-                Cb = kn.empty((Nc, d), _BF16, c)
-                D.all_gather_rows(send, Cb, group)
-            c_direct = False
-            # with a backward to follow, the one-call step reads the mask straight from the gathered buffer: no unpack launch
-            packed_step = q_f32 and wants_grad and (hasattr(kn, "train_step_packed_f32") or hasattr(kn, "inbatch_step_packed_f32"))
-            if not packed_step:
-                colmask = kn.empty((Nc,), torch.uint8, c)
-                kn.unpack_mask(Cb, W, n_ctx, colmask)
-            if not q_f32:
-                kn.cast_bf16(q, Qb)
-
-        inv_T = 1.0 / float(temperature)
+        m8 = _mask_u8(ctx_mask)
+        q_f32 = q.dtype == torch.float32 and caps.inbatch_fwd_f32
+        Qb = kn.empty((B, d), _BF16, q)
+        Qb, Cb, colmask, rows_c, Nc, c_direct, q_f32, packed_step = (
+            _stage_multi(kn, caps, q, c, m8, Qb, q_f32, W, group, gather, wants_grad) if multi else _stage_single(kn, q, c, m8, Qb, q_f32))
         grad_scale = inv_T / Nq  # d loss / d S of the global mean, before grad_output
         y_off = r * rows_c       # dpr_task.py:189-190 (label offset of this rank's columns)
-        eager = None  # gradients computed in this call, scaled by ctx.used (a device scalar)
-        used = None
-        S_dbg = None
-        loss_is_mean = False  # the kernel already multiplied the numerator by 1 / Nq
         dc_dtype = _dc_wire_dtype(group) if multi else torch.float32
-        if not multi and _fp32_g_mode() and wants_grad:
-            if q_f32:
-                row_loss, row_lse, loss_sum, G, S_dbg = kn.inbatch_fwd_f32(q, c if c_direct else None, Qb, Cb, pos_idx, y_off, colmask,
-                                                                           inv_T, grad_scale, want_logits=True)
-            else:
-                row_loss, row_lse, loss_sum, G, S_dbg = kn.inbatch_fwd(Qb, Cb, pos_idx, y_off, colmask, inv_T, grad_scale, want_logits=True)
-        elif multi and packed_step and hasattr(kn, "train_step_packed_f32"):
-            # forward and backward of this rank's rows in ONE library call; gradients scaled by the grad_output the last backward saw
-            used = _ExpectedGradScale.get(q.device, (B, Nc, d))
-            if _OPX_PACKED and kernels is None and q.is_contiguous() and pos_idx.dtype == torch.int64 and pos_idx.is_contiguous() \
-                    and dc_dtype in (torch.float32, _BF16):
-                # host side in C++ (csrc/opx.cpp: packed_train_step): the allocations, the library call and its fall-back to fp32
-                # partials in one function; backward's counterpart is packed_backward
-                loss_sum, row_lse, dQ, dC_part, Qb, G, part = _OPX.packed_train_step(q.detach(), Cb, pos_idx, W, r, n_ctx, inv_T, grad_scale, 1.0 / Nq,
-                                                                                     used, 0 if dc_dtype == _BF16 else 2)
-                G = G if (G is not None and G.numel() > 0) else None  # (an undefined at::Tensor arrives as None)
-                if part is not None and part.numel() > 0:
-                    dQ = (dQ, part)
-                ctx.opx_packed = True
-            else:
-                try:
-                    row_loss, row_lse, loss_sum, G, dQ, dC_part = kn.train_step_packed_f32(q, Cb, Qb, W, r, n_ctx, pos_idx, inv_T, grad_scale,
-                                                                                           1.0 / Nq, used, dc_dtype, defer_dq=True, want_G="auto")
-                except Exception as e:  # a plan without a bf16 dC epilogue: fp32 partials, rounded to the wire format in backward
-                    if dc_dtype == torch.float32 or "dc_kind" not in str(e):
-                        raise
-                    row_loss, row_lse, loss_sum, G, dQ, dC_part = kn.train_step_packed_f32(q, Cb, Qb, W, r, n_ctx, pos_idx, inv_T, grad_scale,
-                                                                                           1.0 / Nq, used, torch.float32, defer_dq=True,
-                                                                                           want_G="auto")
-            eager, loss_is_mean = (dQ, dC_part), True
-        elif multi and packed_step:  # (stand-in kernels of the CPU tests)
-            row_loss, row_lse, loss_sum, G, dQ, dC_part = kn.inbatch_step_packed_f32(q, Cb, Qb, W, r, n_ctx, pos_idx, inv_T, grad_scale)
-            eager = (dQ, dC_part)
-        elif q_f32 and wants_grad and hasattr(kn, "train_step_f32"):
-            # a backward will follow: forward and backward in ONE library call (two launches at the BASELINE shapes);
-            # backward() only checks the grad_output it was given against the one the gradients were scaled by
-            used = _ExpectedGradScale.get(q.device, (B, Nc, d))
-            row_loss, row_lse, loss_sum, G, dQ, dC_part = kn.train_step_f32(q, c if c_direct else None, Qb, Cb, pos_idx, y_off, colmask,
-                                                                            inv_T, grad_scale, 1.0 / Nq, used, defer_dq=True, want_G="auto")
-            eager, loss_is_mean = (dQ, dC_part), True
-        elif q_f32 and wants_grad and hasattr(kn, "inbatch_step_f32"):  # (stand-in kernels of the CPU tests)
-            row_loss, row_lse, loss_sum, G, dQ, dC_part = kn.inbatch_step_f32(q, c if c_direct else None, Qb, Cb, pos_idx,
-                                                                              y_off, colmask, inv_T, grad_scale)
-            eager = (dQ, dC_part)
-        elif q_f32:
-            row_loss, row_lse, loss_sum, G, _ = kn.inbatch_fwd_f32(q, c if c_direct else None, Qb, Cb, pos_idx, y_off,
-                                                                   colmask, inv_T, grad_scale)
-        else:
-            row_loss, row_lse, loss_sum, G, _ = kn.inbatch_fwd(Qb, Cb, pos_idx, y_off, colmask, inv_T, grad_scale)
+        bw, loss_sum, loss_is_mean, saved = _run_step(kn, caps, q, c if c_direct else None, Qb, Cb, colmask, Nc, q_f32, packed_step, pos_idx, W, r,
+                                                      n_ctx, inv_T, grad_scale, y_off, multi, wants_grad, dc_dtype, kernels)
         loss_sum = loss_sum[:1]
         if multi:
             D.all_reduce_sum(loss_sum, group)  # (of the means when loss_is_mean: the sum over ranks is the global mean)
         loss = (loss_sum if loss_is_mean else loss_sum / Nq).reshape(())
-
-        ctx.kn, ctx.group = kn, group
-        ctx.dims = (W, r, B, d, n_ctx, rows_c)
-        ctx.site = (B, Nc, d)
-        ctx.multi = multi
-        ctx.direct_ctx_grad = gather is not None  # c came straight from defer_context_grad (the task's own flow)
-        ctx.in_dtypes = (q.dtype, c.dtype)
-        ctx.eager, ctx.used = eager, used
-        ctx.spare = (Qb, Cb, G) if (eager is not None and used is not None) else None
-        # (G is None where the step never materialised the dScores: a second backward through a retained graph recomputes them)
-        ctx.regen = (pos_idx, y_off, None if (multi and packed_step) else colmask, inv_T, grad_scale) if ctx.spare is not None and G is None else None
-        ctx.pending = pending if multi else None
-        if eager is None:
-            ctx.save_for_backward(Qb, Cb, G)
-        ctx.row_lse = row_lse
-        ctx.dbg = None if S_dbg is None else (S_dbg, pos_idx + y_off, grad_scale)
+        if saved is not None:
+            ctx.save_for_backward(*saved)
+        if bw.kind is FP32G_DEBUG:
+            bw.labels = pos_idx + y_off
+        ctx.state = bw
+        bw.fast, bw.kn, bw.group, bw.W, bw.n_ctx, bw.rows_c, bw.d, bw.site, bw.multi = False, kn, group, W, n_ctx, rows_c, d, (B, Nc, d), multi
+        # direct_ctx_grad: c came straight from defer_context_grad (the task's own flow)
+        bw.direct_ctx_grad, bw.in_dtypes, bw.pending, bw.can_widen = gather is not None, (q.dtype, c.dtype), pending if multi else None, caps.widen
         return loss
 
     @staticmethod
     def backward(ctx, grad_out):
-        if ctx.fast is not None or getattr(ctx, "fast_done", False):
-            need_dq, need_dc = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-            go = grad_out if (grad_out.dtype == torch.float32 and grad_out.is_contiguous()) else grad_out.detach().float().contiguous()
-            if ctx.fast is not None:
-                # computed in forward for grad_output = *used: ONE launch compares and only rescales when the scale really changed; the
-                # tensors are handed to autograd and forgotten (see the general path below)
-                dQ, dC, part, used, site = ctx.fast
-                ctx.fast, ctx.fast_done = None, True
-                _, nxt = _OPX.rescale(dQ, part, dC, go, used, need_dq, need_dc)
-                _ExpectedGradScale.publish(go.device, nxt, site)
-            else:
-                # a second backward through a retained graph: the backward GEMMs run again on the operands the step left behind
-                kn = default_kernels()
-                Qb, Cb, G, pos_idx, mask, inv_T, grad_scale = ctx.regen
-                if G is None:
-                    G = kn.inbatch_fwd(Qb, Cb, pos_idx, 0, mask.view(torch.uint8) if mask.dtype == torch.bool else mask, inv_T, grad_scale)[3]
-                    ctx.regen = (Qb, Cb, G, pos_idx, mask, inv_T, grad_scale)
-                dQ, dC = kn.inbatch_bwd(G, Qb, Cb, 1.0, go.reshape(1), need_dq, need_dc)
-            return (dQ if need_dq else None), (dC if need_dc else None), None, None, None, None, None, None, None
-        kn, group = ctx.kn, ctx.group
-        W, r, B, d, n_ctx, rows_c = ctx.dims
+        st = ctx.state
         need_dq, need_dc = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if st.fast:  # FAST, or the REGEN it has turned into: fp32 in and out on one rank, nothing to slice, cast or reduce
+            go = grad_out if (grad_out.dtype == torch.float32 and grad_out.is_contiguous()) else grad_out.detach().float().contiguous()
+            if st.kind is FAST:
+                # computed in forward for grad_output = *used: ONE launch compares and only rescales when the scale really changed; the
+                # tensors are handed to autograd and forgotten (see PRESCALED below)
+                dQ, dC, part = st.grads
+                used, st.kind, st.grads, st.used = st.used, REGEN, None, None
+                _, nxt = _OPX.rescale(dQ, part, dC, go, used, need_dq, need_dc)
+                _ExpectedGradScale.publish(go.device, nxt, st.site)
+            else:
+                dQ, dC, st.G = _regen_grads(default_kernels(), st.Qb, st.Cb, st.G, st.pos_idx, 0, st.mask, st.inv_T, st.grad_scale, go.reshape(1),
+                                            need_dq, need_dc)
+            return (dQ if need_dq else None), (dC if need_dc else None), None, None, None, None, None, None, None
         go = grad_out.detach().reshape(1).float().contiguous()  # device scalar: AMP loss scale, no host sync
-        mine_ready = None
-        if ctx.eager is not None and ctx.used is not None:
-            # computed in forward for grad_output = *ctx.used; ONE launch compares and only rescales when the scale really changed.
+        mine_ready = None  # (the reduce-scatter's receive buffer, where csrc/opx.cpp has made it already)
+        if st.kind is PRESCALED:
+            # computed in forward for grad_output = *st.used; ONE launch compares and only rescales when the scale really changed.
             # The tensors are handed to autograd and FORGOTTEN here: AccumulateGrad takes a gradient nobody else references as
             # .grad itself, and clones it otherwise (one copy launch per step, 50 MB of traffic at cfg3 per rank).
-            dQ, dC_part = ctx.eager
-            ctx.eager = None
-            mine_ready = None
-            if ctx.opx_packed and ctx.multi:
+            dQs, dC_part = st.grads
+            dQ, part = dQs if isinstance(dQs, tuple) else (dQs, None)  # (dQ buffer, split-K slabs: the rescale adds them up into the buffer)
+            if st.opx_packed and st.multi:
                 # csrc/opx.cpp: the rescale launch, dC_part in the wire format (one cast launch where the step wrote fp32 for a bf16 wire)
                 # and the reduce-scatter's receive buffer, in one C++ call
-                part = dQ[1] if isinstance(dQ, tuple) else None
-                nxt, dC_part, mine_ready = _OPX.packed_backward(dQ[0] if isinstance(dQ, tuple) else dQ, part, dC_part, go, ctx.used,
-                                                                0 if _dc_wire_dtype(group) == _BF16 else 2, rows_c, need_dq, need_dc)
+                nxt, dC_part, mine_ready = _OPX.packed_backward(dQ, part, dC_part, go, st.used, 0 if _dc_wire_dtype(st.group) == _BF16 else 2,
+                                                                st.rows_c, need_dq, need_dc)
             else:
-                out2 = kn.rescale_grads(dQ if need_dq else None, dC_part if need_dc else None, go, ctx.used)
-                nxt = out2[1:2]
-            if isinstance(dQ, tuple):
-                dQ = dQ[0]  # (the slabs have been added up into it)
-            ctx.used = None
-            _ExpectedGradScale.publish(go.device, nxt, ctx.site)
-            go = None
-        elif ctx.spare is not None:
-            # a second backward through a retained graph: the first one gave its gradient tensors away; the backward GEMMs run
-            # again on the operands the step left behind (exact, rare)
-            Qb, Cb, G = ctx.spare
-            if G is None:
-                pos_idx, y_off, colmask, inv_T, grad_scale = ctx.regen
-                if colmask is None:
-                    colmask = kn.empty((Cb.shape[0],), torch.uint8, Cb)
-                    kn.unpack_mask(Cb, W, n_ctx, colmask)
-                G = kn.inbatch_fwd(Qb, Cb, pos_idx, y_off, colmask, inv_T, grad_scale)[3]
-                ctx.spare = (Qb, Cb, G)
-            dQ, dC_part = kn.inbatch_bwd(G, Qb, Cb, 1.0, go, need_dq, need_dc)
-            go = None
-        elif ctx.eager is not None:
-            dQ, dC_part = ctx.eager  # computed in forward for grad_output = 1 (stand-in kernels); the scale is applied below
-        elif ctx.dbg is not None:
-            # fp32-G debug mode: G = (exp(S - lse) - onehot) * scale recomputed in fp32, split into a bf16 pair, two GEMM passes
-            Qb, Cb, _ = ctx.saved_tensors
-            S, labels, gs = ctx.dbg
-            G32 = torch.exp(S - ctx.row_lse[:, None])
-            G32[torch.arange(S.shape[0], device=S.device), labels] -= 1.0
-            G32 *= gs
-            hi = G32.to(_BF16)
-            lo = (G32 - hi.float()).to(_BF16)
-            dQ1, dC1 = kn.inbatch_bwd(hi, Qb, Cb, 1.0, go, need_dq, need_dc)
-            dQ2, dC2 = kn.inbatch_bwd(lo, Qb, Cb, 1.0, go, need_dq, need_dc)
-            dQ = dQ1 + dQ2 if need_dq else None
-            dC_part = dC1 + dC2 if need_dc else None
+                nxt = st.kn.rescale_grads(dQs if need_dq else None, dC_part if need_dc else None, go, st.used)[1:2]
+            st.kind, st.grads, st.used = REGEN, None, None
+            _ExpectedGradScale.publish(go.device, nxt, st.site)
             go = None
         else:
-            Qb, Cb, G = ctx.saved_tensors
-            dQ, dC_part = kn.inbatch_bwd(G, Qb, Cb, 1.0, go, need_dq, need_dc)
-            go = None
+            dQ, dC_part, go = _local_grads(ctx, st, go, need_dq, need_dc)
         dq = dc = None
         if need_dq:
-            dq = (dQ if go is None else dQ * go).to(ctx.in_dtypes[0])
-        if need_dc:
-            if not ctx.multi:
-                dc = dC_part[:n_ctx]
-                dc = (dc if go is None else dc * go).to(ctx.in_dtypes[1])
-            else:
-                wire = _dc_wire_dtype(group)
-                mine = mine_ready if mine_ready is not None else kn.empty((rows_c, d), wire, dC_part)
-                if go is not None:
-                    dC_part = dC_part * go  # scale before the collective: nothing is left to do after it
-                if dC_part.dtype != wire:
-                    dC_part = dC_part.to(wire)  # half the bytes on the links (and in RCCL's reduction)
-                widen = wire != ctx.in_dtypes[1] and ctx.in_dtypes[1] == torch.float32 and hasattr(kn, "widen")
-                if ctx.pending is not None and ctx.direct_ctx_grad and (wire == ctx.in_dtypes[1] or widen):
-                    # reduce-scatter on RCCL's stream; whoever consumes dc (defer_context_grad, after the query-tower backward has
-                    # been enqueued) waits for it -- and, on a half-width wire, widens the result into the fp32 gradient there.
-                    # Only in the task's own flow (c IS the output of defer_context_grad: `gather` given), where autograd hands this
-                    # very tensor to that node.  Should anything still sit in between (another consumer of c, a hook), the tensor that
-                    # arrives there is a different one: the half-width wire therefore returns ZEROS here (whatever autograd adds to
-                    # them stays right) and post() adds the widened rows to whatever arrives instead of overwriting it.
-                    ctx.pending.work = D.reduce_scatter_rows(dC_part, mine, group, async_op=True)
-                    if widen:
-                        # nothing to return yet: a gradient of zeros that costs no launch (one cached zero, expanded).  post() hands
-                        # the widened rows on in its place, or adds them to whatever autograd made of it (zeros + somebody else's term)
-                        dc = _zeros_view((n_ctx, d), mine.device)
-
-                        def post(g, kn=kn, mine=mine, zptr=dc.data_ptr(), shape=(n_ctx, d)):
-                            if g.data_ptr() == zptr and g.stride() == (0, 0):
-                                return kn.widen(mine, kn.empty(shape, torch.float32, mine))
-                            g.add_(kn.widen(mine, kn.empty(shape, torch.float32, mine)).to(g.dtype))
-                            return g
-
-                        ctx.pending.post = post
-                    else:
-                        dc = mine[:n_ctx]
-                else:
-                    D.reduce_scatter_rows(dC_part, mine, group)  # sum over ranks of the partials of MY columns
-                    if widen:
-                        dc = kn.widen(mine, kn.empty((n_ctx, d), torch.float32, mine))
-                    else:
-                        dc = mine[:n_ctx].to(ctx.in_dtypes[1])
+            dq = (dQ if go is None else dQ * go).to(st.in_dtypes[0])
+        if need_dc and st.multi:
+            dc = _reduce_context_grads(st, dC_part, go, mine_ready)
+        elif need_dc:
+            dc = dC_part[:st.n_ctx]
+            dc = (dc if go is None else dc * go).to(st.in_dtypes[1])
         return dq, dc, None, None, None, None, None, None, None
 
 
@@ -1160,13 +1156,8 @@ def _pad_hidden(q, c):
 
 
 def _opx_regen(Qb, Cb, G, pos_idx, mask, inv_T, grad_scale, go, need_dq, need_dc):
-    """Second backward through a retained graph of the C++ node (csrc/opx.cpp: InBatchFn::backward): the backward GEMMs again, on the
-    operands the step left behind; the dScores are recomputed first where the step never materialised them."""
-    kn = default_kernels()
-    if G is None:
-        G = kn.inbatch_fwd(Qb, Cb, pos_idx, 0, mask.view(torch.uint8) if mask.dtype == torch.bool else mask, inv_T, grad_scale)[3]
-    dQ, dC = kn.inbatch_bwd(G, Qb, Cb, 1.0, go.reshape(1), need_dq, need_dc)
-    return dQ, dC, G
+    """Second backward through a retained graph of the C++ node (csrc/opx.cpp: InBatchFn::backward): see _regen_grads."""
+    return _regen_grads(default_kernels(), Qb, Cb, G, pos_idx, 0, mask, inv_T, grad_scale, go.reshape(1), need_dq, need_dc)
 
 
 _OPX_NODE = _OPX is not None and hasattr(_OPX, "inbatch_loss") and os.environ.get("DPRHOT_OPX_NODE", "1") != "0"
@@ -1176,8 +1167,7 @@ if _OPX_NODE:
 
 def inbatch_contrastive_loss(q, c, pos_idx, ctx_mask, temperature=1.0, group=None, kernels=None, gather=None, pending=None):
     if gather is None:
-        if (_OPX_NODE and kernels is None and q.is_cuda and (group is False or D.world(group)[0] == 1) and not _fp32_g_mode()
-                and not (D.force_dist() and group is not False)):
+        if _OPX_NODE and _plain_single_rank(q, group, kernels):
             # the plain single-rank fp32 step: a C++ autograd node (csrc/opx.cpp), no Python frame in forward or backward
             # (DPRHOT_OPX_NODE=0: InBatchContrastive's own fast path, the same two library calls from Python)
             loss = _OPX.inbatch_loss(q, c, pos_idx, ctx_mask, 1.0 / float(temperature), default_kernels()._lib.options_epoch())
@@ -1202,7 +1192,7 @@ class WindowedContrastive(torch.autograd.Function):
         Cb = kn.empty((Nc_pad, d), _BF16, c)
         kn.prep(q, Qb, c, Cb[:n_ctx])
         m8 = torch.ones(Nc_pad, dtype=torch.uint8, device=c.device)
-        m8[:n_ctx].copy_(ctx_mask.view(torch.uint8) if ctx_mask.dtype == torch.bool else ctx_mask)
+        m8[:n_ctx].copy_(_mask_bytes(ctx_mask))
         if Nc_pad != n_ctx:
             Cb[n_ctx:].zero_()
         inv_T = 1.0 / float(temperature)
@@ -1241,7 +1231,7 @@ def _sim_fwd(kn, q, c, colmask, inv_T):
     if colmask is not None or Nc_pad != Nc:
         m8 = torch.zeros(Nc_pad, dtype=torch.uint8, device=c.device)
         if colmask is not None:
-            m8[:Nc].copy_(colmask.view(torch.uint8) if colmask.dtype == torch.bool else colmask)
+            m8[:Nc].copy_(_mask_bytes(colmask))
         if Nc_pad != Nc:
             Cb[Nc:].zero_()
             m8[Nc:] = 1
@@ -1303,7 +1293,7 @@ class PairwiseScore(torch.autograd.Function):
     def forward(ctx, q, c, mask, kernels):
         kn = kernels if kernels is not None else default_kernels()
         qf, cf = q.detach().float().contiguous(), c.detach().float().contiguous()
-        m8 = None if mask is None else (mask.view(torch.uint8) if mask.dtype == torch.bool else mask.to(torch.uint8)).contiguous().view(-1)
+        m8 = None if mask is None else _mask_u8(mask).contiguous().view(-1)
         ctx.kn, ctx.in_dtypes = kn, (q.dtype, c.dtype)
         ctx.save_for_backward(qf, cf, m8)
         return kn.pairwise_fwd(qf, cf, m8)
@@ -1356,7 +1346,7 @@ def rank_and_loss(q, c, labels, colmask=None, inv_T=1.0, kernels=None):
     kn.cast_bf16(c, Cb[:Nc])
     m8 = torch.zeros(Nc_pad, dtype=torch.uint8, device=c.device)
     if colmask is not None:
-        m8[:Nc].copy_(colmask.view(torch.uint8) if colmask.dtype == torch.bool else colmask)
+        m8[:Nc].copy_(_mask_bytes(colmask))
     if Nc_pad != Nc:
         Cb[Nc:].zero_()
         m8[Nc:] = 1
