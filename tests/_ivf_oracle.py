@@ -5,7 +5,14 @@
     score(n, doc) = sum over entries (e, u) of query n of max(0, max over postings (doc, v) of expert e of <u, v>) + <cls_q[n], cls_doc[doc]>
 
 An entry whose expert has no posting for a doc adds 0; every doc id in [0, corpus_len) has a score.  `bf16=True` rounds every operand
-to bf16 first (round to nearest even), which is what the HIP path computes from.  Nothing here knows the packed device layout."""
+to bf16 first (round to nearest even), which is what the HIP path computes from.  Nothing here knows the packed device layout.
+
+Non-finite products ("Limits"): with p the fp64 dot product of an entry and a posting,
+
+    contribution of the entry to a doc = max over the doc's postings of (p if p > 0 else 0)
+
+so a NaN product counts as absent (it fails `p > 0`, whatever else the doc holds), a +inf product is positive and is added (the cell
+becomes +inf), -inf adds 0 -- and whether a doc HAS a posting (m, A below) is decided by the posting, not by the product's value."""
 import numpy as np
 import torch
 
@@ -33,14 +40,17 @@ def score_matrix(postings, queries, corpus_len, cls_q=None, cls_doc=None, bf16=F
             ids, V = post[int(e)]
             for u in vecs:
                 u = _r(u, bf16).reshape(-1)
-                dots = V @ u
-                absd = np.abs(V) @ np.abs(u)
-                best = np.full(corpus_len, -np.inf)
-                np.maximum.at(best, ids, dots)
+                with np.errstate(invalid="ignore"):  # (inf x 0 and inf - inf are NaN products, by the rule above)
+                    dots = V @ u
+                    absd = np.abs(V) @ np.abs(u)  # (A is an error model for finite operands; a NaN operand makes it a NaN)
+                best = np.zeros(corpus_len)
+                np.maximum.at(best, ids, np.where(dots > 0, dots, 0.0))  # (NaN > 0 is False: nothing folded here is a NaN)
                 babs = np.zeros(corpus_len)
-                np.maximum.at(babs, ids, absd)
-                has = np.isfinite(best)
-                S[n, has] += np.maximum(best[has], 0.0)
+                with np.errstate(invalid="ignore"):
+                    np.maximum.at(babs, ids, absd)
+                has = np.zeros(corpus_len, dtype=bool)
+                has[ids] = True
+                S[n, has] += best[has]
                 A[n, has] += babs[has]
                 m[n, has] += 1
     if cls_q is not None and len(cls_q):
