@@ -134,6 +134,11 @@ SIGNATURES = {
                                         c_int64, c_int, c_void_p, c_int64, c_void_p]),
     "dprhot_colbert_pq_search": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int, c_int,
                                          c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "dprhot_spar_workspace_bytes": (c_int, [c_int, c_int, c_int, POINTER(c_size_t)]),
+    "dprhot_spar_score": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, POINTER(c_float), c_int, c_int64,
+                                  c_int, c_void_p, c_int64, c_void_p]),
+    "dprhot_spar_search": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, POINTER(c_float), c_int, c_int64,
+                                   c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "dprhot_router_head_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
     "dprhot_router_head_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -236,6 +241,12 @@ def ivf_workspace_bytes(nq: int, n_entries: int, chunk: int, has_cls: bool) -> i
 def colbert_workspace_bytes(nq: int, chunk: int) -> int:
     out = c_size_t(0)
     check(lib.dprhot_colbert_workspace_bytes(int(nq), int(chunk), ctypes.byref(out)), "dprhot_colbert_workspace_bytes")
+    return out.value
+
+
+def spar_workspace_bytes(nq: int, W: int, chunk: int) -> int:
+    out = c_size_t(0)
+    check(lib.dprhot_spar_workspace_bytes(int(nq), int(W), int(chunk), ctypes.byref(out)), "dprhot_spar_workspace_bytes")
     return out.value
 
 

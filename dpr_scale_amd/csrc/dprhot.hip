@@ -38,6 +38,7 @@
 #include "router_head.h"
 #include "colbert.h"
 #include "colbert_pq.h"
+#include "spar.h"
 
 using namespace dprhot;
 
@@ -2875,6 +2876,106 @@ int dprhot_colbert_pq_search(const uint8_t* tok_code, const uint8_t* blk_rows, c
   };
   return topk_search_chunks("colbert_pq", fill, nq, corpus_len, id_begin, id_end, k, chunk, values, indices, first, workspace,
                             workspace_bytes, stream);
+}
+
+
+// ---- SPAR retrieval: two resident indexes, a grid of weights, one pass (csrc/spar.h) ----
+static int spar_check(const void* Q1, const void* Q2, int nq, int d1, int d2, const void* C1, const void* C2, int64_t n_ctx, const float* lam,
+                      int W) {
+  REQUIRE(Q1 && Q2 && C1 && C2 && lam, "NULL pointer (Q1, Q2, C1, C2 and lam are required)");
+  REQUIRE(aligned16(Q1) && aligned16(Q2) && aligned16(C1) && aligned16(C2), "operand rows must be 16-byte aligned");
+  REQUIRE(d1 > 0 && d1 % 32 == 0 && d2 > 0 && d2 % 32 == 0, "d1=%d and d2=%d must be positive multiples of 32 (pad with zeros)", d1, d2);
+  REQUIRE(W >= 1 && W <= SP_MAXW, "W=%d weights out of range (1 .. %d per call)", W, SP_MAXW);
+  for (int w = 0; w < W; ++w) REQUIRE(lam[w] - lam[w] == 0.f, "weight %d of %d is not finite", w, W);
+  REQUIRE(nq > 0 && (long long)W * nq < (1ll << 31) && nq <= 65535 * SP_B, "W * nq = %d * %d state rows out of range (1 .. 2^31 - 1)", W, nq);
+  REQUIRE(n_ctx > 0 && n_ctx < (1ll << 31), "n_ctx=%lld out of range (1 .. 2^31 - 1)", (long long)n_ctx);
+  return DPRHOT_OK;
+}
+
+// one launch of spar_kernel over passage ids j0 .. j0 + cols (checked by the callers)
+static SparArgs spar_args(const dprhot_bf16* Q1, const dprhot_bf16* Q2, int nq, int d1, int d2, const dprhot_bf16* C1, const dprhot_bf16* C2,
+                          const float* lam, int W, int64_t j0, int cols) {
+  SparArgs a{};
+  a.Q1 = reinterpret_cast<const uint16_t*>(Q1);
+  a.Q2 = reinterpret_cast<const uint16_t*>(Q2);
+  a.C1 = reinterpret_cast<const uint16_t*>(C1) + (size_t)j0 * d1;
+  a.C2 = reinterpret_cast<const uint16_t*>(C2) + (size_t)j0 * d2;
+  a.nq = nq; a.cols = cols; a.d1 = d1; a.d2 = d2; a.W = W;
+  for (int w = 0; w < W; ++w) a.lam[w] = lam[w];
+  return a;
+}
+static dim3 spar_grid(int nq, int cols) { return dim3((unsigned)cdiv(cols, SP_B), (unsigned)cdiv(nq, SP_B)); }
+
+int dprhot_spar_workspace_bytes(int nq, int W, int chunk, size_t* bytes) {
+  REQUIRE(bytes != nullptr, "NULL out pointer");
+  REQUIRE(W >= 1 && W <= SP_MAXW, "W=%d weights out of range (1 .. %d per call)", W, SP_MAXW);
+  REQUIRE(nq > 0 && (long long)W * nq < (1ll << 31), "W * nq = %d * %d state rows out of range (1 .. 2^31 - 1)", W, nq);
+  REQUIRE(chunk > 0 && chunk % 8 == 0, "chunk=%d must be a positive multiple of 8", chunk);
+  REQUIRE((long long)W * nq * chunk < (1ll << 40), "W * nq * chunk = %d * %d * %d candidate slots out of range (< 2^40)", W, nq, chunk);
+  *bytes = search_ws_bytes(W * nq, chunk);
+  return DPRHOT_OK;
+}
+
+int dprhot_spar_score(const dprhot_bf16* Q1, const dprhot_bf16* Q2, int nq, int d1, int d2, const dprhot_bf16* C1, const dprhot_bf16* C2,
+                      int64_t n_ctx, const float* lam, int W, int64_t doc_begin, int cols, float* S, int64_t ld, void* stream) {
+  if (int rc = spar_check(Q1, Q2, nq, d1, d2, C1, C2, n_ctx, lam, W)) return rc;
+  if (int rc = check_score_window(S, cols, ld, doc_begin, n_ctx)) return rc;
+  REQUIRE(ld % 8 == 0 && aligned16(S), "S must be 16-byte aligned with ld=%lld a multiple of 8", (long long)ld);
+  SparArgs a = spar_args(Q1, Q2, nq, d1, d2, C1, C2, lam, W, doc_begin, cols);
+  a.S = S;
+  a.ld = (long long)ld;
+  return launch<spar_kernel<false>>(spar_grid(nq, cols), dim3(256), 0, (hipStream_t)stream, a);
+}
+
+int dprhot_spar_search(const dprhot_bf16* Q1, const dprhot_bf16* Q2, int nq, int d1, int d2, const dprhot_bf16* C1, const dprhot_bf16* C2,
+                       int64_t n_ctx, const float* lam, int W, int64_t id_begin, int64_t id_end, int k, int chunk, float* values,
+                       int64_t* indices, int first, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = spar_check(Q1, Q2, nq, d1, d2, C1, C2, n_ctx, lam, W)) return rc;
+  REQUIRE(values && indices, "NULL pointer");
+  REQUIRE(k >= 1 && k <= n_ctx, "topk=%d out of range (1 .. n_ctx=%lld)", k, (long long)n_ctx);
+  REQUIRE(0 <= id_begin && id_begin < id_end && id_end <= n_ctx, "bad passage-id range [%lld, %lld) of %lld", (long long)id_begin,
+          (long long)id_end, (long long)n_ctx);
+  REQUIRE(chunk > 0 && chunk % 8 == 0, "chunk=%d must be a positive multiple of 8", chunk);
+  REQUIRE((long long)W * nq * chunk < (1ll << 40), "W * nq * chunk = %d * %d * %d candidate slots out of range (< 2^40)", W, nq, chunk);
+  const int rows = W * nq;
+  const bool wide = k > TK_KWIDE;
+  const size_t need = search_ws_bytes(rows, chunk) + (wide ? wsel_ws_bytes(rows, k) : 0);
+  if (workspace == nullptr || workspace_bytes < need)
+    return fail(DPRHOT_E_WORKSPACE, "spar_search needs %zu workspace bytes (dprhot_spar_workspace_bytes%s), got %zu", need,
+                wide ? " + dprhot_topk_wide_workspace_bytes" : "", workspace_bytes);
+  REQUIRE(aligned16(workspace), "workspace must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  if (k > TK_KMAX) {  // beyond the candidate-list merge: every chunk materialised, the chunk driver's selection
+    auto fill = [&](int64_t j0, int cols, float* S, int ld) {
+      return dprhot_spar_score(Q1, Q2, nq, d1, d2, C1, C2, n_ctx, lam, W, j0, cols, S, ld, stream);
+    };
+    return topk_search_chunks("spar", fill, rows, n_ctx, id_begin, id_end, k, chunk, values, indices, first, workspace, workspace_bytes,
+                              stream);
+  }
+  // the layout of dprhot_search for W * nq rows: scores of the first chunk / candidate values, candidate columns, candidate counts
+  float* S = static_cast<float*>(workspace);
+  int* cand_j = reinterpret_cast<int*>(static_cast<char*>(workspace) + (size_t)rows * chunk * 4);
+  int* cnt = reinterpret_cast<int*>(static_cast<char*>(workspace) + (size_t)rows * chunk * 8);
+  HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)rows * sizeof(int), st));
+  for (int64_t j0 = id_begin; j0 < id_end; j0 += chunk) {
+    const int cols = (int)(id_end - j0 < chunk ? id_end - j0 : chunk);
+    const int ld = (cols + 7) / 8 * 8;  // (<= chunk: chunk is a multiple of 8)
+    SparArgs a = spar_args(Q1, Q2, nq, d1, d2, C1, C2, lam, W, j0, cols);
+    if (first && j0 == id_begin) {  // nothing to filter against yet: materialise this chunk's scores and select from them
+      a.S = S;
+      a.ld = ld;
+      if (int rc = launch<spar_kernel<false>>(spar_grid(nq, cols), dim3(256), 0, st, a)) return rc;
+      if (int rc = dprhot_topk_update(S, rows, cols, ld, j0, k, values, indices, 1, stream)) return rc;
+      continue;
+    }
+    // scores that cannot enter a row's top-k never leave the tile; at most `cols` candidates per row and chunk
+    a.kth_val = values; a.kth_idx = indices; a.k = k; a.col_offset = (long long)j0;
+    a.cnt = cnt; a.cand_v = S; a.cand_j = cand_j; a.ldc = ld;
+    if (int rc = launch<spar_kernel<true>>(spar_grid(nq, cols), dim3(256), 0, st, a)) return rc;
+    TopkArgs p{S, rows, cols, (long long)ld, (long long)j0, k, values, indices, 0, cand_j, cnt};
+    if (int rc = launch_topk(p, rows, st)) return rc;
+  }
+  return DPRHOT_OK;
 }
 
 }  // extern "C"

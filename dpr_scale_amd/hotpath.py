@@ -602,6 +602,33 @@ class HipKernels:
                                                        int(pool), *self._topk_tail(id_begin, id_end, values, indices, first, chunk, ws)),
                         "dprhot_colbert_search")
 
+    # -- SPAR: two resident indexes, a grid of weights in one pass (csrc/spar.h; dpr_scale_amd/spar.py) ----
+    def spar_workspace(self, nq, W, chunk, k, like):
+        return self._chunk_workspace(self._lib.spar_workspace_bytes(nq, W, chunk), W * nq, k, like)
+
+    def _spar_operands(self, index, q1, q2, lam):
+        """Q1, Q2, nq, d1, d2, C1, C2, n_ctx, lam, W: what both SPAR entry points begin with; lam is a host sequence of floats."""
+        self._require_gpu(q1, q2, index.c1, index.c2)
+        assert q1.dtype == _BF16 and q2.dtype == _BF16 and q1.is_contiguous() and q2.is_contiguous() and q1.shape[0] == q2.shape[0]
+        assert q1.shape[1] == index.c1.shape[1] and q2.shape[1] == index.c2.shape[1], "query widths must be the index's padded widths"
+        W = len(lam)
+        return (_ptr(q1), _ptr(q2), q1.shape[0], q1.shape[1], q2.shape[1], _ptr(index.c1), _ptr(index.c2), index.corpus_len,
+                (ctypes.c_float * W)(*[float(x) for x in lam]), W)
+
+    def spar_score(self, index, q1, q2, lam, doc_begin, cols, S):
+        """Writes s[w][i][j] = fma(lam[w], <q2[i], c2[j]>, <q1[i], c1[j]>) of passages doc_begin .. doc_begin + cols into S [W * nq, >= cols]
+        fp32, row w * nq + i (dprhot_spar_score)."""
+        self._require_gpu(S)
+        self._lib.check(self.lib.dprhot_spar_score(*self._spar_operands(index, q1, q2, lam), int(doc_begin), int(cols), _ptr(S), S.stride(0),
+                                                   self._stream()), "dprhot_spar_score")
+
+    def spar_search(self, index, q1, q2, lam, id_begin, id_end, values, indices, first, chunk, ws):
+        """Folds passage ids [id_begin, id_end) into the running top-k of every weight, values / indices [W * nq, k] (dprhot_spar_search)."""
+        self._require_gpu(values, indices, ws)
+        self._lib.check(self.lib.dprhot_spar_search(*self._spar_operands(index, q1, q2, lam),
+                                                    *self._topk_tail(id_begin, id_end, values, indices, first, chunk, ws)),
+                        "dprhot_spar_search")
+
     # -- product-quantised postings (csrc/ivf_pq.h; DESIGN.md section 10.2; dpr_scale_amd/ivf.py owns training and the index) ----
     def pq_encode(self, vec, codebook, entry="dprhot_pq_encode"):
         """codes uint8 [n, m] of the rows vec bf16 [n, dp] under codebook bf16 [m, 256, dsub] (dprhot_pq_encode)."""

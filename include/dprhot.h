@@ -460,6 +460,31 @@ int dprhot_colbert_pq_search(const uint8_t* tok_code, const uint8_t* blk_rows, c
                              int64_t id_begin, int64_t id_end, int k, int chunk, float* values, int64_t* indices, int first,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* SPAR retrieval (spar/spar_retrieval.py, spar_weight_tuning.py; csrc/spar.h): a dense retriever and a lexical
+ * model searched together, for a whole grid of weights in one pass over the corpus.  Two resident indexes C1 bf16 [n_ctx, d1] and
+ * C2 bf16 [n_ctx, d2] (passage id = row), queries Q1 bf16 [nq, d1] and Q2 bf16 [nq, d2], row-major without padding between rows,
+ * d1 and d2 positive multiples of 32 (pad with zeros), weights lam fp32 [W] on the HOST (passed to the kernel by value), 1 <= W <= 32:
+ *   s[w][i][j] = fmaf(lam[w], <Q2[i], C2[j]>, <Q1[i], C1[j]>)
+ * bf16 products, fp32 accumulators, ONE fp32 fma per score.  The order of the additions inside the two dot products is fixed: a score
+ * depends on its four rows and lam[w] only, and has the same bits whether dprhot_spar_score stores it or dprhot_spar_search ranks it.
+ * dprhot_spar_score WRITES S[w * nq + i][j - doc_begin] for doc_begin <= j < doc_begin + cols <= n_ctx, every cell and nothing else of
+ * S [W * nq, ld] (ld >= cols, ld % 8 == 0).
+ * dprhot_spar_search folds passage ids [id_begin, id_end) into values / indices [W * nq, k] (row w * nq + i): total order, `first`,
+ * the -inf / -1 unfilled tail and "a NaN is never selected" as in dprhot_topk_update; disjoint id ranges may be folded into one result,
+ * which for every w equals dprhot_topk over the dprhot_spar_score matrix of those ranges bit for bit.  k <= 1024: the first chunk of an
+ * empty state is materialised and selected from, every other chunk leaves the GEMM tile as candidate lists (only scores that rank ahead
+ * of their row's k-th entry) which the streaming top-k merges; k > 1024: every chunk is materialised (k > 4096: the HBM-resident
+ * selection).  workspace: dprhot_spar_workspace_bytes(nq, W, chunk) (+ dprhot_topk_wide_workspace_bytes(W * nq, k) behind it when
+ * k > 4096); DPRHOT_E_WORKSPACE when smaller.
+ * Limits (DPRHOT_E_INVALID): NULL or not 16-byte aligned pointers, d1 / d2 % 32, W outside 1 .. 32, a non-finite weight, W * nq >= 2^31,
+ * W * nq * chunk >= 2^40, not 0 <= id_begin < id_end <= n_ctx < 2^31, not 1 <= k <= n_ctx, chunk % 8. */
+int dprhot_spar_workspace_bytes(int nq, int W, int chunk, size_t* bytes);
+int dprhot_spar_score(const dprhot_bf16* Q1, const dprhot_bf16* Q2, int nq, int d1, int d2, const dprhot_bf16* C1, const dprhot_bf16* C2,
+                      int64_t n_ctx, const float* lam, int W, int64_t doc_begin, int cols, float* S, int64_t ld, void* stream);
+int dprhot_spar_search(const dprhot_bf16* Q1, const dprhot_bf16* Q2, int nq, int d1, int d2, const dprhot_bf16* C1, const dprhot_bf16* C2,
+                       int64_t n_ctx, const float* lam, int W, int64_t id_begin, int64_t id_end, int k, int chunk, float* values,
+                       int64_t* indices, int first, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The CITADEL / SPLADE encoder head behind the MLM logits (dpr_scale/models/citadel_models/citadel_model.py:46-82, splade_model.py:26-32;
  * csrc/router_head.h), forward and backward without a [B, T, V] temporary.  logits [B, T1, V] of `dtype` (0 bf16,
  * 1 fp16, 2 fp32) with unit column stride and ELEMENT strides stride_b / stride_t (a [:, 1:, :] view or a column slice of a wider buffer
