@@ -146,50 +146,30 @@ int launch(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... arg
 
 // ---- explicit process-wide options (dprhot_set_option): test and A/B switches of the plans.  Production never sets one; they replace
 // the environment switches the library used to cache on first use (hidden configuration behind an ABI that advertises none).
-enum OptId { OPT_TILE, OPT_NO_TR, OPT_UNFUSED_BWD, OPT_BIG_MIN, OPT_NO_NL, OPT_NO_BIG_BWD, OPT_NO_SKINNY, OPT_NO_SMALL_STEP, OPT_NO_SHORT,
-             OPT_SK_COLS, OPT_SEARCH_UNFUSED, OPT_NO_8PB, OPT_NO_WIDE, OPT_WIDE_NOCOPY, OPT_NO_8P_STORE, OPT_NO_WIDE_BWD, OPT_NT_STORES, OPT_SK_DQ_SLICES, OPT_SK_FUSED, OPT_SK_DBG, OPT_SK_W8, OPT_SK_PAIR, OPT_SK_SIM_W8, OPT_SK_SIM_PRIV, OPT_SK_TAIL, OPT_SK_DC_REGSCALE, OPT_G8_ONE_TILE, OPT_NL_P16, OPT_SK_DQ_ATOMIC, OPT_NL_MIN, OPT_G128_DMA, OPT_DC_ALONE_8P, OPT_DQ_ONE_ROUND, OPT_DQ_CAP_FEW, OPT_LOSS_WITH_DQ, OPT_NL128, OPT_NL128_BELOW, OPT_PAIR128, OPT_PAIR128_CAP, OPT_NL128_MIN_TILES, OPT_P16_STAGED, OPT_SMALL_SIM, OPT_SMALL_STEP_ROLES, OPT_SMALL_SIM_COPY, OPT_COUNT };
+enum OptId { OPT_TILE, OPT_NO_TR, OPT_BIG_MIN, OPT_NO_SKINNY, OPT_NO_SMALL_STEP, OPT_NO_WIDE, OPT_NO_WIDE_BWD, OPT_SK_FUSED, OPT_SK_W8,
+             OPT_SK_PAIR, OPT_SK_TAIL, OPT_SK_DC_REGSCALE, OPT_NL_P16, OPT_SK_DQ_ATOMIC, OPT_NL_MIN, OPT_G128_DMA, OPT_LOSS_WITH_DQ,
+             OPT_NL128, OPT_PAIR128, OPT_P16_STAGED, OPT_SMALL_SIM, OPT_SMALL_STEP_ROLES, OPT_SMALL_SIM_COPY, OPT_COUNT };
 struct OptDef { OptId id; const char* name; int def; const char* what; };
 constexpr OptDef kOptDefs[OPT_COUNT] = {
     {OPT_TILE, "tile", -1, "0..5 pins the tile of the single-GEMM launches (gemm_bf16.h), -1 = plan"},
     {OPT_NO_TR, "no_tr", 0, "1 swaps the LDS transpose read for plain 16-bit gathers (cross-check)"},
-    {OPT_UNFUSED_BWD, "unfused_bwd", 0, "1 runs dC and dQ as two launches"},
     {OPT_BIG_MIN, "big_min", 256, "fewest 256x256 tiles for which the large-shape kernels are chosen (0 = never; tests lower it)"},
-    {OPT_NO_NL, "no_nl", 0, "1 disables the no-logits forward"},
-    {OPT_NO_BIG_BWD, "no_big_bwd", 0, "1 disables the 256x256 backward pair"},
     {OPT_NO_SKINNY, "no_skinny", 0, "1 disables the few-rows x many-contexts plan (skinny.h)"},
     {OPT_NO_SMALL_STEP, "no_small_step", 0, "1 disables the fused softmax+backward kernel of the latency-bound shapes (step_small.h)"},
-    {OPT_NO_SHORT, "no_short", 0, "1 disables the short-row (K-split slab) forward"},
-    {OPT_SK_COLS, "sk_cols", 0, "64 / 128 forces the sim unit width of the skinny plan, 0 = plan"},
-    {OPT_SEARCH_UNFUSED, "search_unfused", 0, "1 materialises every chunk's scores in dprhot_search (no filter epilogue)"},
-    {OPT_NO_8PB, "no_8pb", 0, "1 keeps the backward pair on gemm256.h instead of the phase-interleaved schedule"},
     {OPT_NO_WIDE, "no_wide", 0, "1 keeps vocabulary-wide fp32 operands on the register-staged sim kernel (wide.h off)"},
-    {OPT_WIDE_NOCOPY, "wide_nocopy", 0, "TIMING EXPERIMENT ONLY: 1 drops the bf16 copy-out of wide.h (the backward then reads garbage)"},
-    {OPT_NO_8P_STORE, "no_8p_store", 0, "1 keeps dprhot_sim_fwd's large shapes on the round-1 256 x 256 kernel (gemm256.h)"},
     {OPT_NO_WIDE_BWD, "no_wide_bwd", 0, "1 keeps the backward of vocabulary-wide vectors on the generic pair kernel (skinny.h units off)"},
-    {OPT_NT_STORES, "nt_stores", 1, "0 writes dC_part of the few-rows plans (skinny.h units: cfg3 per rank, router width) with plain instead of non-temporal stores (A/B of the cache policy)"},
-    {OPT_SK_DQ_SLICES, "sk_dq_slices", 0, "context slices of the few-rows plan's dQ units (0 = plan)"},
     {OPT_SK_FUSED, "sk_fused", 1, "few-rows plan without its dScores launch (G == NULL): 1 = where it measured faster (B x Nc >= 2^19), 2 = wherever the plan exists (tests), 0 = never"},
-    {OPT_SK_DBG, "sk_dbg", 0, "TIMING EXPERIMENTS ONLY (fused few-rows backward; bits): 1 dC units leave at once, 2 dQ units leave at once, 4 (unused), 8 the plain slab sum in the finishing launch's place (wrong dQ), 16 the dQ slabs leave with ordinary instead of non-temporal stores"},
     {OPT_SK_W8, "sk_w8", 1, "fused few-rows backward with eight waves per workgroup (512 threads, half the output tile per wave: 13.0-13.5 against 13.9-14.4 us at cfg3 per rank); 0 = four"},
     {OPT_SK_PAIR, "sk_pair", 0, "fused few-rows backward with one kind of unit (sk_bwdp_kernel: a P tile is loaded once for both products: measured 21.2 against 13.5 us at cfg3 per rank); 0 = dQ units and dC units (sk_bwdf_kernel)"},
-    {OPT_SK_SIM_W8, "sk_sim_w8", 1, "few-rows sim launch with eight waves per workgroup (128-column units, fp32 q): 0 = four"},
-    {OPT_SK_SIM_PRIV, "sk_sim_priv", 1, "few-rows sim launch with wave-private rings and no barrier in the K loop (sk_simp_kernel; fp32 q, 128-column units, grids of at most one unit per CU): 0 = sk_sim_kernel"},
     {OPT_SK_TAIL, "sk_tail", 0, "fused few-rows backward: 1 = the dQ slabs are folded by the last workgroups of the backward launch itself, behind a count of the dQ units (write-through slab stores, sc1 loads; no sk_dq_finish launch), 2 = the same with ordinary stores + one release fence per dQ unit and an acquire fence in the finishing role; 0 = the finishing launch (measured: scratch/negative/README.md, round 5)"},
     {OPT_SK_DC_REGSCALE, "sk_dc_regscale", 0, "fused few-rows backward, dC units: 1 = the Q fragments are scaled by f in registers between the transpose read and the MFMA (no scale pass over the LDS image, one workgroup barrier less; measured: the pass's 0.75 us reappear in the MFMA loop, step 25.7-25.8 against 25.3-25.6 us), 0 = the scale pass of round 4"},
-    {OPT_G8_ONE_TILE, "g8_one_tile", 0, "storing epilogues of the phase-interleaved 256 x 256 kernel (dScores pass, stored logits): 1 = one workgroup per tile instead of persistent workgroups (a finished workgroup's stores drain under its successor's prologue)"},
     {OPT_NL_P16, "nl_p16", 1, "no-logits forward with the dScores wanted: 1 = ONE pass of the GEMM (strip statistics + the tile's fp16 softmax numerators, Epi8StatsP, two-phase schedule) and a row kernel that rescales them into G in place; 0 = two GEMM passes (statistics, then the logits recomputed into G: Epi8G)"},
     {OPT_SK_DQ_ATOMIC, "sk_dq_atomic", 0, "fused few-rows backward: 1 = the dQ units scale their tiles to the row softmax themselves and ADD them into dQ (global_atomic_add_f32; dQ zero-filled by the sim launch): no slabs, no finishing launch -- dQ reproducible to rounding, not to the bit; 0 = slice-normalised slabs + sk_dq_finish_kernel (bit-reproducible)"},
     {OPT_NL_MIN, "nl_min", 128, "fewest 256x256 tiles from which the forward never stores the logits (round 6: 128 -- with the one-pass forward 1024 x 8192 x 768 steps in 81 instead of 92 us, 512 x 16384 in 116 instead of 126; at 64 tiles it is a wash, at 32 it loses); the smaller of this and big_min counts"},
     {OPT_G128_DMA, "g128_dma", 1, "128 x 128 x 64 tile of the GEMM engine with its operands staged by LDS-DMA (gemm128d.h) instead of global -> VGPR -> ds_write (gemm_bf16.h): 1 = wherever the launch qualifies (bf16 operands, whole 64-deep K steps, 32-bit offsets); 0 = never"},
-    {OPT_DC_ALONE_8P, "dc_alone_8p", 1, "long context axis (512 <= B <= 2048, Nc >= 32 B): the dC tiles ALONE on the phase-interleaved 256 x 256 kernel (gemm8pb.h) in a launch of their own, in front of the launch with the dQ units, instead of dC on the 128 x 128 tile: 1 = where the row pitch of G is a multiple of 128 KiB (Nc = 65536: the 128-wide tiles' 256-byte pieces then alias in the memory system -- 180 us where 126 are expected -- and the 512-byte pieces of the 256-wide tile do not: backward 325 -> 275 us at 1024 x 65536, 557 -> 470 at 2048 x 65536; it LOSES at 32768 / 49152 columns: profiles/r06_dc_alone_ab.txt), 2 = always, 0 = never"},
-    {OPT_DQ_ONE_ROUND, "dq_one_round", 1, "long context axis (1024 <= B <= 2048, Nc >= 32 B): 1 = the context slices of the dQ units are cut so that the units fill the 256 CUs once (up to 32 slices: 1536 x 65536 x 768 backward 419 -> 351 us, 2048 x 65536 497 -> 459, 1024 x 65536 294 -> 282; profiles/r06_dq_round_ab.txt), 0 = at most 16 slices"},
-    {OPT_DQ_CAP_FEW, "dq_cap_few", 0, "256 x 256 backward pair under 512 query rows: the most context slices a dQ tile is cut into; 0 = the rule (16, or 32 where 16 slices already take more than one round of the 256 CUs), else that many"},
     {OPT_LOSS_WITH_DQ, "loss_with_dq", 1, "one-call training step on the no-logits forward, single rank: 1 = the sum of the row losses is formed by one more workgroup of the launch that combines the dQ slabs (same arithmetic as reduce_sum_kernel) instead of a launch of its own between forward and backward; 0 = its own launch"},
     {OPT_NL128, "nl128", 1, "training forward (dScores wanted, logits not) in ONE pass on the 128 x 128 LDS-DMA tile (EpiSimP: strip statistics + fp16 softmax numerators, then the row kernel of the 256 x 256 family) where the 256-wide tiles would leave most of the chip idle: 1 = on, 0 = the logits-storing forward (sim GEMM with fp32 S, streaming softmax) there"},
-    {OPT_NL128_BELOW, "nl128_max_tiles", 512, "the 128-tile one-pass forward takes the shapes with at most this many 128 x 128 tiles (512 = one round of two workgroups per CU; beyond, where the 256 x 256 no-logits forward qualifies, that one runs: 1536 x 8192 x 768, 768 tiles, 48.6 us against ~37)"},
     {OPT_PAIR128, "pair128", 1, "backward pair (dC tiles next to split-K dQ tiles in one launch) on the 128 x 128 LDS-DMA tile (gemm128d_pair_kernel): 1 = where the rule pair128_use picks it, 2 = wherever the launch qualifies (A/B), 0 = never (the register-staged pair / the 256 x 256 pair)"},
-    {OPT_PAIR128_CAP, "pair128_slices", 0, "K slices of a dQ tile in the 128 x 128 backward pair: 0 = the rule of pair128_plan, else that many (A/B)"},
-    {OPT_NL128_MIN_TILES, "nl128_min_tiles", 32, "fewest 128 x 128 tiles for the 128-tile one-pass forward (32 against 128, step us: 512 x 2048 44.1 -> 40.7, 768 x 2048 49.7 -> 42.5, 1024 x 1024 47.3 -> 43.5, 256 x 4096 / 192 x 4096 / 256 x 2048 level)"},
     {OPT_P16_STAGED, "p16_staged", 1, "one-pass forward on the 256 x 256 kernel: the fp16 numerators leave through the per-wave LDS patch (64-byte pieces of 16 rows per store instruction instead of 32-byte pieces of 32 rows; bit-identical): 1 = except where the row pitch of G is a multiple of 128 KiB (forward us, arms alternating, profiles/r06_p16_staged_ab.txt: 8192^2 155.4 -> 147.8, 4096 x 8192 83.2 -> 79.3, 4096 x 16384 153 -> 146 and its step 390 -> 372; at 65536 columns the forward gains nothing and the step of 8192 x 65536 LOSES 100 us of 2880), 2 = always, 0 = never"},
     {OPT_SMALL_SIM, "small_sim", 1, "sim launch of the batch-32 step (B <= 32, fp32 q, 256-deep K chunks: sim_small.h): 1 = one wave per 16 x 16 tile and K chunk on an exact 3-D grid (row tile, column tile, chunk: no division and one wait on the arguments in front of the first operand load, the mask byte loaded last), whole-line loads rounded into a wave-private LDS patch, no barrier (bit-identical to the engine; 32 x 256 x 768 step 9.19 -> 8.29 us, with the 3-D grid 7.21 -> 7.05); 0 = the GEMM engine (tile 5); A/B only: 2 = fp32 straight into fragment registers, no LDS (8.52 us), 3 / 4 = forms 1 / 2 with two waves per workgroup (8.70 / 9.41 us)"},
     {OPT_SMALL_STEP_ROLES, "small_step_roles", 3, "softmax + backward launch of the batch-32 step (B <= 32, at most 768 columns: step_small_kernel_roles / step_small_kernel_out in step_small.h): one launch split by role -- d / 16 dC workgroups (slabs + Q tile, full softmax, one barrier, dC product and stores) next to one dQ workgroup per 16-row half and column tile (half the slabs + C tile, 8 K slices); 3 = form 2 with the outputs written by workgroups of their own that have no product to do, in front of the grid, instead of by the dC workgroup of tile 0: a loss block (softmax up to the row loss, logsumexp / row loss, one barrier, the loss sum) and two row-store blocks (one 16-row half each: dScores / logits, no barrier); the device-side scale is the last load of a role, not a wait in front of it (a stamping launch of the packed step keeps form 2), 2 = 32-column dQ tiles (d % 32 == 0, else form 1; 32 x 256 x 768 step 8.29 -> 7.74 us), 1 = 16-column dQ tiles (7.84 us), 0 = every workgroup does both products (step_small_kernel); all forms bit-identical (tests/test_small_step_roles.py, tests/test_small_step_out.py, tests/test_small_step_split_gpu.py)"},
@@ -217,8 +197,6 @@ bool use_tr() { return opt(OPT_NO_TR) == 0; }
 
 int force_tile() { return opt(OPT_TILE); }
 
-bool unfused_bwd() { return opt(OPT_UNFUSED_BWD) != 0; }
-
 constexpr int kNumCU = 256;
 
 // tile configurations {BM, BN, BK}
@@ -238,23 +216,26 @@ bool big_ok(int M, int N, int K) {
 // as the 256x256 tile, plus an even number of K steps and operands addressable with 32-bit byte offsets.
 // (the storing / filtering uses of the same kernel -- dprhot_sim_fwd, dprhot_search -- keep the 256-tile gate they were measured at)
 bool g8_ok(int M, int N, int K) {
-  return !opt(OPT_NO_NL) && force_tile() < 0 && big_ok(M, N, K) && K % 128 == 0 && (double)M * K * 2 < 4.0e9 && (double)N * K * 2 < 4.0e9;
+  return force_tile() < 0 && big_ok(M, N, K) && K % 128 == 0 && (double)M * K * 2 < 4.0e9 && (double)N * K * 2 < 4.0e9;
 }
 bool nl_ok(int M, int N, int K) {
   const long wgs = (long)((M + 255) / 256) * ((N + 255) / 256);
   const int need = big_min_wgs() < opt(OPT_NL_MIN) ? big_min_wgs() : opt(OPT_NL_MIN);
   const bool big = M > 128 && K % 64 == 0 && K >= 128 && big_min_wgs() > 0 && wgs >= need;  // (big_ok with this plan's own tile count)
-  return !opt(OPT_NO_NL) && force_tile() < 0 && big && K % 128 == 0 && (double)M * K * 2 < 4.0e9 && (double)N * K * 2 < 4.0e9;
+  return force_tile() < 0 && big && K % 128 == 0 && (double)M * K * 2 < 4.0e9 && (double)N * K * 2 < 4.0e9;
 }
 
 // One-pass training forward on the 128 x 128 LDS-DMA tile (EpiSimP + g8_lse_p2g_kernel): more than 128 rows, whole 64-deep K steps,
-// at least 32 128-wide tiles (option nl128_min_tiles); where the 256 x 256 forward qualifies too, at most one round of them (option
-// nl128_max_tiles) and fewer than 256 tiles of 256 x 256 -- where it does not (K a multiple of 64 but not of 128), every size; 32-bit
-// element offsets.
+// at least kNl128MinTiles 128-wide tiles; where the 256 x 256 forward qualifies too, at most one round of them (kNl128MaxTiles) and
+// fewer than 256 tiles of 256 x 256 -- where it does not (K a multiple of 64 but not of 128), every size; 32-bit element offsets.
+// kNl128MinTiles: 32 against 128, step us: 512 x 2048 44.1 -> 40.7, 768 x 2048 49.7 -> 42.5, 1024 x 1024 47.3 -> 43.5, 256 x 4096 /
+// 192 x 4096 / 256 x 2048 level.  kNl128MaxTiles: 512 = one round of two workgroups per CU; beyond, where the 256 x 256 no-logits forward
+// qualifies, that one runs: 1536 x 8192 x 768, 768 tiles, 48.6 us against ~37.
+constexpr int kNl128MinTiles = 32, kNl128MaxTiles = 512;
 bool nl128_ok(int M, int N, int K) {
-  if (!opt(OPT_NL128) || opt(OPT_NO_NL) || !opt(OPT_G128_DMA) || !opt(OPT_NL_P16) || force_tile() >= 0) return false;
+  if (!opt(OPT_NL128) || !opt(OPT_G128_DMA) || !opt(OPT_NL_P16) || force_tile() >= 0) return false;
   const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128), t256 = (long)((M + 255) / 256) * ((N + 255) / 256);
-  return M > 128 && K % 64 == 0 && K >= 64 && N % 8 == 0 && N >= 1024 && t128 >= opt(OPT_NL128_MIN_TILES) && (!nl_ok(M, N, K) || (t128 <= opt(OPT_NL128_BELOW) && t256 < 256)) &&
+  return M > 128 && K % 64 == 0 && K >= 64 && N % 8 == 0 && N >= 1024 && t128 >= kNl128MinTiles && (!nl_ok(M, N, K) || (t128 <= kNl128MaxTiles && t256 < 256)) &&
          (double)M * K < 4.0e9 && (double)N * K < 4.0e9 && (N + 63) / 64 <= 1024 * 64;
 }
 
@@ -302,8 +283,7 @@ int launch_big(const GemmArgs& a, const Epi& epi, hipStream_t st) {
 template <class Epi, int SCHED = 4>
 int launch_g8(const GemmArgs& a, const Epi& epi, hipStream_t st) {
   const int nbx = cdiv(a.N, G2_B), nby = cdiv(a.M, G2_B);
-  const bool stores_tile = std::is_same<Epi, Epi8G>::value || std::is_same<Epi, Epi8Store>::value || std::is_same<Epi, Epi8StatsP>::value;
-  const int grid = (nbx * nby < kNumCU || (stores_tile && opt(OPT_G8_ONE_TILE) != 0)) ? nbx * nby : kNumCU;
+  const int grid = nbx * nby < kNumCU ? nbx * nby : kNumCU;
   return launch<gemm8p_kernel<Epi, 0, SCHED>>(dim3((unsigned)grid), dim3(G2_THREADS), g8_lds_total, st, a, epi, nbx, nby);
 }
 // the inputs every gemm8p.h sim epilogue shares
@@ -407,7 +387,7 @@ struct DqPlan { int tile, splits, kchunk; bool big; };
 // the 256x256 LDS-DMA backward pair (gemm256.h): both contraction lengths multiples of 64, enough 256-row blocks to
 // matter, operands addressable with 32-bit element offsets
 bool big_bwd_ok(int B, int Nc, int d) {
-  if (opt(OPT_NO_BIG_BWD) || force_tile() >= 0 || big_min_wgs() <= 0 || unfused_bwd()) return false;
+  if (force_tile() >= 0 || big_min_wgs() <= 0) return false;
   if (B % 64 != 0 || Nc % 64 != 0) return false;
   if ((double)B * Nc >= 4.0e9 || (double)Nc * d >= 4.0e9) return false;
   const long units = (long)((Nc + 255) / 256 + (B + 255) / 256) * ((d + 255) / 256);
@@ -426,15 +406,15 @@ DqPlan dq_plan(int B, int Nc, int d) {
     // fit one round, 32 lose or change nothing (256 x 16384 86.0 -> 100.3, 256 x 8192 60.2 -> 60.9).
     int cap = 16;
     if (B < 512) {
-      const int forced = opt(OPT_DQ_CAP_FEW);
       const long at16 = (long)cdiv(Nc, 256) * cdiv(d, 256) + (long)cdiv(B, 256) * cdiv(d, 256) * 16;
-      cap = forced > 0 ? forced : (at16 > kNumCU ? 32 : 16);
+      cap = at16 > kNumCU ? 32 : 16;
     }
     if (splits > cap) splits = cap;
     // Long context axis (the dQ units run in a launch of their own: dprhot_inbatch_bwd's long_axis rule): ONE round of units on the
     // 256 CUs instead -- 1024 x 65536 x 768: 12 tiles x 21 slices = 252 units where 16 slices left a quarter of the chip idle;
-    // 2048 x 65536: 24 x 10 = 240 units in one round where 24 x 16 = 384 took two (round 6)
-    if (B >= 1024 && B <= 2048 && (long)Nc >= 32L * B && opt(OPT_DQ_ONE_ROUND) != 0) {
+    // 2048 x 65536: 24 x 10 = 240 units in one round where 24 x 16 = 384 took two (round 6; backward us against at most 16 slices:
+    // 1536 x 65536 x 768 419 -> 351, 2048 x 65536 497 -> 459, 1024 x 65536 294 -> 282: profiles/r06_dq_round_ab.txt)
+    if (B >= 1024 && B <= 2048 && (long)Nc >= 32L * B) {
       const int tiles = cdiv(B, 256) * cdiv(d, 256);
       int one = kNumCU / tiles;
       if (one > 32) one = 32;
@@ -468,7 +448,7 @@ DqPlan dq_plan(int B, int Nc, int d) {
 struct Pair128Plan { bool ok; int splits, kchunk; };
 Pair128Plan pair128_plan(int B, int Nc, int d) {
   Pair128Plan p{};
-  p.ok = opt(OPT_PAIR128) != 0 && opt(OPT_G128_DMA) != 0 && use_tr() && force_tile() < 0 && !unfused_bwd() && Nc % 8 == 0 &&
+  p.ok = opt(OPT_PAIR128) != 0 && opt(OPT_G128_DMA) != 0 && use_tr() && force_tile() < 0 && Nc % 8 == 0 &&
          d % 8 == 0 && B >= 64 && d >= 8 && (double)B * Nc < 4.0e9 && (double)Nc * d < 4.0e9;
   // K slices of a dQ tile.  The dQ units lead the grid and the (shorter) dC tiles fill in behind them, so the launch is as long as the
   // larger of one dQ unit and the chip's share of all K steps; every slice costs a slab of B x d fp32 written and read again.  Two
@@ -480,7 +460,6 @@ Pair128Plan pair128_plan(int B, int Nc, int d) {
   int s = (int)((double)Nc / (128.0 * (avg < 1.0 ? 1.0 : avg)) + 0.999);
   if (s < Nc / (4 * B)) s = Nc / (4 * B);
   if (s > 16) s = 16;
-  if (opt(OPT_PAIR128_CAP) > 0) s = opt(OPT_PAIR128_CAP);
   if (s > Nc / 256) s = Nc / 256;
   if (s < 1) s = 1;
   p.kchunk = cdiv(cdiv(Nc, 64), s) * 64;
@@ -527,17 +506,15 @@ SkPlan sk_plan(int B, int Nc, int d) {
   const int min_nc = B > 64 ? 256 : 512;  // (128 x 264: 17.8 vs 21.1 us; 96 x 392: 17.5 vs 21.2; 64 x 392: 17.0 vs 16.8)
   const bool fused_small = (B <= SS_ROWS && Nc <= 1024) || (B <= SS_MAXB && Nc <= 256);  // shapes the fused small step keeps (small_step_ok)
   SkPlan p{};
-  p.ok = !off && force_tile() < 0 && !unfused_bwd() && B <= SK_MAXB && B % 32 == 0 && d % 128 == 0 && d >= 128 && d <= 1024 && Nc >= min_nc &&
+  p.ok = !off && force_tile() < 0 && B <= SK_MAXB && B % 32 == 0 && d % 128 == 0 && d >= 128 && d <= 1024 && Nc >= min_nc &&
          Nc <= 16384 && (no_small || !fused_small);
   p.nt = cdiv(Nc, SK_COLS);
   {
     // sim unit width: 128 columns x 4 ring slots, or 64 columns x 8 slots (twice the units, two thirds of a unit's K range in flight).
     // The narrow unit pays when the wide ones would leave most of the chip idle (B = 32 x Nc = 2112, cfg2 gathered over 8 ranks: 17
     // wide units, step 18.8 -> 17.6 us); with every CU busy it loses (cfg3 per rank, 260 wide units: sim 12.4 vs 11.0 us, and the G
-    // launch then folds twice the tile statistics).  DPRHOT_SK_COLS=64 / 128 forces one.
-    const int forced = opt(OPT_SK_COLS);
-    const bool few = cdiv(B, SK_ROWS) * cdiv(Nc, SK_COLS) < kNumCU / 2;
-    const bool narrow = forced == 64 || (forced != 128 && few);
+    // launch then folds twice the tile statistics).
+    const bool narrow = cdiv(B, SK_ROWS) * cdiv(Nc, SK_COLS) < kNumCU / 2;
     p.scols = (narrow && cdiv(Nc, SK_SCOLS) <= 8 * SK_MAXG) ? SK_SCOLS : SK_COLS;
   }
   p.nts = cdiv(Nc, p.scols);  // statistics tiles = sim units per row block
@@ -547,7 +524,6 @@ SkPlan sk_plan(int B, int Nc, int d) {
   int ns = kNumCU / 2 / ndt;  // dQ units: (slice of contexts) x (64 columns of d); ~half a unit per CU measured best: the
   if (nk <= 8) ns = 1;  // up to 512 contexts one slice is short enough, and it needs no partial sums and no reduction launch (128 x 264: 17.8 -> 15.7 us;
                         // at 520 contexts it is a tie, beyond that the unsplit units are the launch's long pole)
-  if (opt(OPT_SK_DQ_SLICES) > 0) ns = opt(OPT_SK_DQ_SLICES);
   if (ns < 1) ns = 1;         // units run next to the dC units, and fewer slices mean fewer partial sums to write and re-read
   if (ns > 64) ns = 64;   // bounds the fp32 partial traffic
   p.ksteps = cdiv(nk, ns);
@@ -635,13 +611,12 @@ WsLayout ws_layout(int B, int Nc, int d, const FwdPlan& fp, const SkPlan& sk) {
 // Forward plan, a pure function of the shape (both forward launches derive it independently).
 //  short rows (the BASELINE training shapes): sim split over K into `splits` slabs, softmax with the row in registers
 //  long rows: sim with per-tile statistics, then the streaming gfinal kernel
-bool no_short() { return opt(OPT_NO_SHORT) != 0; }
 FwdPlan fwd_plan(int B, int Nc, int d) {
   FwdPlan p{};
   // wide: vocabulary-wide vectors (CITADEL router, d = 30522): the contraction is long and the logit matrix small -- the
   // K range is what has to be spread over the chip (B = 128, Nc = 1024 are only 32 tiles of 64 x 64)
   const bool wide = d >= 4096 && Nc <= 4096 && B <= 256;
-  p.short_rows = Nc <= 4096 && (B <= 64 || wide) && !no_short() && force_tile() < 0;
+  p.short_rows = Nc <= 4096 && (B <= 64 || wide) && force_tile() < 0;
   if (!p.short_rows) {
     p.tile = (force_tile() < 0 && big_ok(B, Nc, d)) ? kBigTile : pick_tile(B, Nc, d, 1, 2 * kNumCU);
     p.splits = 1;
@@ -691,7 +666,7 @@ bool wide_sim_ok(int B, int Nc, int d, const FwdPlan& fp) {
 // backward of the same shape class on the units of skinny.h (dprhot_inbatch_bwd): rows in blocks of 32 up to 128, vectors in whole
 // 64-column dQ tiles, contexts within one dQ slice (<= 24 ring steps of 64), 32-bit element offsets
 bool wide_bwd_ok(int B, int Nc, int d) {
-  return !opt(OPT_NO_WIDE_BWD) && !opt(OPT_NO_SKINNY) && force_tile() < 0 && !unfused_bwd() && d >= 4096 && d % 64 == 0 && B <= SK_MAXB &&
+  return !opt(OPT_NO_WIDE_BWD) && !opt(OPT_NO_SKINNY) && force_tile() < 0 && d >= 4096 && d % 64 == 0 && B <= SK_MAXB &&
          B % 32 == 0 && Nc % 8 == 0 && Nc >= 64 && Nc <= 1536 && (double)Nc * d < 4.0e9;
 }
 
@@ -730,8 +705,7 @@ bool small_step_ok(int B, int Nc, int d, const FwdPlan& fp) {
   // two row blocks (32 < B <= 64) up to 256 columns only -- measured (scratch/rb_probe.py, two launches against three): 64 x 256 x 768
   // 13.3 against 16.2 us, 64 x 128 x 1024 13.5 / 14.0, but 64 x 512 18.6 / 17.5 and 64 x 768 24.0 / 22.8: every workgroup repeats
   // BOTH blocks' softmax, and beyond 256 columns that second helping costs more than the launch it saves
-  return !opt(OPT_NO_SMALL_STEP) && B <= SS_MAXB && Nc <= (B <= SS_ROWS ? SS_MAXNC : 256) && d % 16 == 0 && fp.short_rows && fp.splits <= 4 &&
-         !unfused_bwd();
+  return !opt(OPT_NO_SMALL_STEP) && B <= SS_MAXB && Nc <= (B <= SS_ROWS ? SS_MAXNC : 256) && d % 16 == 0 && fp.short_rows && fp.splits <= 4;
 }
 
 // The plan of one shape, derived once per call: what dprhot_inbatch_step_f32 runs there; every entry point of the family, the host queries
@@ -828,16 +802,18 @@ int launch_dq(DqPlan p, const dprhot_bf16* G, const dprhot_bf16* C, int B, int N
 template <int NCH, int COLS, int SLOTS>
 int launch_sk_sim_c(const SkSimArgs& a, int grid, hipStream_t st) {
   const size_t lds = sk_sim_lds();
-  if constexpr (COLS == SK_COLS) {
-    if (a.q != nullptr && opt(OPT_SK_SIM_PRIV) != 0 && grid <= kNumCU) {
-      // wave-private rings, one workgroup per CU (round 5): as many chunks in flight per wave as 160 KiB of LDS hold next to the q block
+  if (a.q == nullptr) return launch<sk_sim_kernel<NCH, false, COLS, SLOTS>>(dim3((unsigned)grid), dim3(SK_THREADS), lds, st, a);
+  if constexpr (COLS == SK_COLS) {  // fp32 q at 128-column units: eight waves per workgroup
+    if (grid <= kNumCU) {
+      // wave-private rings and no barrier in the K loop, one workgroup per CU (round 5): as many chunks in flight per wave as 160 KiB of
+      // LDS hold next to the q block
       constexpr int PS = NCH <= 12 ? 6 : (NCH <= 14 ? 5 : 4);
       return launch<sk_simp_kernel<NCH, PS>>(dim3((unsigned)grid), dim3(512), sk_simp_lds(NCH, PS), st, a);
     }
-    if (a.q != nullptr && opt(OPT_SK_SIM_W8) != 0) return launch<sk_sim_kernel<NCH, true, COLS, SLOTS, 8>>(dim3((unsigned)grid), dim3(512), lds, st, a);
+    return launch<sk_sim_kernel<NCH, true, COLS, SLOTS, 8>>(dim3((unsigned)grid), dim3(512), lds, st, a);
+  } else {
+    return launch<sk_sim_kernel<NCH, true, COLS, SLOTS>>(dim3((unsigned)grid), dim3(SK_THREADS), lds, st, a);
   }
-  if (a.q != nullptr) return launch<sk_sim_kernel<NCH, true, COLS, SLOTS>>(dim3((unsigned)grid), dim3(SK_THREADS), lds, st, a);
-  return launch<sk_sim_kernel<NCH, false, COLS, SLOTS>>(dim3((unsigned)grid), dim3(SK_THREADS), lds, st, a);
 }
 template <int NCH>
 int launch_sk_sim(const SkSimArgs& a, int grid, int scols, hipStream_t st) {
@@ -874,11 +850,11 @@ int sk_step(const StepCtx& cx, const float* q, const dprhot_bf16* Cb, dprhot_bf1
   const SkFused fz = sk_fused_plan(sk, nts, nk_f, B, Nc, d);
   const bool fused = G == nullptr && S_out == nullptr && fz.ok;
   if (G == nullptr && !fused) return fail(DPRHOT_E_INVALID, "few-rows step: G == NULL needs the fused-dScores plan (dprhot_step_wants_g)");
-  // the finishing role inside the backward launch (sk_fin_unit): two-kinds form only; a dbg switch that silences units would strand it
-  const bool tail = fused && !fz.pair && opt(OPT_SK_TAIL) != 0 && (opt(OPT_SK_DBG) & 7) == 0 && fz.nslices <= 62 && d <= 1024;
+  // the finishing role inside the backward launch (sk_fin_unit): two-kinds form only
+  const bool tail = fused && !fz.pair && opt(OPT_SK_TAIL) != 0 && fz.nslices <= 62 && d <= 1024;
   unsigned* const tail_cnt = reinterpret_cast<unsigned*>(ws + wl.header + 128);
   // round 6: no finishing launch at all -- the dQ units add their tiles into dQ, zero-filled by the sim launch (two-kinds form, dQ wanted)
-  const bool dq_atomic = fused && !fz.pair && !tail && opt(OPT_SK_DQ_ATOMIC) != 0 && opt(OPT_SK_W8) != 0 && dQ != nullptr && (opt(OPT_SK_DBG) & 15) == 0;
+  const bool dq_atomic = fused && !fz.pair && !tail && opt(OPT_SK_DQ_ATOMIC) != 0 && opt(OPT_SK_W8) != 0 && dQ != nullptr;
   if (fused) {
     a.S = nullptr;
     a.P = reinterpret_cast<uint16_t*>(ws + wl.logits);
@@ -908,7 +884,7 @@ int sk_step(const StepCtx& cx, const float* q, const dprhot_bf16* Cb, dprhot_bf1
     const int ndq = fz.nslices * (d / SK_QN), ndq_pad = (ndq + 7) & ~7, ndc = nts * (d / SK_DN);
     SkBwdFArgs b{a.P, Qb, Cb, B, Nc, d, tile_lse, gold, y, y_offset, nts, tpr, pk.rows_c, pk.n_ctx, grad_scale, h_scale, d_scale,
                  dC_part, cx.dc_bf16 ? 1 : 0, pk.stamp_src != nullptr ? pk.rows_c : 0, pk.n_ctx, loss_sum, cx.loss_scale,
-                 row_loss, row_lse, fz.ksteps, fz.nslices, part, dQ, ndq_pad, opt(OPT_NT_STORES) ? 1 : 0, opt(OPT_SK_DBG)};
+                 row_loss, row_lse, fz.ksteps, fz.nslices, part, dQ, ndq_pad, /*nt_store=*/1, /*dbg=*/0};
     b.reg_scale = opt(OPT_SK_DC_REGSCALE) != 0 ? 1 : 0;
     b.dq_atomic = dq_atomic ? 1 : 0;
     const size_t lds = sk_bwdf_lds();
@@ -934,10 +910,6 @@ int sk_step(const StepCtx& cx, const float* q, const dprhot_bf16* Cb, dprhot_bf1
       else rc = w8 ? launch<sk_bwdf_kernel<16, 8>>(grid, block, lds, st, b) : launch<sk_bwdf_kernel<16, 4>>(grid, block, lds, st, b);
     }
     if (rc) return rc;
-    if (!tail && (opt(OPT_SK_DBG) & 8)) {
-      // TIMING EXPERIMENT ONLY (sk_dbg & 8): the plain slab sum in the finishing launch's place (wrong dQ) -- which launch carries the gaps?
-      return launch_sk_dq_reduce(part, fz.nslices, B, d, h_scale, d_scale, dQ, st);
-    }
     if (!tail && !dq_atomic) {
       // one workgroup per row where the row fits 256 threads (d <= 1024): the row's statistics are derived once, not once per part
       const int fthreads = d / 4 >= 256 ? 256 : cdiv(d / 4, 64) * 64;
@@ -960,7 +932,7 @@ int sk_step(const StepCtx& cx, const float* q, const dprhot_bf16* Cb, dprhot_bf1
     float* part = cx.dq_part != nullptr ? cx.dq_part : reinterpret_cast<float*>(ws + wl.dq_part);
     const int ndq = sk.nslices * (d / SK_QN), ndq_pad = (ndq + 7) & ~7, ndc = sk.nt * (d / SK_DN);
     SkBwdArgs b{G, Qb, Cb, B, Nc, d, h_scale, d_scale, dC_part, rl, loss_sum, cx.loss_scale, cx.dc_bf16 ? 1 : 0,
-                pk.stamp_src != nullptr ? pk.rows_c : 0, pk.n_ctx, sk.ksteps, sk.nslices, part, dQ, ndq_pad, opt(OPT_NT_STORES) ? 1 : 0};
+                pk.stamp_src != nullptr ? pk.rows_c : 0, pk.n_ctx, sk.ksteps, sk.nslices, part, dQ, ndq_pad, /*nt_store=*/1};
     if ((rc = launch_sk_bwd(b, ndq_pad + ndc, st))) return rc;
     // (else the caller's finishing launch forms dQ from the slabs: dprhot_rescale_grads; one slice: the dQ units stored the scaled sum themselves)
     if (cx.dq_part == nullptr && sk.nslices > 1) return launch_sk_dq_reduce(part, sk.nslices, B, d, h_scale, d_scale, dQ, st);
@@ -973,9 +945,9 @@ int sk_step(const StepCtx& cx, const float* q, const dprhot_bf16* Cb, dprhot_bf1
 
 int sim_fwd_body(const PackedSpec& pk, const dprhot_bf16* Q, int B, const dprhot_bf16* C, int Nc, int d, const uint8_t* colmask, float inv_T,
                  float* S, hipStream_t st) {
-  if (g8_ok(B, Nc, d) && !opt(OPT_NO_8P_STORE)) {
+  if (g8_ok(B, Nc, d)) {
     // large score matrices (validation with the logits wanted, the head chunk of a retrieval): the phase-interleaved kernel with
-    // the store epilogue that writes whole rows (Epi8Store); the round-1 256 x 256 kernel stays behind the option
+    // the store epilogue that writes whole rows (Epi8Store)
     Epi8Store epi;
     static_cast<Epi8Base&>(epi) = g8_base(pk, Q, B, Nc, nullptr, 0, colmask, inv_T, nullptr);
     epi.S = S;
@@ -1053,7 +1025,7 @@ int sim_stats_f32_body(const PackedSpec& pk, const float* q, const float* c, dpr
     if (c != nullptr && wide_sim_ok(B, Nc, d, fp) && pk.base == nullptr) {
       // vocabulary-wide fp32 operands: LDS-DMA ring of fp32 tiles, bf16 rounding on the fragment read (wide.h)
       WideSimArgs wa{q, c, Qb, Cb, B, Nc, d, colmask, inv_T, reinterpret_cast<float*>(ws + wl.logits), (size_t)B * Nc, fp.kchunk,
-                     reinterpret_cast<unsigned long long*>(ws + wl.header), 2, opt(OPT_WIDE_NOCOPY), cdiv(Nc, WD_B), cdiv(B, WD_B)};
+                     reinterpret_cast<unsigned long long*>(ws + wl.header), 2, /*no_copy=*/0, cdiv(Nc, WD_B), cdiv(B, WD_B)};
       return launch<wide_sim_kernel>(dim3((unsigned)(wa.nbx * wa.nby * fp.splits)), dim3(WD_THREADS), wd_lds_bytes, st, wa);
     }
     EpiSim epi{reinterpret_cast<float*>(ws + wl.logits), colmask, B, Nc, inv_T, nullptr, nullptr, nullptr, 0, nullptr,
@@ -1192,7 +1164,7 @@ BwdPlan bwd_plan(int B, int Nc, int d, const SkPlan& sk, bool both, bool stamp) 
   const bool long_axis_small = ((B < 512 && Nc >= 56 * 1024) || (B >= 512 && B < 1024 && (long)Nc >= 32L * B)) && !sk.ok &&
                                !wide_bwd_ok(B, Nc, d) && big_bwd_ok(B, Nc, d) && !pair128_use(B, Nc, d);
   b.kind = b.dq.big ? BWD_PAIR256 : BWD_PAIR;
-  if (!both || unfused_bwd() || force_tile() >= 0 || long_axis_small) b.kind = BWD_APART;  // dC and dQ in launches of their own
+  if (!both || force_tile() >= 0 || long_axis_small) b.kind = BWD_APART;  // dC and dQ in launches of their own
   else if (!stamp && sk.ok) b.kind = BWD_FEW_ROWS, b.slabs = sk.nslices;
   else if (!stamp && wide_bwd_ok(B, Nc, d)) b.kind = BWD_WIDE, b.slabs = 1;
   else if (pair128_use(B, Nc, d)) b.kind = BWD_PAIR128, b.pp = pair128_plan(B, Nc, d), b.slabs = b.pp.splits;
@@ -1216,7 +1188,7 @@ int inbatch_bwd_body(const StepCtx& cx, const BwdPlan& bp, const dprhot_bf16* G,
     float* part = sk.nslices > 1 ? reinterpret_cast<float*>(ws + wl.dq_part) : nullptr;
     const int ndq = sk.nslices * (d / SK_QN), ndq_pad = (ndq + 7) & ~7, ndc = sk.nt * (d / SK_DN);
     SkBwdArgs b{G, Q, C, B, Nc, d, h_scale, d_scale, dC_part, nullptr, nullptr, 1.0f, 0, 0, 0, sk.ksteps, sk.nslices, part, dQ, ndq_pad,
-                opt(OPT_NT_STORES) ? 1 : 0};
+                /*nt_store=*/1};
     if (int rc = launch_sk_bwd(b, ndq_pad + ndc, st)) return rc;
     if (sk.nslices > 1) return launch_sk_dq_reduce(part, sk.nslices, B, d, h_scale, d_scale, dQ, st);
     return DPRHOT_OK;
@@ -1226,11 +1198,11 @@ int inbatch_bwd_body(const StepCtx& cx, const BwdPlan& bp, const dprhot_bf16* G,
     // of a large store -- the unit shapes of skinny.h (whole operand footprint in flight by LDS-DMA, stores through LDS in whole
     // lines), dC tiles and dQ tiles side by side in one launch; the contexts fit one dQ slice, so no partial sums and no reduction.
     // The 141 MB of fp32 gradients leave with non-temporal stores: nobody re-reads them inside the step, and written normally they push
-    // the step's operands out of the 256 MB Infinity Cache (measured, scratch/router_ab.py: step 116 -> 99.5 us; the same policy on the
+    // the step's operands out of the 256 MB Infinity Cache (measured: step 116 -> 99.5 us; the same policy on the
     // 8192^2 launches -- stored logits, 256 x 256 backward -- LOST 5-10 % and is not used there: profiles/r03_nt_stores_ab.txt).
     const int ksteps = cdiv(Nc, 64);
     const int ndq = d / SK_QN, ndq_pad = (ndq + 7) & ~7, ndc = cdiv(Nc, SK_COLS) * cdiv(d, SK_DN);
-    SkBwdArgs b{G, Q, C, B, Nc, d, h_scale, d_scale, dC_part, nullptr, nullptr, 1.0f, 0, 0, 0, ksteps, 1, nullptr, dQ, ndq_pad, opt(OPT_NT_STORES) ? 1 : 0};
+    SkBwdArgs b{G, Q, C, B, Nc, d, h_scale, d_scale, dC_part, nullptr, nullptr, 1.0f, 0, 0, 0, ksteps, 1, nullptr, dQ, ndq_pad, /*nt_store=*/1};
     return launch_sk_bwd(b, ndq_pad + ndc, st);
   }
   if (bp.kind == BWD_PAIR128) {
@@ -1262,20 +1234,23 @@ int inbatch_bwd_body(const StepCtx& cx, const BwdPlan& bp, const dprhot_bf16* G,
     // of 8 ranks): the dC tiles of the pair launch are only K = B deep -- 8 to 32 K steps between a pipeline fill and a 256 KiB store
     // -- next to dQ units several times as long (the K slices of dQ stop at 16), and the launch loses to dC on the 128 x 128 engine in a
     // launch of its own (dc_body) followed by this launch with its dQ units only.  Measured, pair / dC apart, us (d = 768,
-    // scratch/bwd_hybrid_ab.py, profiles/r05_bwd_long_axis.txt): 1024 x 32768 181 / 154, 1024 x 49152 292 / 236, 1024 x 65536 482 / 299,
+    // profiles/r05_bwd_long_axis.txt): 1024 x 32768 181 / 154, 1024 x 49152 292 / 236, 1024 x 65536 482 / 299,
     // 512 x 16384 73 / 70, 512 x 32768 117 / 112, 512 x 65536 356 / 202, 2048 x 65536 611 / 555, 1024 x 32768 x 1024 217 / 197; the
     // pair stays where it wins: 1024 x 8192 43 / 71, 1024 x 16384 82 / 96, 2048 x 16384 122 / 146, 2048 x 32768 228 / 289, 512 x 8192 33 / 50.
     const bool long_axis = B >= 512 && B <= 2048 && (long)Nc >= 32L * B;
-    const bool no8 = opt(OPT_NO_8PB) != 0;
     // (round 6: B and Nc multiples of 64 suffice -- a unit with an odd number of K steps skips the MFMAs of its last half pair; the packed
     //  multi-rank layout's column counts are multiples of 64, rarely of 128)
-    const bool ok8 = !no8 && B % 64 == 0 && Nc % 64 == 0 && p.kchunk % 128 == 0 && (double)B * Nc < 2.0e9 && (double)Nc * d < 2.0e9;
+    const bool ok8 = B % 64 == 0 && Nc % 64 == 0 && p.kchunk % 128 == 0 && (double)B * Nc < 2.0e9 && (double)Nc * d < 2.0e9;
     a1.kchunk = B;  // dC: one K range (B % 64 == 0)
     // the same epilogues for the phase-interleaved kernel (gemm8pb.h)
     const Epi8Scale s1{e1.out, e1.M, e1.N, e1.h_scale, e1.d_scale, e1.stamp_src, e1.stamp_period, e1.stamp_row};
     const Epi8Scale s2{e2.out, e2.M, e2.N, e2.h_scale, e2.d_scale, e2.stamp_src, e2.stamp_period, e2.stamp_row};
-    if (long_axis && ok8 && (opt(OPT_DC_ALONE_8P) == 2 || (opt(OPT_DC_ALONE_8P) == 1 && ((size_t)Nc * 2) % ((size_t)128 << 10) == 0))) {
-      // (A/B, round 6) the dC tiles alone on the phase-interleaved kernel: no dQ units four times as long next to them
+    if (long_axis && ok8 && ((size_t)Nc * 2) % ((size_t)128 << 10) == 0) {
+      // (round 6) the dC tiles ALONE on the phase-interleaved kernel, in a launch of their own in front of the launch with the dQ units: no
+      // dQ units four times as long next to them.  Only where the row pitch of G is a multiple of 128 KiB (Nc = 65536): the 128-wide tiles'
+      // 256-byte pieces then alias in the memory system -- 180 us where 126 are expected -- and the 512-byte pieces of the 256-wide tile do
+      // not: backward 325 -> 275 us at 1024 x 65536, 557 -> 470 at 2048 x 65536; it LOSES at 32768 / 49152 columns
+      // (profiles/r06_dc_alone_ab.txt)
       const int nbx1a = cdiv(d, G2_B), nby1a = cdiv(Nc, G2_B);
       if (int rc = launch<gemm8p_bwd_kernel<Epi8Scale>>(dim3((unsigned)(nbx1a * nby1a)), dim3(G2_THREADS), g8_lds_total, st, a1, s1, nbx1a, nby1a, a2, s2,
                                                         cdiv(d, G2_B), 0, p.splits))
@@ -1830,7 +1805,6 @@ int dprhot_search(const dprhot_bf16* Q, int nq, const dprhot_bf16* C, int64_t n_
   float* S = static_cast<float*>(workspace);
   int* cand_j = reinterpret_cast<int*>(static_cast<char*>(workspace) + (size_t)nq * chunk * 4);
   int* cnt = reinterpret_cast<int*>(static_cast<char*>(workspace) + (size_t)nq * chunk * 8);
-  const bool unfused = opt(OPT_SEARCH_UNFUSED) != 0;
   HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)nq * sizeof(int), st));
   // An empty state is started from a SHORT head (its scores are materialised and selected from: cost proportional to the head), the
   // filtered chunks behind it may be as long as the workspace allows: every chunk costs one merge launch, and a merge rewrites the
@@ -1844,11 +1818,10 @@ int dprhot_search(const dprhot_bf16* Q, int nq, const dprhot_bf16* C, int64_t n_
     if (step > chunk) step = chunk;
     const int cols = (int)((n_ctx - j0 < step) ? (n_ctx - j0) : step);
     const dprhot_bf16* Cj = C + (size_t)j0 * d;
-    if ((first && j0 == 0) || unfused) {
+    if (first && j0 == 0) {
       // nothing to filter against yet: materialise this chunk's scores and select from them
       if (int rc = dprhot_sim_fwd(Q, nq, Cj, cols, d, nullptr, 1.0f, S, stream)) return rc;
-      if (int rc = dprhot_topk_update(S, nq, cols, cols, id_offset + j0, k, values, indices, (first && j0 == 0) ? 1 : 0, stream))
-        return rc;
+      if (int rc = dprhot_topk_update(S, nq, cols, cols, id_offset + j0, k, values, indices, 1, stream)) return rc;
       continue;
     }
     // scores that cannot enter the top-k never leave the GEMM tile

@@ -735,7 +735,7 @@ struct SkBwdArgs {
   float* part;            // [nslices][B][d] dQ partial sums (nslices > 1)
   float* dQ;              // [B][d]: nslices == 1 -- the one slice IS the sum, scaled and stored here
   int ndq_pad;
-  int nt_store = 0;       // 1: dC (and an unsplit dQ) leave with non-temporal stores: nobody re-reads them inside the step, and written normally
+  int nt_store = 0;       // (every host path passes 1; the option nt_stores that set it is retired)  1: dC (and an unsplit dQ) leave with non-temporal stores: nobody re-reads them inside the step, and written normally
                           // they displace the operands in L2 / the Infinity Cache (cfg3 per rank 31.1 -> 29.9 us, router width 116 -> 99.5)            // dQ units rounded up to a multiple of 8 (keeps workgroup % 8 == XCD for the dC units)
 };
 
@@ -1095,8 +1095,8 @@ struct SkBwdFArgs {
   float* part;            // [nslices][B][d] slice-normalised slabs (finished by sk_dq_finish_kernel)
   float* dQ;              // (unused: the finishing launch writes dQ)
   int ndq_pad;
-  int nt_store;
-  int dbg = 0;            // TIMING EXPERIMENTS ONLY (option sk_dbg): 1 dC units leave at once, 2 dQ units leave at once, 
+  int nt_store;           // (every host path passes 1: SkBwdArgs::nt_store)
+  int dbg = 0;            // no host path sets it any more (the option sk_dbg is retired).  Timing experiments only: 1 dC units leave at once, 2 dQ units leave at once
   // Round 5: the finishing role INSIDE this launch (sk_fin_unit): the dQ units publish their slabs with write-through stores and count
   // themselves in; the last workgroups of the grid wait for that count and fold the slabs.  nullptr: sk_dq_finish_kernel does it.
   unsigned* tail_cnt = nullptr;  // zeroed by the sim launch (SkSimArgs::zero_me)

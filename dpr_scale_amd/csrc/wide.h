@@ -39,7 +39,7 @@ struct WideSimArgs {
   int kchunk;        // k values per split (a multiple of 32)
   unsigned long long* zero_words;  // cleared by workgroup (0,0,0) for the softmax launch's ticket
   int n_zero;
-  int no_copy;       // timing experiment only (option wide_nocopy): skip the bf16 copy-out
+  int no_copy;       // no host path sets it any more: the host passes 0 (the option wide_nocopy is retired).  Timing experiment only: skip the bf16 copy-out
   int nbx, nby;      // column / row tiles (the grid is 1-D: nbx * nby * splits workgroups)
 };
 

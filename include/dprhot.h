@@ -47,15 +47,34 @@ typedef uint16_t dprhot_bf16;
 int dprhot_version(void);
 const char* dprhot_last_error(void);
 
-/* Process-wide test / A-B switches of the shape plans (all default to "plan decides"; production never calls this).  Names:
- *   tile (-1 | 0..5)   no_tr   unfused_bwd   big_min (256)   no_nl   no_big_bwd   no_skinny   no_small_step   no_short
- *   sk_cols (0 | 64 | 128)   search_unfused   no_8pb   no_wide   no_8p_store   no_wide_bwd   nt_stores (1)   sk_dq_slices (0)
- *   sk_fused (1: the few-rows step without its dScores launch from 2^19 scores up | 2: wherever it exists | 0: never)
- *   sk_w8 (1) / sk_sim_w8 (1): eight waves per workgroup in the few-rows backward / sim launch   sk_pair (0): one kind of backward unit
- *   sk_dbg (0; timing experiments only)
- *   small_sim (1: the batch-32 step's sim launch on csrc/sim_small.h | 0: on the GEMM engine | 2..4: its other forms; same bits from all)
- *   small_step_roles (3: the batch-32 step's softmax + backward launch split by role, outputs from a workgroup of their own |
- *                     2: outputs from the dC workgroup of tile 0 | 1: 2 with 16-column dQ tiles | 0: unsplit; same bits from all)
+/* Process-wide test / A-B switches of the shape plans (production never calls this).  Every name with its default, one per line
+ * (tests/test_abi.py holds this list against the library's own table):
+ *   tile (-1)              0..5 pins the tile of the single-GEMM launches, -1: the plan decides
+ *   no_tr (0)              1: plain 16-bit gathers in place of the LDS transpose read (cross-check)
+ *   big_min (256)          fewest 256 x 256 tiles for the large-shape kernels (0: never; tests lower it)
+ *   nl_min (128)           fewest 256 x 256 tiles from which the forward never stores the logits
+ *   no_skinny (0)          1: no few-rows x many-contexts plan
+ *   no_small_step (0)      1: no fused softmax + backward kernel of the latency-bound shapes
+ *   no_wide (0)            1: vocabulary-wide fp32 operands stay on the register-staged sim kernel
+ *   no_wide_bwd (0)        1: the backward of vocabulary-wide vectors stays on the generic pair kernel
+ *   sk_fused (1)           the few-rows step without its dScores launch: 1 from 2^19 scores up | 2 wherever it exists | 0 never
+ *   sk_w8 (1)              eight waves per workgroup in the fused few-rows backward, 0: four
+ *   sk_pair (0)            1: one kind of unit in the fused few-rows backward
+ *   sk_tail (0)            1 | 2: the dQ slabs are folded by the last workgroups of the few-rows backward launch itself
+ *   sk_dc_regscale (0)     1: the dC units of the fused few-rows backward scale their Q fragments in registers
+ *   sk_dq_atomic (0)       1: the dQ units of the fused few-rows backward add into dQ (reproducible to rounding, not to the bit)
+ *   nl_p16 (1)             no-logits forward with the dScores wanted in one GEMM pass, 0: two passes
+ *   g128_dma (1)           the 128 x 128 tile staged by LDS-DMA, 0: never
+ *   loss_with_dq (1)       the one-call step sums the row losses in the launch that combines the dQ slabs, 0: in a launch of its own
+ *   nl128 (1)              one-pass training forward on the 128 x 128 tile where the 256-wide tiles would leave the chip idle, 0: off
+ *   pair128 (1)            backward pair on the 128 x 128 tile: 1 where its rule picks it | 2 wherever it qualifies | 0 never
+ *   p16_staged (1)         fp16 numerators of the 256 x 256 one-pass forward leave through LDS: 1 by its rule | 2 always | 0 never
+ *   small_sim (1)          the batch-32 step's sim launch on csrc/sim_small.h | 0: on the GEMM engine | 2..4: its other forms
+ *   small_step_roles (3)   the batch-32 step's softmax + backward launch split by role, outputs from workgroups of their own |
+ *                          2: outputs from the dC workgroup of tile 0 | 1: 2 with 16-column dQ tiles | 0: unsplit
+ *   small_sim_copy (1)     the batch-32 sim launch writes its bf16 copies on waves of their own, 0: on the compute waves
+ * An option changes which kernels run -- the summation order and where a value is rounded with them -- never what is computed;
+ * sk_dq_atomic = 1 alone gives up run-to-run bit-reproducibility.
  * Setting one changes the plans of every later call on every thread (workspace sizes included: query them after setting).
  * DPRHOT_E_INVALID for an unknown name. */
 int dprhot_set_option(const char* name, int value);

@@ -13,11 +13,8 @@ __device__ unsigned long long g_dprhot_tmb[4 * 4096 * 8];
 int main(int argc, char** argv) {
   const int B = argc > 1 ? atoi(argv[1]) : 128, K = argc > 2 ? atoi(argv[2]) : 8, d = argc > 3 ? atoi(argv[3]) : 768, W = 8;
   const bool no_g = argc > 4 && atoi(argv[4]) != 0;  // 1: G == NULL -- the plan without the dScores launch (round 4)
-  if (argc > 5) dprhot_set_option("sk_dbg", atoi(argv[5]));        // 1: dC units leave at once, 2: dQ units leave at once
-  if (argc > 6) dprhot_set_option("sk_dq_slices", atoi(argv[6]));  // context slices of the dQ units
-  if (argc > 7) dprhot_set_option("sk_w8", atoi(argv[7]));         // 1: eight waves per workgroup in the fused backward launch
-  if (argc > 9) dprhot_set_option("sk_sim_w8", atoi(argv[9]));     // 0: four waves per workgroup in the sim launch
-  if (argc > 8) dprhot_set_option("sk_pair", atoi(argv[8]));       // 1: one kind of unit (sk_bwdp_kernel; its stamps print as "dc")
+  if (argc > 5) dprhot_set_option("sk_w8", atoi(argv[5]));    // 1: eight waves per workgroup in the fused backward launch
+  if (argc > 6) dprhot_set_option("sk_pair", atoi(argv[6]));  // 1: one kind of unit (sk_bwdp_kernel; its stamps print as "dc")
   const int n_ctx = B * K;
   int rows_c; dprhot_packed_rows(n_ctx, d, &rows_c);
   const int Nc = W * rows_c;

@@ -11,6 +11,12 @@ from conftest import ROOT
 HEADER = os.path.join(ROOT, "include", "dprhot.h")
 
 
+# options that no test, benchmark or tool ever set: retired, each the constant its default was
+RETIRED_OPTIONS = ("unfused_bwd", "no_nl", "no_big_bwd", "no_short", "sk_cols", "sk_dq_slices", "dq_cap_few", "pair128_slices", "search_unfused",
+                   "no_8pb", "no_8p_store", "g8_one_tile", "sk_sim_w8", "sk_sim_priv", "dc_alone_8p", "dq_one_round", "nl128_max_tiles",
+                   "nl128_min_tiles", "nt_stores", "sk_dbg", "wide_nocopy")
+
+
 def declared_symbols():
     src = open(HEADER).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
@@ -104,8 +110,12 @@ def test_argument_validation_is_host_side():
         assert lib.dprhot_workspace_bytes(*shape, ctypes.byref(big)) == 0
         assert big.value >= -(-(-(-shape[1] // 64)) // 13) * shape[0] * shape[2] * 4
     assert lib.dprhot_set_option(b"sk_fused", 1) == 0
-    for name, default in ((b"sk_w8", 1), (b"sk_sim_w8", 1), (b"sk_pair", 0), (b"sk_tail", 0), (b"sk_sim_priv", 1), (b"sk_fused", 1), (b"nt_stores", 1)):
+    for name, default in ((b"sk_w8", 1), (b"sk_pair", 0), (b"sk_tail", 0), (b"sk_fused", 1)):
         assert lib.dprhot_get_option(name, ctypes.byref(n)) == 0 and n.value == default, (name, n.value)
+    # the retired switches are unknown names to both calls (each is the constant its default was)
+    for name in RETIRED_OPTIONS:
+        for rc in (lib.dprhot_set_option(name.encode(), 1), lib.dprhot_get_option(name.encode(), ctypes.byref(n))):
+            assert rc == -1 and b"unknown option" in lib.dprhot_last_error(), (name, rc, lib.dprhot_last_error())
     # the few-rows plan's measured boundaries ("Mid-size steps"), seen through the slab count: split-K slabs where
     # the plan applies with more than 512 contexts, none where its dQ units are unsplit or another plan has the shape
     for shape, want_slabs in (((128, 1032, 768), True), ((64, 1088, 1024), True), ((32, 1056, 768), True), ((32, 2112, 768), True),
@@ -187,6 +197,23 @@ def test_missing_library_fails_loudly(tmp_path, monkeypatch):
         sys.modules.pop("dpr_scale_amd._lib", None)
         if saved is not None:
             sys.modules["dpr_scale_amd._lib"] = saved
+
+def test_option_names_agree_in_header_table_and_library():
+    """The comment above dprhot_set_option, the table kOptDefs and the names the library answers to are one set, with one default each."""
+    from dpr_scale_amd import _lib
+
+    comment = re.search(r"/\*((?:(?!\*/).)*)\*/\s*int dprhot_set_option", open(HEADER).read(), flags=re.S).group(1)
+    in_header = {m.group(1): int(m.group(2)) for m in re.finditer(r"^ \*   ([a-z][a-z0-9_]*) \((-?\d+)\)", comment, flags=re.M)}
+    src = open(os.path.join(ROOT, "dpr_scale_amd", "csrc", "dprhot.hip")).read()
+    table = src[src.index("kOptDefs[OPT_COUNT] = {"):src.index("constexpr bool opt_table_in_enum_order")]
+    in_table = {m.group(1): int(m.group(2)) for m in re.finditer(r'^\s*\{OPT_[A-Z0-9_]+, "([a-z0-9_]+)", (-?\d+),', table, flags=re.M)}
+    assert len(in_table) == 23 and not set(in_table) & set(RETIRED_OPTIONS)
+    n = ctypes.c_int(0)
+    asked = set(in_header) | set(in_table) | set(RETIRED_OPTIONS)
+    accepted = {name for name in asked if _lib.lib.dprhot_get_option(name.encode(), ctypes.byref(n)) == 0}
+    assert set(in_header) == set(in_table) == accepted, (sorted(set(in_header) ^ set(in_table)), sorted(set(in_table) ^ accepted))
+    assert in_header == in_table  # the defaults as well
+
 
 def test_plans_are_total_functions_of_the_shape():
     """Every entry point derives its plans (tiles, splits, workspace layout) from (B, Nc, d) on the host before anything is launched:

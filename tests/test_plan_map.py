@@ -21,8 +21,8 @@ LAUNCHED = {}  # shape -> kernel names seen
 # (the fused small step; the few-rows step's sim, dScores and backward units with and without the dScores launch; the wide-vector sim;
 # the register-staged sim, streaming softmax and backward pair; the one-pass forwards on the 256 x 256 and 128 x 128 tiles and their
 # row kernel; the backward pairs on the 128 x 128 LDS-DMA tile and the phase-interleaved 256 x 256 tile.  The 256 x 256 LDS-DMA pair,
-# gemm256_bwd_kernel, is not one of them: at default options dq_plan's shapes all qualify for the phase-interleaved kernel -- it runs
-# only under option no_8pb or past 2^31-byte operands.)
+# gemm256_bwd_kernel, is not one of them: the shapes of this table all qualify for the phase-interleaved kernel -- it runs only where a
+# shape fails a term of `ok8` in inbatch_bwd_body: B or Nc no multiple of 64, kchunk % 128 != 0, or operands past 2^31 bytes.)
 FAMILIES = ["step_small_kernel", "sk_sim_kernel", "sk_simp_kernel", "sk_g_kernel", "sk_bwd_kernel", "sk_bwdf_kernel", "wide_sim_kernel",
             "gemm_bf16_kernel", "gfinal_kernel", "gfinal_short_kernel", "gemm_pair_kernel", "gemm8p_kernel", "g8_lse_p2g_kernel",
             "gemm128d_kernel", "gemm128d_pair_kernel", "gemm8p_bwd_kernel"]
