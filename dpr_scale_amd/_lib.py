@@ -49,7 +49,8 @@ SIGNATURES = {
     "dprhot_search_workspace_bytes": (c_int, [c_int, c_int, POINTER(c_size_t)]),
     "dprhot_search": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int,
                               c_void_p, c_size_t, c_void_p]),
-    "dprhot_inbatch_fwd": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_float,
+    "dprhot_search_plan": (c_int, [c_int, c_int64, c_int, c_int, c_int, c_int, POINTER(c_int64), c_int, POINTER(c_int)]),
+    "dprhot_inbatch_fwd":(c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_float,
                                    c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                    c_void_p]),
     "dprhot_sim_stats": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_float, c_void_p,
@@ -191,6 +192,19 @@ def search_workspace_bytes(nq, chunk):
     out = c_size_t(0)
     check(lib.dprhot_search_workspace_bytes(int(nq), int(chunk), ctypes.byref(out)), "dprhot_search_workspace_bytes")
     return out.value
+
+
+def search_plan(nq, n_ctx, d, k, chunk, first):
+    """[(j0, cols, head, form)] of the launches dprhot_search makes for this shape under the current options (dprhot_search_plan: host
+    code only).  form: 0..5 register-staged tile, 6 the 256 x 256 kernel, 7 the phase-interleaved kernel, 8 tile 0 on LDS-DMA."""
+    n = c_int(0)
+    args = (int(nq), int(n_ctx), int(d), int(k), int(chunk), int(bool(first)))
+    rc = lib.dprhot_search_plan(*args, None, 0, ctypes.byref(n))
+    if rc != 0 and n.value == 0:
+        check(rc, "dprhot_search_plan")
+    steps = (c_int64 * (4 * n.value))()
+    check(lib.dprhot_search_plan(*args, steps, n.value, ctypes.byref(n)), "dprhot_search_plan")
+    return [(steps[4 * i], int(steps[4 * i + 1]), bool(steps[4 * i + 2]), int(steps[4 * i + 3])) for i in range(n.value)]
 
 
 def packed_rows(n_ctx: int, d: int) -> int:

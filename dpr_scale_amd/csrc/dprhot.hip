@@ -262,6 +262,15 @@ int pick_tile(int M, int N, int K, int splits_hint, int want) {
   return 2;
 }
 
+// The kernel of a bf16 score GEMM S[M,N] = Q x C^T (both operands k-major, no split-K) that stores or filters its tile: the storing
+// forward (sim_fwd_body) and the filtered chunks of dprhot_search make this one choice.
+struct SimGemm { bool g8; int tile, kchunk; };  // g8: the phase-interleaved kernel (gemm8p.h); else the tile id of launch_gemm and its K range
+SimGemm sim_gemm(int M, int N, int K) {
+  if (g8_ok(M, N, K)) return SimGemm{true, kBigTile, K};
+  const int tile = (force_tile() < 0 && big_ok(M, N, K)) ? kBigTile : pick_tile(M, N, K, 1, 2 * kNumCU);
+  return SimGemm{false, tile, cdiv(K, kTiles[tile].bk) * kTiles[tile].bk};
+}
+
 template <int BM, int BN, int BK, bool AK, bool BKM, bool TR, class Epi, bool AF = false, bool BF = false>
 int launch_one(const GemmArgs& a, const Epi& epi, int splits, hipStream_t st) {
   dim3 grid(cdiv(a.N, BN), cdiv(a.M, BM), splits);
@@ -296,6 +305,17 @@ Epi8Base g8_base(const PackedSpec& pk, const dprhot_bf16* Q, int B, int Nc, cons
   return b;
 }
 
+// whether a launch on tile 0 runs with LDS-DMA staging (gemm128d.h) instead of register staging: launch_gemm's rule, also read by the
+// plan query of the search (gemm_form)
+template <bool AK, bool BKM>
+bool g128d_takes(const GemmArgs& a) {
+  constexpr bool needs_tr = !(AK && BKM);
+  const bool tr = needs_tr ? use_tr() : false;
+  // (K: whole 64-deep steps -- or, with B mn-major, any K from 64 on (a multiple of 8 when A is k-major): the partial last step is read against zeros, g1_tile)
+  return opt(OPT_G128_DMA) != 0 && (tr || !needs_tr) && (a.K % 64 == 0 || (!BKM && a.K >= 64 && (!AK || a.K % 8 == 0))) && a.kchunk % 64 == 0 && a.M >= 8 && a.N >= 8 &&
+         (double)(AK ? a.M : a.K) * a.lda < 4.0e9 && (double)(BKM ? a.N : a.K) * a.ldb < 4.0e9;  // (32-bit element offsets inside one K range)
+}
+
 template <bool AK, bool BKM, class Epi>
 int launch_gemm(int tile, const GemmArgs& a, const Epi& epi, int splits, hipStream_t st) {
   if constexpr (AK && BKM) {
@@ -306,9 +326,7 @@ int launch_gemm(int tile, const GemmArgs& a, const Epi& epi, int splits, hipStre
   }
   constexpr bool needs_tr = !(AK && BKM);
   const bool tr = needs_tr ? use_tr() : false;
-  // (K: whole 64-deep steps -- or, with B mn-major, any K from 64 on (a multiple of 8 when A is k-major): the partial last step is read against zeros, g1_tile)
-  if (tile == 0 && opt(OPT_G128_DMA) != 0 && (tr || !needs_tr) && (a.K % 64 == 0 || (!BKM && a.K >= 64 && (!AK || a.K % 8 == 0))) && a.kchunk % 64 == 0 && a.M >= 8 && a.N >= 8 &&
-      (double)(AK ? a.M : a.K) * a.lda < 4.0e9 && (double)(BKM ? a.N : a.K) * a.ldb < 4.0e9) {  // (32-bit element offsets inside one K range)
+  if (tile == 0 && g128d_takes<AK, BKM>(a)) {
     // the same tile with LDS-DMA staging (gemm128d.h): same images, same fragments, same epilogues
     return launch<gemm128d_kernel<AK, BKM, Epi>>(dim3(cdiv(a.N, 128), cdiv(a.M, 128), splits), dim3(256), g1_lds_bytes, st, a, epi);
   }
@@ -945,7 +963,8 @@ int sk_step(const StepCtx& cx, const float* q, const dprhot_bf16* Cb, dprhot_bf1
 
 int sim_fwd_body(const PackedSpec& pk, const dprhot_bf16* Q, int B, const dprhot_bf16* C, int Nc, int d, const uint8_t* colmask, float inv_T,
                  float* S, hipStream_t st) {
-  if (g8_ok(B, Nc, d)) {
+  const SimGemm g = sim_gemm(B, Nc, d);
+  if (g.g8) {
     // large score matrices (validation with the logits wanted, the head chunk of a retrieval): the phase-interleaved kernel with
     // the store epilogue that writes whole rows (Epi8Store)
     Epi8Store epi;
@@ -954,8 +973,8 @@ int sim_fwd_body(const PackedSpec& pk, const dprhot_bf16* Q, int B, const dprhot
     GemmArgs a8{Q, C, B, Nc, d, d, d, d};
     return launch_g8<Epi8Store, 2>(a8, epi, st);
   }
-  const int tile = (force_tile() < 0 && big_ok(B, Nc, d)) ? kBigTile : pick_tile(B, Nc, d, 1, 2 * kNumCU);
-  GemmArgs a{Q, C, B, Nc, d, d, d, cdiv(d, kTiles[tile].bk) * kTiles[tile].bk};
+  const int tile = g.tile;
+  GemmArgs a{Q, C, B, Nc, d, d, d, g.kchunk};
   EpiSim epi{S, colmask, B, Nc, inv_T, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0};
   epi = with_packed_mask(pk, epi);
   return launch_gemm<true, true>(tile, a, epi, 1, st);
@@ -1789,12 +1808,73 @@ int dprhot_search_workspace_bytes(int nq, int chunk, size_t* h_out) {
   return DPRHOT_OK;
 }
 
-int dprhot_search(const dprhot_bf16* Q, int nq, const dprhot_bf16* C, int64_t n_ctx, int d, int64_t id_offset, int k, int chunk,
-                  float* values, int64_t* indices, int first, void* workspace, size_t workspace_bytes, void* stream) {
-  REQUIRE(Q && C && values && indices, "NULL pointer");
+// ---- the plan of dprhot_search: every host decision of a call in one place ---------------------------------------------------------
+// The form code of a launch (include/dprhot.h, dprhot_search_plan): 0..5 a register-staged tile of gemm_bf16.h, 6 the 256 x 256
+// gemm256_kernel, 7 the phase-interleaved gemm8p_kernel, 8 tile 0 on LDS-DMA (gemm128d.h).  Derived from the same SimGemm and the same
+// g128d_takes that the launch reads.
+static int gemm_form(const SimGemm& g, int M, int N, int K) {
+  if (g.g8) return 7;
+  if (g.tile == kBigTile) return 6;
+  const GemmArgs a{nullptr, nullptr, M, N, K, K, K, g.kchunk};
+  return (g.tile == 0 && g128d_takes<true, true>(a)) ? 8 : g.tile;
+}
+struct SearchStep {
+  int64_t j0;  // first row of the shard
+  int cols;
+  bool head;   // scores stored and selected from (dprhot_sim_fwd + dprhot_topk_update); else filtered in the GEMM epilogue and merged
+  SimGemm g;
+};
+static int check_search_shape(int nq, int64_t n_ctx, int d, int k, int chunk) {
   REQUIRE(nq > 0 && n_ctx > 0 && d > 0 && d % 8 == 0, "bad shape nq=%d n_ctx=%lld d=%d", nq, (long long)n_ctx, d);
   REQUIRE(n_ctx % 8 == 0 && chunk > 0 && chunk % 8 == 0, "n_ctx=%lld and chunk=%d must be multiples of 8", (long long)n_ctx, chunk);
   REQUIRE(k > 0 && k <= TK_KMAX, "k=%d out of range (1..%d)", k, TK_KMAX);
+  return DPRHOT_OK;
+}
+// Calls f(step) for every launch pair of a search over n_ctx rows, in order; stops at the first non-zero return and passes it on.
+// An empty state is started from a SHORT head (its scores are materialised and selected from: cost proportional to the head), the
+// filtered chunks behind it may be as long as the workspace allows: every chunk costs one merge launch, and a merge rewrites the
+// whole state (k = 1000: 57 us each; 31 chunks of 65536 spent 1.7 ms of a 5.6 ms search merging)
+// Behind the head every chunk is as long as everything scored before it (doubling, up to `chunk`): a chunk that covers the
+// fraction f of the corpus behind a prefix s leaves ~k f / s candidates per row against the threshold of its start -- f = s keeps
+// that at ~k (the merge's fast path holds 2048), f = 4 s left 4 k and a 790 us merge.
+extern "C++" {
+template <class F>
+int search_plan(int nq, int64_t n_ctx, int d, int chunk, int first, F&& f) {
+  const int head = chunk < 65536 ? chunk : 65536;
+  for (int64_t j0 = 0, step = 0; j0 < n_ctx; j0 += step) {
+    step = (first && j0 == 0) ? head : (first ? (j0 < chunk ? (j0 / 8 * 8 > head ? j0 / 8 * 8 : head) : chunk) : chunk);
+    if (step > chunk) step = chunk;
+    const int cols = (int)((n_ctx - j0 < step) ? (n_ctx - j0) : step);
+    if (int rc = f(SearchStep{j0, cols, first && j0 == 0, sim_gemm(nq, cols, d)})) return rc;
+  }
+  return DPRHOT_OK;
+}
+}  // extern "C++"
+
+int dprhot_search_plan(int nq, int64_t n_ctx, int d, int k, int chunk, int first, int64_t* h_steps, int capacity, int* h_count) {
+  REQUIRE(h_count != nullptr && capacity >= 0 && (h_steps != nullptr || capacity == 0), "NULL pointer");
+  if (int rc = check_search_shape(nq, n_ctx, d, k, chunk)) return rc;
+  int n = 0;
+  (void)search_plan(nq, n_ctx, d, chunk, first, [&](const SearchStep& s) {
+    if (n < capacity) {
+      int64_t* e = h_steps + (size_t)n * 4;
+      e[0] = s.j0;
+      e[1] = s.cols;
+      e[2] = s.head ? 1 : 0;
+      e[3] = gemm_form(s.g, nq, s.cols, d);
+    }
+    ++n;
+    return DPRHOT_OK;
+  });
+  *h_count = n;
+  REQUIRE(n <= capacity, "search plan has %d steps, capacity %d", n, capacity);
+  return DPRHOT_OK;
+}
+
+int dprhot_search(const dprhot_bf16* Q, int nq, const dprhot_bf16* C, int64_t n_ctx, int d, int64_t id_offset, int k, int chunk,
+                  float* values, int64_t* indices, int first, void* workspace, size_t workspace_bytes, void* stream) {
+  REQUIRE(Q && C && values && indices, "NULL pointer");
+  if (int rc = check_search_shape(nq, n_ctx, d, k, chunk)) return rc;
   REQUIRE(id_offset >= 0, "negative id_offset");
   REQUIRE(aligned16(Q) && aligned16(C), "pointers must be 16-byte aligned");
   const size_t need = search_ws_bytes(nq, chunk);
@@ -1806,47 +1886,29 @@ int dprhot_search(const dprhot_bf16* Q, int nq, const dprhot_bf16* C, int64_t n_
   int* cand_j = reinterpret_cast<int*>(static_cast<char*>(workspace) + (size_t)nq * chunk * 4);
   int* cnt = reinterpret_cast<int*>(static_cast<char*>(workspace) + (size_t)nq * chunk * 8);
   HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)nq * sizeof(int), st));
-  // An empty state is started from a SHORT head (its scores are materialised and selected from: cost proportional to the head), the
-  // filtered chunks behind it may be as long as the workspace allows: every chunk costs one merge launch, and a merge rewrites the
-  // whole state (k = 1000: 57 us each; 31 chunks of 65536 spent 1.7 ms of a 5.6 ms search merging)
-  // Behind the head every chunk is as long as everything scored before it (doubling, up to `chunk`): a chunk that covers the
-  // fraction f of the corpus behind a prefix s leaves ~k f / s candidates per row against the threshold of its start -- f = s keeps
-  // that at ~k (the merge's fast path holds 2048), f = 4 s left 4 k and a 790 us merge.
-  const int head = chunk < 65536 ? chunk : 65536;
-  for (int64_t j0 = 0, step = 0; j0 < n_ctx; j0 += step) {
-    step = (first && j0 == 0) ? head : (first ? (j0 < chunk ? (j0 / 8 * 8 > head ? j0 / 8 * 8 : head) : chunk) : chunk);
-    if (step > chunk) step = chunk;
-    const int cols = (int)((n_ctx - j0 < step) ? (n_ctx - j0) : step);
+  return search_plan(nq, n_ctx, d, chunk, first, [&](const SearchStep& s) -> int {
+    const int cols = s.cols;
+    const int64_t j0 = s.j0;
     const dprhot_bf16* Cj = C + (size_t)j0 * d;
-    if (first && j0 == 0) {
-      // nothing to filter against yet: materialise this chunk's scores and select from them
+    if (s.head) {
+      // nothing to filter against yet: materialise this chunk's scores and select from them (the forward makes the same sim_gemm choice)
       if (int rc = dprhot_sim_fwd(Q, nq, Cj, cols, d, nullptr, 1.0f, S, stream)) return rc;
-      if (int rc = dprhot_topk_update(S, nq, cols, cols, id_offset + j0, k, values, indices, 1, stream)) return rc;
-      continue;
+      return dprhot_topk_update(S, nq, cols, cols, id_offset + j0, k, values, indices, 1, stream);
     }
-    // scores that cannot enter the top-k never leave the GEMM tile
-    if (g8_ok(nq, cols, d)) {  // the phase-interleaved kernel (gemm8p.h); thresholds arrive with the tile's input words
-      // (Round 4 merged warm chunks in groups of up to four -- option search_group: up to four chunks filtered against the same stale
-      //  thresholds appended to ONE candidate list of `chunk` entries per row, with no bound on the append: a corpus whose later
-      //  chunks beat the current k-th value could write past its row.  It had measured no gain -- 4.76 ms either way at 1024 x 2 M,
-      //  k = 1000 -- and is gone; one merge per chunk, at most `cols` candidates per row and chunk, is what the workspace is sized for.)
-      {
-        const Epi8Filter e8{values, indices, k, nq, cols, (long long)(id_offset + j0), cnt, S, cand_j, Q, 0};
-        GemmArgs a8{Q, Cj, nq, cols, d, d, d, d};
-        if (int rc = launch_g8(a8, e8, st)) return rc;
-      }
-      TopkArgs p8{S, nq, cols, (long long)cols, (long long)(id_offset + j0), k, values, indices, 0, cand_j, cnt};
-      if (int rc = launch_topk(p8, nq, st)) return rc;
-      continue;
+    // scores that cannot enter the top-k never leave the GEMM tile; one merge per chunk, at most `cols` candidates per row and chunk,
+    // is what the workspace is sized for
+    if (s.g.g8) {  // the phase-interleaved kernel (gemm8p.h); thresholds arrive with the tile's input words
+      const Epi8Filter e8{values, indices, k, nq, cols, (long long)(id_offset + j0), cnt, S, cand_j, Q, 0};
+      GemmArgs a8{Q, Cj, nq, cols, d, d, d, d};
+      if (int rc = launch_g8(a8, e8, st)) return rc;
+    } else {
+      GemmArgs a{Q, Cj, nq, cols, d, d, d, s.g.kchunk};
+      EpiFilter epi{values, indices, k, nq, cols, (long long)(id_offset + j0), cnt, S, cand_j};
+      if (int rc = launch_gemm<true, true>(s.g.tile, a, epi, 1, st)) return rc;
     }
-    const int tile = (force_tile() < 0 && big_ok(nq, cols, d)) ? kBigTile : pick_tile(nq, cols, d, 1, 2 * kNumCU);
-    GemmArgs a{Q, Cj, nq, cols, d, d, d, cdiv(d, kTiles[tile].bk) * kTiles[tile].bk};
-    EpiFilter epi{values, indices, k, nq, cols, (long long)(id_offset + j0), cnt, S, cand_j};
-    if (int rc = launch_gemm<true, true>(tile, a, epi, 1, st)) return rc;
     TopkArgs p{S, nq, cols, (long long)cols, (long long)(id_offset + j0), k, values, indices, 0, cand_j, cnt};
-    if (int rc = launch_topk(p, nq, st)) return rc;
-  }
-  return DPRHOT_OK;
+    return launch_topk(p, nq, st);
+  });
 }
 
 // ---- the training step: check the arguments, derive the plan once, claim the workspace, run the body with a default context ----

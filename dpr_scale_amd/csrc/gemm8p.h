@@ -907,8 +907,8 @@ struct Epi8Filter {
   float* cand_v;            // [M][N]
   int* cand_j;              // [M][N]
   const void* dummy;
-  int j_bias = 0;           // added to the column written to cand_j: a chunk appended to the candidate lists of the chunk(s) before
-                            // it (dprhot_search merges groups of warm chunks once; the merge sees columns relative to the group's start)
+  int j_bias = 0;           // added to the column written to cand_j; always 0: dprhot_search merges every chunk on its own, so a
+                            // column is relative to its own chunk (the field stays: the kernel's registers are counted by hand)
   __device__ __forceinline__ const void* meta_src(int m0, int n0, int e) const {
     if (e >= 512 && e < 768) return kth_val + (size_t)min(m0 + e - 512, M - 1) * k + (k - 1);
     return dummy;

@@ -312,6 +312,14 @@ int dprhot_search_workspace_bytes(int nq, int chunk, size_t* h_out);
 int dprhot_search(const dprhot_bf16* Q, int nq, const dprhot_bf16* C, int64_t n_ctx, int d, int64_t id_offset,
                   int k, int chunk, float* values, int64_t* indices, int first, void* workspace,
                   size_t workspace_bytes, void* stream);
+/* The launches dprhot_search would make for this shape under the current options, in order, without touching a device: the same host
+ * function dprhot_search iterates.  Four int64 words per step in h_steps: the step's first row j0, its column count, 1 for the head of
+ * an empty state (scores stored by dprhot_sim_fwd's kernel and selected from) or 0 for a filtered chunk, and the form of its GEMM:
+ * 0..5 the register-staged tile of that id, 6 the 256 x 256 gemm256_kernel, 7 the phase-interleaved gemm8p_kernel, 8 tile 0 on
+ * LDS-DMA (gemm128d_kernel).  The head's form is also the form of dprhot_sim_fwd at (nq, cols, d).  Arguments are validated as by
+ * dprhot_search; *h_count receives the number of steps, and the call fails (DPRHOT_E_INVALID, nothing beyond capacity written) when
+ * capacity steps do not hold them.  h_steps may be NULL with capacity 0. */
+int dprhot_search_plan(int nq, int64_t n_ctx, int d, int k, int chunk, int first, int64_t* h_steps, int capacity, int* h_count);
 
 /* Pairwise scores of the CITADEL router / distillation path (dpr_scale/task/citadel_task.py:137-146, sim_score(...,
  * pairwise=True)): query b against its own M contexts,  S[b][j] = <q[b], c[b*M + j]>, -inf where mask[b*M + j] != 0

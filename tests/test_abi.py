@@ -58,6 +58,21 @@ def test_argument_validation_is_host_side():
     assert lib.dprhot_search(None, 1, None, 8, 64, 0, 1, 8, None, None, 1, None, 0, None) == -1
     assert lib.dprhot_search_workspace_bytes(4, 12, ctypes.byref(out)) == -1  # chunk % 8
     assert lib.dprhot_search_workspace_bytes(4, 16, ctypes.byref(out)) == 0 and out.value >= 4 * 16 * 8
+    # the plan query of the search: the same shape checks as dprhot_search, host code only, and a capacity it does not exceed
+    cnt, steps = ctypes.c_int(-5), (ctypes.c_int64 * 8)()
+    good = dict(nq=4, n=64, d=64, k=5, chunk=32, first=1)
+    for bad, word in ((dict(nq=0), b"bad shape"), (dict(n=0), b"bad shape"), (dict(d=12), b"bad shape"), (dict(n=60), b"multiples of 8"),
+                      (dict(chunk=12), b"multiples of 8"), (dict(chunk=0), b"multiples of 8"), (dict(k=0), b"out of range"),
+                      (dict(k=1025), b"out of range")):
+        a = {**good, **bad}
+        assert lib.dprhot_search_plan(*a.values(), steps, 2, ctypes.byref(cnt)) == -1 and word in lib.dprhot_last_error(), bad
+        assert lib.dprhot_search(_ONE, a["nq"], _ONE, a["n"], a["d"], 0, a["k"], a["chunk"], _ONE, _ONE, 1, _ONE, 1 << 20, None) == -1
+        assert word in lib.dprhot_last_error() and cnt.value == -5, bad
+    assert lib.dprhot_search_plan(*good.values(), steps, 2, None) == -1 and b"NULL" in lib.dprhot_last_error()
+    assert lib.dprhot_search_plan(*good.values(), None, 2, ctypes.byref(cnt)) == -1 and b"NULL" in lib.dprhot_last_error()
+    assert lib.dprhot_search_plan(*good.values(), steps, -1, ctypes.byref(cnt)) == -1
+    assert lib.dprhot_search_plan(*good.values(), steps, 1, ctypes.byref(cnt)) == -1 and cnt.value == 2 and b"capacity" in lib.dprhot_last_error()
+    assert lib.dprhot_search_plan(*good.values(), steps, 2, ctypes.byref(cnt)) == 0 and cnt.value == 2 and list(steps) == [0, 32, 1, 3, 32, 32, 0, 3]
     null = None
     assert lib.dprhot_inbatch_step_f32(null, null, null, null, 4, 8, 64, null, 0, null, 1.0, 1.0, 1.0, null, null, null, null,
                                        null, null, null, null, null, 0, null) == -1

@@ -646,7 +646,7 @@ def test_topk_state_with_fewer_columns_than_k(kn, dev):
 
 @pytest.mark.parametrize("nq,shards,d,k,chunk", [(9, (4000, 13, 8, 2051), 64, 20, 1024), (130, (50000,), 768, 100, 8192),
                                                  (512, (100000, 40000), 128, 50, 32768),  # >= 256 tiles per chunk: the gemm8p.h filter epilogue
-                                                 (512, (300000,), 128, 50, 32768),  # warm chunks merged in groups of 2, then 4 (dprhot_search)
+                                                 (512, (300000,), 128, 50, 32768),  # a head and nine filtered chunks, each merged on its own (dprhot_search)
                                                  (300, (200000, 70000), 128, 1000, 32768),  # ... at k = 1000, a second shard behind them
                                                  (7, (30000, 5000), 128, 1000, 4096),  # --topk 1000: dragon/README recipes
                                                  (40, (60000, 9000), 128, 300, 8192)])  # 48 KB variant, counted candidate merges
