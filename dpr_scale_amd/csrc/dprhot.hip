@@ -173,7 +173,7 @@ constexpr OptDef kOptDefs[OPT_COUNT] = {
     {OPT_P16_STAGED, "p16_staged", 1, "one-pass forward on the 256 x 256 kernel: the fp16 numerators leave through the per-wave LDS patch (64-byte pieces of 16 rows per store instruction instead of 32-byte pieces of 32 rows; bit-identical): 1 = except where the row pitch of G is a multiple of 128 KiB (forward us, arms alternating, profiles/r06_p16_staged_ab.txt: 8192^2 155.4 -> 147.8, 4096 x 8192 83.2 -> 79.3, 4096 x 16384 153 -> 146 and its step 390 -> 372; at 65536 columns the forward gains nothing and the step of 8192 x 65536 LOSES 100 us of 2880), 2 = always, 0 = never"},
     {OPT_SMALL_SIM, "small_sim", 1, "sim launch of the batch-32 step (B <= 32, fp32 q, 256-deep K chunks: sim_small.h): 1 = one wave per 16 x 16 tile and K chunk on an exact 3-D grid (row tile, column tile, chunk: no division and one wait on the arguments in front of the first operand load, the mask byte loaded last), whole-line loads rounded into a wave-private LDS patch, no barrier (bit-identical to the engine; 32 x 256 x 768 step 9.19 -> 8.29 us, with the 3-D grid 7.21 -> 7.05); 0 = the GEMM engine (tile 5); A/B only: 2 = fp32 straight into fragment registers, no LDS (8.52 us), 3 / 4 = forms 1 / 2 with two waves per workgroup (8.70 / 9.41 us)"},
     {OPT_SMALL_STEP_ROLES, "small_step_roles", 3, "softmax + backward launch of the batch-32 step (B <= 32, at most 768 columns: step_small_kernel_roles / step_small_kernel_out in step_small.h): one launch split by role -- d / 16 dC workgroups (slabs + Q tile, full softmax, one barrier, dC product and stores) next to one dQ workgroup per 16-row half and column tile (half the slabs + C tile, 8 K slices); 3 = form 2 with the outputs written by workgroups of their own that have no product to do, in front of the grid, instead of by the dC workgroup of tile 0: a loss block (softmax up to the row loss, logsumexp / row loss, one barrier, the loss sum) and two row-store blocks (one 16-row half each: dScores / logits, no barrier); the device-side scale is the last load of a role, not a wait in front of it (a stamping launch of the packed step keeps form 2), 2 = 32-column dQ tiles (d % 32 == 0, else form 1; 32 x 256 x 768 step 8.29 -> 7.74 us), 1 = 16-column dQ tiles (7.84 us), 0 = every workgroup does both products (step_small_kernel); all forms bit-identical (tests/test_small_step_roles.py, tests/test_small_step_out.py, tests/test_small_step_split_gpu.py)"},
-    {OPT_SMALL_SIM_COPY, "small_sim_copy", 1, "sim launch of the batch-32 step where small_sim selects form 1: 1 = the bf16 copies Qb / Cb are written by waves of their own behind the compute waves in dispatch order (sim_small_split_kernel: 16 rows x one 256-deep chunk of one operand per wave, whole-line loads, the same v_cvt_pk_bf16_f32 pairing, 8-byte stores; the compute waves go from their MFMA chain straight to their slab stores; bit-identical); 0 = every compute wave of row tile 0 / column tile 0 stores the copies itself, in front of its slab stores (sim_small_kernel)"},
+    {OPT_SMALL_SIM_COPY, "small_sim_copy", 1, "sim launch of the batch-32 step where small_sim selects form 1: 1 = the bf16 copies Qb / Cb are written by waves of their own behind the compute waves in dispatch order (sim_small_split_kernel: 16 rows x one 256-deep chunk of one operand per wave, whole-line loads, the same v_cvt_pk_bf16_f32 pairing; the compute waves go from their MFMA chain straight to their slab stores; bit-identical), and the copy waves store 16-byte WRITE-THROUGH (sc1) pieces -- lanes 2m / 2m + 1 exchange one 8-byte piece by DPP quad_perm [1, 0, 3, 2], eight buffer stores per lane, nothing waits for them -- so the copies' 442 KB are not dirty lines of the XCD L2s that the kernel boundary writes back behind the last wave (profiles/dirty_boundary_probe.txt: 0.2 us per boundary; 32 x 256 x 768 step 6.62 -> 6.42 us, profiles/small_wt_ab.txt; tests/test_small_wt_gpu.py); 2 = the copy waves with the 8-byte plain stores they had before (A/B); 0 = every compute wave of row tile 0 / column tile 0 stores the copies itself, in front of its slab stores (sim_small_kernel).  The same write-through form for the dC tiles of the second launch LOST (scratch/negative/README.md)"},
 };
 constexpr bool opt_table_in_enum_order() {  // (round 6: a row added in the wrong place made two options answer to each other's names)
   for (int i = 0; i < OPT_COUNT; ++i)
@@ -707,6 +707,9 @@ int launch_sim_small(bool b_f32, const GemmArgs& a, const EpiSim& epi, int split
     // (C tiles only where the contexts are fp32 and have a copy) -- two layers per chunk where a layer of the grid is smaller than that
     const int units = (b_f32 && a.Bcopy != nullptr ? nct : 0) + (a.Acopy != nullptr ? nrt : 0);
     const dim3 grid(nrt, nct, splits + cdiv(units, nrt * nct) * splits), block(64);
+    if (opt(OPT_SMALL_SIM_COPY) != 2)  // write-through copies (a template argument, not a branch in the kernel)
+      return b_f32 ? launch<sim_small_split_kernel<true, 1>>(grid, block, lds, st, splits, a, epi)
+                   : launch<sim_small_split_kernel<false, 1>>(grid, block, lds, st, splits, a, epi);
     return b_f32 ? launch<sim_small_split_kernel<true>>(grid, block, lds, st, splits, a, epi)
                  : launch<sim_small_split_kernel<false>>(grid, block, lds, st, splits, a, epi);
   }

@@ -40,6 +40,8 @@ inline size_t sim_small_lds(int form, bool b_f32, int wpg) {
   return form == SS_PATCH ? (size_t)wpg * SMS_PATCH * 2 * (b_f32 ? 2 : 1) : 0;
 }
 
+typedef uint32_t sms_u32x4 __attribute__((ext_vector_type(4)));
+
 __device__ __forceinline__ bf16x8 sms_round(const float4& a, const float4& b) {
   const uint4 v = make_uint4(cvt_pk_bf16(a.x, a.y), cvt_pk_bf16(a.z, a.w), cvt_pk_bf16(b.x, b.y), cvt_pk_bf16(b.z, b.w));
   return __builtin_bit_cast(bf16x8, v);
@@ -207,7 +209,13 @@ __global__ __launch_bounds__(64 * SMS_MAXW) void sim_small_kernel(int wpg, GemmA
 // beyond the operand are loaded clamped and not stored.  No LDS hop, no fragment reads, no MFMA chain, half the bytes: on a CU of
 // its own such a wave ends before the compute waves do, and these no longer carry 8 (16) stores between their chain and their slab.
 // Everything either role's addresses are made of is in the first 64 bytes of the kernel arguments (`splits` in wpg's place).
-template <bool B_F32>
+// WT (option small_sim_copy = 1; 2 keeps the 8-byte plain stores for the A/B): the same words leave as 16-byte WRITE-THROUGH stores.  A kernel's end writes back what its stores left dirty
+// in the XCD L2s, behind the last wave (profiles/dirty_boundary_probe.txt: the copies' 442 KB cost the boundary 0.2 us); an sc1
+// store goes through and leaves no dirty line, and at 16 bytes per lane it costs what a plain one does -- at 8 bytes 2.7 x.  Nothing
+// re-reads Qb / Cb in front of the next boundary.  A lane holds 8 bytes of row r0 and 8 of row r0 + 8 per kk; lanes 2m and 2m + 1
+// (neighbouring 8-byte pieces of both rows) exchange one of them by DPP quad_perm [1, 0, 3, 2]: the even lane then owns 16 contiguous
+// bytes of row r0, the odd lane 16 of row r0 + 8 -- eight stores per lane instead of sixteen, 16 rows x 64 B per instruction.
+template <bool B_F32, int WT = 0>
 __device__ __forceinline__ void sms_copy_wave(int zc, int splits, const GemmArgs& p) {
   DPRHOT_TM(0);
   const int lane = threadIdx.x & 63;
@@ -233,27 +241,47 @@ __device__ __forceinline__ void sms_copy_wave(int zc, int splits, const GemmArgs
   uint2 v[2 * SMS_KK];
 #pragma unroll
   for (int j = 0; j < 2 * SMS_KK; ++j) v[j] = make_uint2(cvt_pk_bf16(raw[j].x, raw[j].y), cvt_pk_bf16(raw[j].z, raw[j].w));
-  // (two predicates for sixteen stores: a lane's second row is inside the operand only if its first one is)
-  if (r0 < rows) {
-    uint16_t* const dp = dst + (size_t)r0 * ld + kbeg + (lane & 7) * 4;
+  if constexpr (WT != 0) {
+    const bool odd = (lane & 1) != 0;
+    const int myrow = r0 + (odd ? 8 : 0);
+    // (the descriptor ends with the operand's last row: the range check would drop a row beyond it even without the predicate)
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(dst, 0, rows * ld * 2, 0x00020000);
+    const int off = (myrow * ld + kbeg + ((lane & 7) - (odd ? 1 : 0)) * 4) * 2;
+    sms_u32x4 w[SMS_KK];
 #pragma unroll
-    for (int kk = 0; kk < SMS_KK; ++kk) *reinterpret_cast<uint2*>(dp + kk * 32) = v[2 * kk];
-    if (r0 + 8 < rows) {
+    for (int kk = 0; kk < SMS_KK; ++kk) {
+      const uint2 mine = odd ? v[2 * kk + 1] : v[2 * kk], give = odd ? v[2 * kk] : v[2 * kk + 1];
+      const uint2 got = make_uint2((uint32_t)__builtin_amdgcn_update_dpp(0, (int)give.x, 0xB1, 0xF, 0xF, false),
+                                   (uint32_t)__builtin_amdgcn_update_dpp(0, (int)give.y, 0xB1, 0xF, 0xF, false));
+      w[kk] = odd ? sms_u32x4{got.x, got.y, mine.x, mine.y} : sms_u32x4{mine.x, mine.y, got.x, got.y};
+    }
+    if (myrow < rows) {
 #pragma unroll
-      for (int kk = 0; kk < SMS_KK; ++kk) *reinterpret_cast<uint2*>(dp + (size_t)8 * ld + kk * 32) = v[2 * kk + 1];
+      for (int kk = 0; kk < SMS_KK; ++kk) __builtin_amdgcn_raw_buffer_store_b128(w[kk], rs, off + kk * 64, 0, 16);  // aux 16: sc1
+    }
+  } else {
+    // (two predicates for sixteen stores: a lane's second row is inside the operand only if its first one is)
+    if (r0 < rows) {
+      uint16_t* const dp = dst + (size_t)r0 * ld + kbeg + (lane & 7) * 4;
+#pragma unroll
+      for (int kk = 0; kk < SMS_KK; ++kk) *reinterpret_cast<uint2*>(dp + kk * 32) = v[2 * kk];
+      if (r0 + 8 < rows) {
+#pragma unroll
+        for (int kk = 0; kk < SMS_KK; ++kk) *reinterpret_cast<uint2*>(dp + (size_t)8 * ld + kk * 32) = v[2 * kk + 1];
+      }
     }
   }
   DPRHOT_TM(6);
 }
 
-template <bool B_F32>
+template <bool B_F32, int WT = 0>
 __global__ __launch_bounds__(64) void sim_small_split_kernel(int splits, GemmArgs p, EpiSim epi) {
   extern __shared__ __attribute__((aligned(16))) uint16_t sms_smem[];
   const int bz = (int)blockIdx.z;
   if (bz < splits)
     sms_tile<B_F32, SS_PATCH, false>(sms_smem, 0, (int)blockIdx.x, (int)blockIdx.y, bz, p, epi);
   else
-    sms_copy_wave<B_F32>(bz - splits, splits, p);
+    sms_copy_wave<B_F32, WT>(bz - splits, splits, p);
 }
 
 }  // namespace dprhot

@@ -72,7 +72,8 @@ const char* dprhot_last_error(void);
  *   small_sim (1)          the batch-32 step's sim launch on csrc/sim_small.h | 0: on the GEMM engine | 2..4: its other forms
  *   small_step_roles (3)   the batch-32 step's softmax + backward launch split by role, outputs from workgroups of their own |
  *                          2: outputs from the dC workgroup of tile 0 | 1: 2 with 16-column dQ tiles | 0: unsplit
- *   small_sim_copy (1)     the batch-32 sim launch writes its bf16 copies on waves of their own, 0: on the compute waves
+ *   small_sim_copy (1)     the batch-32 sim launch writes its bf16 copies on waves of their own, as 16-byte write-through pieces |
+ *                          2: as 8-byte plain pieces | 0: on the compute waves
  * An option changes which kernels run -- the summation order and where a value is rounded with them -- never what is computed;
  * sk_dq_atomic = 1 alone gives up run-to-run bit-reproducibility.
  * Setting one changes the plans of every later call on every thread (workspace sizes included: query them after setting).
