@@ -547,6 +547,10 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(SoftmaxArgs p) {
         s *= __expf(m - lm);  // m == -inf -> s == 0 * 0
         m = lm;
       }
+      // fmaxf drops a NaN: a float4 of NaN beside -inf has lm == -inf (NaN when all four are) and moves no maximum, but the row's
+      // loss is NaN as nn.CrossEntropyLoss has it.  While this thread has met no number, the sum of the four tells such a float4
+      // (NaN) from a genuinely empty one (-inf); it then takes 0 as the maximum its (NaN) sum is relative to.
+      if (m == -INFINITY && (v.x + v.y) + (v.z + v.w) != -INFINITY) m = 0.f;
       if (m != -INFINITY) s += __expf(v.x - m) + __expf(v.y - m) + __expf(v.z - m) + __expf(v.w - m);
     }
   }

@@ -81,30 +81,45 @@ def forward(q, c, y, colmask, inv_T, gs, y_offset=0, f16=False):
     S = (q64 @ c64.T) * inv_T
     A = (q64.abs() @ c64.abs().T) * abs(inv_T)
     eS = (gamma(d) + U) * A
-    if colmask is not None:
-        mk = colmask.to(torch.bool)
-        S[:, mk] = -math.inf
-        eS[:, mk] = 0.0
-    else:
-        mk = torch.zeros(Nc, dtype=torch.bool, device=q.device)
-    yg = (y.to(torch.int64) + int(y_offset)).to(q.device)
-    rows = torch.arange(B, device=q.device)
+    mk = colmask.to(torch.bool) if colmask is not None else torch.zeros(Nc, dtype=torch.bool, device=q.device)
+    return dict(from_scores(S, y, gs, y_offset, mk, eS, f16=f16), A=A, inv_T=inv_T)
+
+
+def _e_lse_strips(P, gap, eS, lse, m, s):
+    """The lse bound of the strip-statistics plans of the training step (module docstring, "lse")."""
+    return (P * (eS + 4 * U * (1 + gap))).sum(1) + gamma(P.shape[1]) + 2 * U * (lse.abs().nan_to_num(0.0, 0.0, 0.0) + m.abs().nan_to_num(0.0, 0.0, 0.0) + 1)
+
+
+def from_scores(S, y, gs, y_offset=0, mask=None, eS=None, f16=False, e_lse=_e_lse_strips, exp_u=4, g_tiny=0.0):
+    """The reference from the logits on: S [B, Nc] fp64 with the bound eS of its elements (None: the logits are given, eS = 0), mask
+    [Nc] or -- one window per row -- [B, Nc] (True = the column counts as -inf), y [B] rank-local gold.  `e_lse(P, gap, eS, lse, m, s)`
+    is the plan's bound of the row logsumexp (m, s: the row maximum and the sum of exp(S - m)); the exp of the G pass costs
+    exp_u * u (1 + gap) relative; g_tiny: absolute allowance of a G product that is itself flushed.  The same keys as `forward`."""
+    B, Nc = S.shape
+    dev = S.device
+    mk = torch.zeros(Nc, dtype=torch.bool, device=dev) if mask is None else mask.to(torch.bool)
+    eS = torch.zeros_like(S) if eS is None else eS
+    S = torch.where(mk.expand_as(S), torch.full_like(S, -math.inf), S)
+    eS = torch.where(mk.expand_as(S), torch.zeros_like(eS), eS)
+    yg = (y.to(torch.int64) + int(y_offset)).to(dev)
+    rows = torch.arange(B, device=dev)
     lse, m, s = _logsumexp(S)
     fin = torch.isfinite(lse)
     P = torch.where(torch.isfinite(S) & fin[:, None], torch.exp(S - torch.where(fin, lse, 0.0)[:, None]), torch.zeros_like(S))
     gap = torch.where(torch.isfinite(S) & fin[:, None], lse[:, None] - S, torch.zeros_like(S))  # lse - S >= 0
-    e_lse = (P * (eS + 4 * U * (1 + gap))).sum(1) + gamma(Nc) + 2 * U * (lse.abs().nan_to_num(0.0, 0.0, 0.0) + m.abs().nan_to_num(0.0, 0.0, 0.0) + 1)
+    e_lse = e_lse(P, gap, eS, lse, m, s)
     gold = S[rows, yg]
     loss = lse - gold
     e_loss = e_lse + eS[rows, yg] + U * loss.abs().nan_to_num(0.0, 0.0, 0.0)
-    eps = eS + e_lse[:, None] + 4 * U * (1 + gap) + 2 * U
+    eps = eS + e_lse[:, None] + exp_u * U * (1 + gap) + 2 * U
     if f16:
         eps = eps + F16_REL
     G = P * gs
     G[rows, yg] -= gs
     dG = abs(gs) * (P * eps + (F16_ABS if f16 else 0.0) + TINY) + 2 * U * G.abs()
-    return dict(S=S, A=A, eS=eS, lse=lse, e_lse=e_lse, loss=loss, e_loss=e_loss, P=P, G=G, dG=dG, eps=eps, mask=mk, yg=yg, gs=gs,
-                inv_T=inv_T)
+    if g_tiny:
+        dG = dG + g_tiny
+    return dict(S=S, eS=eS, lse=lse, e_lse=e_lse, loss=loss, e_loss=e_loss, P=P, G=G, dG=dG, eps=eps, mask=mk, yg=yg, gs=gs)
 
 
 def _ratio(err, bound):
@@ -161,7 +176,7 @@ def g_scores(Gk, ref):
     lo, hi = _bf16_interval(gk)
     dist = torch.clamp(torch.maximum(lo - Gr, Gr - hi), min=0.0)
     sc = _ratio(dist, dG)
-    masked = ref["mask"][None, :].expand_as(Gr).clone()
+    masked = ref["mask"].expand_as(Gr).clone()  # [Nc], or [B, Nc] where every row has a window of its own
     masked[torch.arange(Gr.shape[0], device=Gr.device), ref["yg"]] = False
     sc = torch.where(masked, torch.where(gk == 0, 0.0, math.inf), sc)
     sc = torch.where(torch.isfinite(gk), sc, torch.full_like(sc, math.inf))
