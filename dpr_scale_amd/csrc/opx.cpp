@@ -338,8 +338,6 @@ at::Tensor floor_loss(const at::Tensor& q, const at::Tensor& c) { return FloorFn
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "host side of dpr_scale_amd's single-rank autograd step (C ABI calls + allocations in C++)";
   m.def("init", &init);
-  m.def("train_step", &train_step);
-  m.def("rescale", &rescale);
   m.def("packed_train_step", &packed_train_step);
   m.def("packed_backward", &packed_backward);
   m.def("inbatch_loss", &inbatch_loss);

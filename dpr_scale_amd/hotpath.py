@@ -7,9 +7,9 @@ HIP dQ / dC GEMMs | RCCL reduce-scatter of dC.  All device work goes through the
 
 `kernels` arguments exist so that the CPU test-suite can exercise the distributed orchestration (gather
 layout, label offsets, reduce-scatter, loss all-reduce) on gloo with a stand-in; the default -- and the only
-thing the product ever passes -- is the HIP library.
+thing the product ever passes -- is the HIP library.  A kernel set offers every entry point HipKernels offers: nothing
+below asks what it was given, so a stand-in takes the routes production takes.
 """
-import collections
 import ctypes
 import os
 
@@ -762,7 +762,7 @@ except Exception:  # pragma: no cover - a broken optional extension must not tak
 
 
 # the multi-rank packed step's host side in C++ (csrc/opx.cpp: packed_train_step / packed_backward); DPRHOT_OPX_PACKED=0: the Python wrappers
-_OPX_PACKED = _OPX is not None and hasattr(_OPX, "packed_train_step") and os.environ.get("DPRHOT_OPX_PACKED", "1") != "0"
+_OPX_PACKED = _OPX is not None and os.environ.get("DPRHOT_OPX_PACKED", "1") != "0"
 
 
 def default_kernels():
@@ -855,41 +855,29 @@ def defer_context_grad(c):
     return _DeferContextGrad.apply(c, pending), pending
 
 
-# ---- the operator's parts.  What the kernel set provides is read once per call, by attribute, into a _Caps; the staged operands and the
-# step's result travel as plain tuples and _Bwd takes attribute stores (a constructor call per step shows in the eager step's host time).
-_Caps = collections.namedtuple("_Caps", "inbatch_fwd_f32 inbatch_step_f32 inbatch_step_packed_f32 train_step_f32 train_step_packed_f32 widen")
-_HIP_CAPS = _Caps(*[hasattr(HipKernels, n) for n in _Caps._fields])  # (the library's own kernel set: read once, here)
-FAST = "FAST"                # the single-rank step of csrc/opx.cpp: gradients computed in forward, scaled by the predicted grad_output
-PRESCALED = "PRESCALED"      # the same from a train_step_* entry point of the kernel set (opx_packed: its host side in csrc/opx.cpp)
-UNIT = "UNIT"                # gradients computed in forward for grad_output = 1 (stand-in kernels); backward applies the scale
+# ---- the operator's parts.  Every kernel set offers what HipKernels offers (the stand-in of the CPU tests included): nothing here asks
+# what it was given.  The staged operands and the step's result travel as plain tuples and _Bwd takes attribute stores (a constructor
+# call per step shows in the eager step's host time).
+PRESCALED = "PRESCALED"      # gradients computed in forward by a train_step_* entry point, scaled by the predicted grad_output
+#                              (opx_packed: the packed step's host side in csrc/opx.cpp)
 SAVED = "SAVED"              # forward only: Qb, Cb, G saved for the backward GEMMs
 FP32G_DEBUG = "FP32G_DEBUG"  # DPRHOT_FP32_G=1: the logits kept, dScores rebuilt in fp32 and sent through the GEMMs as a bf16 pair
-REGEN = "REGEN"              # what FAST / PRESCALED turn into once they have given their tensors away: the backward GEMMs again
+REGEN = "REGEN"              # what PRESCALED turns into once it has given its tensors away: the backward GEMMs again
 
 
 class _Bwd:
-    """The one record forward leaves on ctx: kind, row_lse and that kind's fields -- FAST / PRESCALED: grads, used, site + REGEN's;
-    REGEN: Qb, Cb, G, pos_idx, y_off, mask (None: still packed in Cb), inv_T, grad_scale;  UNIT: grads;  FP32G_DEBUG: S, labels, gs
-    (SAVED and FP32G_DEBUG keep Qb, Cb, G in ctx.saved_tensors).  All but FAST and the REGEN it turns into (`fast`) also carry
-    what the general backward needs: kn, group, W, n_ctx, rows_c, d, multi, direct_ctx_grad, in_dtypes, pending, can_widen."""
+    """The one record forward leaves on ctx: kind, row_lse and that kind's fields -- PRESCALED: grads, used, site, opx_packed + REGEN's;
+    REGEN: Qb, Cb, G, pos_idx, y_off, mask (None: still packed in Cb), inv_T, grad_scale;  FP32G_DEBUG: S, labels, gs
+    (SAVED and FP32G_DEBUG keep Qb, Cb, G in ctx.saved_tensors).  All carry what backward needs besides: kn, group, W, n_ctx, rows_c,
+    d, multi, direct_ctx_grad, in_dtypes, pending."""
 
-    __slots__ = ("kind", "fast", "row_lse", "grads", "used", "site", "opx_packed", "Qb", "Cb", "G", "pos_idx", "y_off", "mask", "inv_T", "grad_scale",
-                 "S", "labels", "gs", "kn", "group", "W", "n_ctx", "rows_c", "d", "multi", "direct_ctx_grad", "in_dtypes", "pending", "can_widen")
+    __slots__ = ("kind", "row_lse", "grads", "used", "site", "opx_packed", "Qb", "Cb", "G", "pos_idx", "y_off", "mask", "inv_T", "grad_scale",
+                 "S", "labels", "gs", "kn", "group", "W", "n_ctx", "rows_c", "d", "multi", "direct_ctx_grad", "in_dtypes", "pending")
 
 
 def _plain_single_rank(q, group, kernels):
-    """Both C++ short cuts (the step below, inbatch_contrastive_loss's node) ask first: own kernels, a device, one rank, no debug mode."""
+    """The C++ node of inbatch_contrastive_loss asks first: own kernels, a device, one rank, no debug mode."""
     return kernels is None and q.is_cuda and (group is False or D.world(group)[0] == 1) and not _fp32_g_mode() and not (D.force_dist() and group is not False)
-
-
-def _opx_step_eligible(q, c, pos_idx, ctx_mask, group, kernels, wants_grad):
-    """The step a single-GPU run issues every iteration (dpr_task.py:197-212) has its host side in C++ (csrc/opx.cpp).  Taken when
-    nothing needs the general code: fp32 contiguous encoder outputs, a whole number of 8-column groups, a byte mask."""
-    if not wants_grad or not c.is_cuda or not _plain_single_rank(q, group, kernels):
-        return False
-    n_ctx, d = c.shape
-    return (q.dtype == torch.float32 and c.dtype == torch.float32 and q.is_contiguous() and c.is_contiguous() and n_ctx % 8 == 0 and d % 8 == 0
-            and q.shape[1] == d and ctx_mask.is_contiguous() and ctx_mask.element_size() == 1 and pos_idx.dtype == torch.int64 and pos_idx.is_contiguous())
 
 
 def _stage_single(kn, q, c, m8, Qb, q_f32):
@@ -912,7 +900,7 @@ def _stage_single(kn, q, c, m8, Qb, q_f32):
     return Qb, Cb, colmask, Nc, Nc, c_direct, q_f32, False
 
 
-def _stage_multi(kn, caps, q, c, m8, Qb, q_f32, W, group, gather, wants_grad):
+def _stage_multi(kn, q, c, m8, Qb, q_f32, W, group, gather, wants_grad):
     """Several ranks.  ONE all-gather: context rows (bf16) + mask bytes in trailing rows of the same buffer; the trailing
     rows become always-masked extra columns (the reference issues 4 fp32 all_gathers, :169-176).  -> as _stage_single"""
     n_ctx, d = c.shape
@@ -927,7 +915,7 @@ def _stage_multi(kn, caps, q, c, m8, Qb, q_f32, W, group, gather, wants_grad):
         Cb = kn.empty((Nc, d), _BF16, c)
         D.all_gather_rows(send, Cb, group)
     # with a backward to follow, the one-call step reads the mask straight from the gathered buffer: no unpack launch
-    packed_step = q_f32 and wants_grad and (caps.train_step_packed_f32 or caps.inbatch_step_packed_f32)
+    packed_step = q_f32 and wants_grad
     colmask = None
     if not packed_step:
         colmask = kn.empty((Nc,), torch.uint8, c)
@@ -937,7 +925,7 @@ def _stage_multi(kn, caps, q, c, m8, Qb, q_f32, W, group, gather, wants_grad):
     return Qb, Cb, colmask, rows_c, Nc, False, q_f32, packed_step
 
 
-def _run_step(kn, caps, q, c32, Qb, Cb, colmask, Nc, q_f32, packed_step, pos_idx, W, r, n_ctx, inv_T, grad_scale, y_off, multi, wants_grad, dc_dtype, kernels):
+def _run_step(kn, q, c32, Qb, Cb, colmask, Nc, q_f32, packed_step, pos_idx, W, r, n_ctx, inv_T, grad_scale, y_off, multi, wants_grad, dc_dtype, kernels):
     """Choose the step's route and run it.  -> (bw, loss_sum, loss_is_mean, saved): the _Bwd with its kind, row_lse and that kind's own
     fields; the loss numerator (already the mean when loss_is_mean: the kernel multiplied it by 1 / Nq); the tensors for forward to save."""
     B, d = q.shape
@@ -948,10 +936,16 @@ def _run_step(kn, caps, q, c32, Qb, Cb, colmask, Nc, q_f32, packed_step, pos_idx
                                             else kn.inbatch_fwd(Qb, Cb, pos_idx, y_off, colmask, inv_T, grad_scale, want_logits=True))
         bw.kind, bw.gs = FP32G_DEBUG, grad_scale  # (forward adds the labels)
         return bw, loss_sum, False, (Qb, Cb, G)
-    used, bw.opx_packed = None, False
-    if multi and packed_step and caps.train_step_packed_f32:
-        # forward and backward of this rank's rows in ONE library call; gradients scaled by the grad_output the last backward saw
-        bw.used = used = _ExpectedGradScale.get(q.device, (B, Nc, d))
+    if not (q_f32 and wants_grad):
+        _, bw.row_lse, loss_sum, G, _ = (kn.inbatch_fwd_f32(q, c32, Qb, Cb, pos_idx, y_off, colmask, inv_T, grad_scale) if q_f32
+                                         else kn.inbatch_fwd(Qb, Cb, pos_idx, y_off, colmask, inv_T, grad_scale))
+        bw.kind = SAVED
+        return bw, loss_sum, False, (Qb, Cb, G)
+    # a backward will follow: forward and backward of this rank's rows in ONE library call (two launches at the BASELINE shapes), the
+    # gradients scaled by the grad_output the last backward saw; backward() only checks the grad_output it was given against that one
+    bw.used = used = _ExpectedGradScale.get(q.device, (B, Nc, d))
+    bw.opx_packed = False
+    if packed_step:
         if _OPX_PACKED and kernels is None and q.is_contiguous() and pos_idx.dtype == torch.int64 and pos_idx.is_contiguous() \
                 and dc_dtype in (torch.float32, _BF16):
             # host side in C++ (csrc/opx.cpp: packed_train_step): the allocations, the library call and its fall-back to fp32
@@ -971,25 +965,13 @@ def _run_step(kn, caps, q, c32, Qb, Cb, colmask, Nc, q_f32, packed_step, pos_idx
                     raise
                 _, bw.row_lse, loss_sum, G, dQ, dC_part = kn.train_step_packed_f32(q, Cb, Qb, W, r, n_ctx, pos_idx, inv_T, grad_scale, 1.0 / Nq,
                                                                                    used, torch.float32, defer_dq=True, want_G="auto")
-    elif multi and packed_step:  # (stand-in kernels of the CPU tests)
-        _, bw.row_lse, loss_sum, _, dQ, dC_part = kn.inbatch_step_packed_f32(q, Cb, Qb, W, r, n_ctx, pos_idx, inv_T, grad_scale)
-    elif q_f32 and wants_grad and caps.train_step_f32:
-        # a backward will follow: forward and backward in ONE library call (two launches at the BASELINE shapes);
-        # backward() only checks the grad_output it was given against the one the gradients were scaled by
-        bw.used = used = _ExpectedGradScale.get(q.device, (B, Nc, d))
+    else:
         _, bw.row_lse, loss_sum, G, dQ, dC_part = kn.train_step_f32(q, c32, Qb, Cb, pos_idx, y_off, colmask, inv_T, grad_scale, 1.0 / Nq, used,
                                                                     defer_dq=True, want_G="auto")
-    elif q_f32 and wants_grad and caps.inbatch_step_f32:  # (stand-in kernels of the CPU tests)
-        _, bw.row_lse, loss_sum, _, dQ, dC_part = kn.inbatch_step_f32(q, c32, Qb, Cb, pos_idx, y_off, colmask, inv_T, grad_scale)
-    else:
-        _, bw.row_lse, loss_sum, G, _ = (kn.inbatch_fwd_f32(q, c32, Qb, Cb, pos_idx, y_off, colmask, inv_T, grad_scale) if q_f32
-                                         else kn.inbatch_fwd(Qb, Cb, pos_idx, y_off, colmask, inv_T, grad_scale))
-        bw.kind = SAVED
-        return bw, loss_sum, False, (Qb, Cb, G)
-    bw.grads, bw.kind = (dQ, dC_part), (UNIT if used is None else PRESCALED)
-    if bw.kind is PRESCALED:  # (what REGEN will need; mask None: still packed in Cb)
-        bw.Qb, bw.Cb, bw.G, bw.pos_idx, bw.y_off, bw.mask, bw.inv_T, bw.grad_scale = Qb, Cb, G, pos_idx, y_off, colmask, inv_T, grad_scale
-    return bw, loss_sum, bw.kind is PRESCALED, None
+    bw.grads, bw.kind = (dQ, dC_part), PRESCALED
+    # (what REGEN will need; mask None: still packed in Cb)
+    bw.Qb, bw.Cb, bw.G, bw.pos_idx, bw.y_off, bw.mask, bw.inv_T, bw.grad_scale = Qb, Cb, G, pos_idx, y_off, colmask, inv_T, grad_scale
+    return bw, loss_sum, True, None
 
 
 def _regen_grads(kn, Qb, Cb, G, pos_idx, y_off, mask, inv_T, grad_scale, go, need_dq, need_dc, packed=None):
@@ -1006,15 +988,12 @@ def _regen_grads(kn, Qb, Cb, G, pos_idx, y_off, mask, inv_T, grad_scale, go, nee
 
 
 def _local_grads(ctx, st, go, need_dq, need_dc):
-    """This rank's gradients for every kind but the per-step ones (FAST and PRESCALED: in backward itself) -> (dQ, dC_part, the
-    grad_output still to apply (None: it is in them already))."""
+    """This rank's gradients, grad_output applied, for every kind but the per-step one (PRESCALED: in backward itself) -> (dQ, dC_part)."""
     kn, kind = st.kn, st.kind
     if kind is REGEN:
         dQ, dC_part, st.G = _regen_grads(kn, st.Qb, st.Cb, st.G, st.pos_idx, st.y_off, st.mask, st.inv_T, st.grad_scale, go, need_dq, need_dc,
                                          (st.W, st.n_ctx))
-        return dQ, dC_part, None
-    if kind is UNIT:  # computed in forward for grad_output = 1 (stand-in kernels); the caller applies the scale
-        return st.grads[0], st.grads[1], go
+        return dQ, dC_part
     Qb, Cb, G = ctx.saved_tensors
     if kind is FP32G_DEBUG:
         # fp32-G debug mode: G = (exp(S - lse) - onehot) * scale recomputed in fp32, split into a bf16 pair, two GEMM passes
@@ -1026,21 +1005,18 @@ def _local_grads(ctx, st, go, need_dq, need_dc):
         lo = (G32 - hi.float()).to(_BF16)
         dQ1, dC1 = kn.inbatch_bwd(hi, Qb, Cb, 1.0, go, need_dq, need_dc)
         dQ2, dC2 = kn.inbatch_bwd(lo, Qb, Cb, 1.0, go, need_dq, need_dc)
-        return (dQ1 + dQ2 if need_dq else None), (dC1 + dC2 if need_dc else None), None
-    dQ, dC_part = kn.inbatch_bwd(G, Qb, Cb, 1.0, go, need_dq, need_dc)
-    return dQ, dC_part, None
+        return (dQ1 + dQ2 if need_dq else None), (dC1 + dC2 if need_dc else None)
+    return kn.inbatch_bwd(G, Qb, Cb, 1.0, go, need_dq, need_dc)
 
 
-def _reduce_context_grads(st, dC_part, go, mine_ready):
-    """Several ranks: dc = this rank's rows of the sum over ranks of the dC partials, in the dtype c came in."""
+def _reduce_context_grads(st, dC_part, mine_ready):
+    """Several ranks: dc = this rank's rows of the sum over ranks of the dC partials (grad_output already in them), in the dtype c came in."""
     kn, group, n_ctx, d, c_dtype = st.kn, st.group, st.n_ctx, st.d, st.in_dtypes[1]
     wire = _dc_wire_dtype(group)
     mine = mine_ready if mine_ready is not None else kn.empty((st.rows_c, d), wire, dC_part)
-    if go is not None:
-        dC_part = dC_part * go  # scale before the collective: nothing is left to do after it
     if dC_part.dtype != wire:
         dC_part = dC_part.to(wire)  # half the bytes on the links (and in RCCL's reduction)
-    widen = wire != c_dtype and c_dtype == torch.float32 and st.can_widen
+    widen = wire != c_dtype and c_dtype == torch.float32
     if st.pending is not None and st.direct_ctx_grad and (wire == c_dtype or widen):
         # reduce-scatter on RCCL's stream; whoever consumes dc (defer_context_grad, after the query-tower backward has
         # been enqueued) waits for it -- and, on a half-width wire, widens the result into the fp32 gradient there.
@@ -1081,16 +1057,6 @@ class InBatchContrastive(torch.autograd.Function):
     def forward(ctx, q, c, pos_idx, ctx_mask, temperature, group, kernels, gather=None, pending=None):
         wants_grad = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
         inv_T = 1.0 / float(temperature)
-        if _OPX is not None and kernels is None and gather is None and _opx_step_eligible(q, c, pos_idx, ctx_mask, group, kernels, wants_grad):
-            B, (n_ctx, d) = q.shape[0], c.shape
-            ctx.state = bw = _Bwd()
-            bw.kind, bw.fast, bw.site, bw.pos_idx, bw.y_off = FAST, True, (B, n_ctx, d), pos_idx, 0
-            bw.mask, bw.inv_T, bw.grad_scale = ctx_mask, inv_T, inv_T / B
-            bw.used = used = _ExpectedGradScale.get(q.device, bw.site)
-            loss_out, bw.row_lse, dQ, dC, bw.Qb, bw.Cb, bw.G, part = _OPX.train_step(q, c, pos_idx, ctx_mask, inv_T, inv_T / B, 1.0 / B, used,
-                                                                                     default_kernels()._lib.options_epoch())
-            bw.grads = (dQ, dC, part)
-            return loss_out[0]
         kn = kernels if kernels is not None else default_kernels()
         W, r = (1, 0) if group is False else D.world(group)  # group=False: single-device strategy, never gather
         B, d = q.shape
@@ -1099,17 +1065,16 @@ class InBatchContrastive(torch.autograd.Function):
         assert pos_idx.shape[0] == B and ctx_mask.shape[0] == n_ctx
         if d % 8 != 0:
             raise ValueError(f"hidden size {d} must be a multiple of 8")
-        caps = _HIP_CAPS if type(kn) is HipKernels else _Caps(*[hasattr(kn, n) for n in _Caps._fields])
         multi = W > 1 or (group is not False and D.force_dist())  # (forced: the multi-rank code path on a one-rank world, for timelines)
         m8 = _mask_u8(ctx_mask)
-        q_f32 = q.dtype == torch.float32 and caps.inbatch_fwd_f32
+        q_f32 = q.dtype == torch.float32
         Qb = kn.empty((B, d), _BF16, q)
         Qb, Cb, colmask, rows_c, Nc, c_direct, q_f32, packed_step = (
-            _stage_multi(kn, caps, q, c, m8, Qb, q_f32, W, group, gather, wants_grad) if multi else _stage_single(kn, q, c, m8, Qb, q_f32))
+            _stage_multi(kn, q, c, m8, Qb, q_f32, W, group, gather, wants_grad) if multi else _stage_single(kn, q, c, m8, Qb, q_f32))
         grad_scale = inv_T / Nq  # d loss / d S of the global mean, before grad_output
         y_off = r * rows_c       # dpr_task.py:189-190 (label offset of this rank's columns)
         dc_dtype = _dc_wire_dtype(group) if multi else torch.float32
-        bw, loss_sum, loss_is_mean, saved = _run_step(kn, caps, q, c if c_direct else None, Qb, Cb, colmask, Nc, q_f32, packed_step, pos_idx, W, r,
+        bw, loss_sum, loss_is_mean, saved = _run_step(kn, q, c if c_direct else None, Qb, Cb, colmask, Nc, q_f32, packed_step, pos_idx, W, r,
                                                       n_ctx, inv_T, grad_scale, y_off, multi, wants_grad, dc_dtype, kernels)
         loss_sum = loss_sum[:1]
         if multi:
@@ -1120,28 +1085,15 @@ class InBatchContrastive(torch.autograd.Function):
         if bw.kind is FP32G_DEBUG:
             bw.labels = pos_idx + y_off
         ctx.state = bw
-        bw.fast, bw.kn, bw.group, bw.W, bw.n_ctx, bw.rows_c, bw.d, bw.site, bw.multi = False, kn, group, W, n_ctx, rows_c, d, (B, Nc, d), multi
+        bw.kn, bw.group, bw.W, bw.n_ctx, bw.rows_c, bw.d, bw.site, bw.multi = kn, group, W, n_ctx, rows_c, d, (B, Nc, d), multi
         # direct_ctx_grad: c came straight from defer_context_grad (the task's own flow)
-        bw.direct_ctx_grad, bw.in_dtypes, bw.pending, bw.can_widen = gather is not None, (q.dtype, c.dtype), pending if multi else None, caps.widen
+        bw.direct_ctx_grad, bw.in_dtypes, bw.pending = gather is not None, (q.dtype, c.dtype), pending if multi else None
         return loss
 
     @staticmethod
     def backward(ctx, grad_out):
         st = ctx.state
         need_dq, need_dc = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if st.fast:  # FAST, or the REGEN it has turned into: fp32 in and out on one rank, nothing to slice, cast or reduce
-            go = grad_out if (grad_out.dtype == torch.float32 and grad_out.is_contiguous()) else grad_out.detach().float().contiguous()
-            if st.kind is FAST:
-                # computed in forward for grad_output = *used: ONE launch compares and only rescales when the scale really changed; the
-                # tensors are handed to autograd and forgotten (see PRESCALED below)
-                dQ, dC, part = st.grads
-                used, st.kind, st.grads, st.used = st.used, REGEN, None, None
-                _, nxt = _OPX.rescale(dQ, part, dC, go, used, need_dq, need_dc)
-                _ExpectedGradScale.publish(go.device, nxt, st.site)
-            else:
-                dQ, dC, st.G = _regen_grads(default_kernels(), st.Qb, st.Cb, st.G, st.pos_idx, 0, st.mask, st.inv_T, st.grad_scale, go.reshape(1),
-                                            need_dq, need_dc)
-            return (dQ if need_dq else None), (dC if need_dc else None), None, None, None, None, None, None, None
         go = grad_out.detach().reshape(1).float().contiguous()  # device scalar: AMP loss scale, no host sync
         mine_ready = None  # (the reduce-scatter's receive buffer, where csrc/opx.cpp has made it already)
         if st.kind is PRESCALED:
@@ -1150,7 +1102,7 @@ class InBatchContrastive(torch.autograd.Function):
             # .grad itself, and clones it otherwise (one copy launch per step, 50 MB of traffic at cfg3 per rank).
             dQs, dC_part = st.grads
             dQ, part = dQs if isinstance(dQs, tuple) else (dQs, None)  # (dQ buffer, split-K slabs: the rescale adds them up into the buffer)
-            if st.opx_packed and st.multi:
+            if st.opx_packed:
                 # csrc/opx.cpp: the rescale launch, dC_part in the wire format (one cast launch where the step wrote fp32 for a bf16 wire)
                 # and the reduce-scatter's receive buffer, in one C++ call
                 nxt, dC_part, mine_ready = _OPX.packed_backward(dQ, part, dC_part, go, st.used, 0 if _dc_wire_dtype(st.group) == _BF16 else 2,
@@ -1159,17 +1111,15 @@ class InBatchContrastive(torch.autograd.Function):
                 nxt = st.kn.rescale_grads(dQs if need_dq else None, dC_part if need_dc else None, go, st.used)[1:2]
             st.kind, st.grads, st.used = REGEN, None, None
             _ExpectedGradScale.publish(go.device, nxt, st.site)
-            go = None
         else:
-            dQ, dC_part, go = _local_grads(ctx, st, go, need_dq, need_dc)
+            dQ, dC_part = _local_grads(ctx, st, go, need_dq, need_dc)
         dq = dc = None
         if need_dq:
-            dq = (dQ if go is None else dQ * go).to(st.in_dtypes[0])
+            dq = dQ.to(st.in_dtypes[0])
         if need_dc and st.multi:
-            dc = _reduce_context_grads(st, dC_part, go, mine_ready)
+            dc = _reduce_context_grads(st, dC_part, mine_ready)
         elif need_dc:
-            dc = dC_part[:st.n_ctx]
-            dc = (dc if go is None else dc * go).to(st.in_dtypes[1])
+            dc = dC_part[:st.n_ctx].to(st.in_dtypes[1])
         return dq, dc, None, None, None, None, None, None, None
 
 
@@ -1187,7 +1137,7 @@ def _opx_regen(Qb, Cb, G, pos_idx, mask, inv_T, grad_scale, go, need_dq, need_dc
     return _regen_grads(default_kernels(), Qb, Cb, G, pos_idx, 0, mask, inv_T, grad_scale, go.reshape(1), need_dq, need_dc)
 
 
-_OPX_NODE = _OPX is not None and hasattr(_OPX, "inbatch_loss") and os.environ.get("DPRHOT_OPX_NODE", "1") != "0"
+_OPX_NODE = _OPX is not None and os.environ.get("DPRHOT_OPX_NODE", "1") != "0"
 if _OPX_NODE:
     _OPX.set_regen(_opx_regen)
 
@@ -1196,7 +1146,7 @@ def inbatch_contrastive_loss(q, c, pos_idx, ctx_mask, temperature=1.0, group=Non
     if gather is None:
         if _OPX_NODE and _plain_single_rank(q, group, kernels):
             # the plain single-rank fp32 step: a C++ autograd node (csrc/opx.cpp), no Python frame in forward or backward
-            # (DPRHOT_OPX_NODE=0: InBatchContrastive's own fast path, the same two library calls from Python)
+            # (DPRHOT_OPX_NODE=0: InBatchContrastive on HipKernels' wrappers, the same two library calls from Python)
             loss = _OPX.inbatch_loss(q, c, pos_idx, ctx_mask, 1.0 / float(temperature), default_kernels()._lib.options_epoch())
             if loss is not None:
                 return loss
@@ -1378,11 +1328,7 @@ def rank_and_loss(q, c, labels, colmask=None, inv_T=1.0, kernels=None):
         Cb[Nc:].zero_()
         m8[Nc:] = 1
     y = torch.as_tensor(labels, dtype=torch.long, device=q.device)
-    if hasattr(kn, "sim_rank_loss"):  # ONE pass of the Nq x Nc GEMM: count and softmax statistics in the same epilogue
-        ranks, loss_sum = kn.sim_rank_loss(Qb, Cb, y, m8, inv_T)
-    else:
-        ranks = kn.sim_rank(Qb, Cb, y, m8, inv_T)
-        _, _, loss_sum, _, _ = kn.inbatch_fwd(Qb, Cb, y, 0, m8, inv_T, 1.0, want_logits=False, want_G=False)
+    ranks, loss_sum = kn.sim_rank_loss(Qb, Cb, y, m8, inv_T)  # ONE pass of the Nq x Nc GEMM: count and softmax statistics in the same epilogue
     return ranks, (loss_sum / q.shape[0]).reshape(())
 
 
@@ -1442,38 +1388,10 @@ class CorpusSearch:
 
     def _fold_wide(self, S, cols, col_offset):
         """k beyond 4096: the library's HBM-resident selection (dprhot_topk_update_wide, csrc/wideselect.h: exact radix select over
-        state + chunk, ties at the k-th score resolved by passage id, then only the k winners are sorted).  _fold_rows_torch below is
-        the path of the stand-in kernels only."""
-        if self.wide_ws is None and hasattr(self.kn, "topk_update_wide"):
+        state + chunk, ties at the k-th score resolved by passage id, then only the k winners are sorted)."""
+        if self.wide_ws is None:
             self.wide_ws = self.kn.topk_wide_workspace(self.values.shape[0], self.k, S)
-        if self.wide_ws is not None:
-            return self.kn.topk_update_wide(S, cols, col_offset, self.values, self.indices, self.first, self.wide_ws)
-        if self.first:
-            self.values.fill_(float("-inf"))
-            self.indices.fill_(-1)
-        self._fold_rows_torch(None, S[:, :cols], col_offset)
-
-    def _fold_rows_torch(self, rows, S, first_col):
-        """Exact fold of one chunk into the state of `rows` (None: all) with torch's stable sorts, in the same total order (score desc,
-        id asc): the library's escape for degenerate rows, and the whole path for stand-in kernels.  A NaN score is never selected
-        (include/dprhot.h): it enters as an unfilled slot (-inf / -1), which ranks behind every real candidate."""
-        sel = slice(None) if rows is None else rows
-        S = S[sel]
-        vals, idx = self.values[sel], self.indices[sel]
-        cols = S.shape[1]
-        kk = min(self.k, cols)
-        nan = torch.isnan(S)
-        S = S.masked_fill(nan, float("-inf"))
-        order = torch.sort(S, dim=1, descending=True, stable=True).indices  # ties: lower column first
-        order = torch.gather(order, 1, torch.sort(torch.gather(nan, 1, order).to(torch.uint8), dim=1, stable=True).indices)[:, :kk]  # NaN last
-        v = torch.gather(S, 1, order)
-        ids = torch.where(torch.gather(nan, 1, order), torch.full_like(order, -1), order + first_col)
-        allv, alli = torch.cat([vals, v], 1), torch.cat([idx, ids], 1)
-        alli_key = torch.where(alli < 0, torch.full_like(alli, torch.iinfo(torch.int64).max), alli)  # empty slots last
-        o1 = torch.sort(alli_key, dim=1, stable=True).indices
-        allv, alli = torch.gather(allv, 1, o1), torch.gather(alli, 1, o1)
-        o2 = torch.sort(allv, dim=1, descending=True, stable=True).indices[:, :self.k]
-        self.values[sel], self.indices[sel] = torch.gather(allv, 1, o2), torch.gather(alli, 1, o2)
+        self.kn.topk_update_wide(S, cols, col_offset, self.values, self.indices, self.first, self.wide_ws)
 
     def add(self, corpus_embs, first_id=0):
         n, d = corpus_embs.shape
@@ -1483,8 +1401,7 @@ class CorpusSearch:
             Cb = self.kn.empty((n, d), _BF16, corpus_embs)
             self.kn.cast_bf16(corpus_embs, Cb)
         if self.wide_k:
-            native = self.k <= self.KWIDE and hasattr(self.kn, "topk_update")
-            return self._add_chunks(Cb, first_id, self._fold_native if native else self._fold_wide)
+            return self._add_chunks(Cb, first_id, self._fold_native if self.k <= self.KWIDE else self._fold_wide)
         n8 = n // 8 * 8
         if n8:
             self.kn.search(self.Qb, Cb[:n8], first_id, self.values, self.indices, self.first, self.chunk, self.ws)
@@ -1497,7 +1414,7 @@ class CorpusSearch:
             self.first = False
 
     def result(self):
-        if self.wide_ws is not None and hasattr(self.kn, "topk_wide_errors"):
+        if self.wide_ws is not None:
             err = self.kn.topk_wide_errors(self.wide_ws, self.values.shape[0])
             if bool(err.any()):  # (one sync, where the caller is about to read the result anyway; no condition sets the word today)
                 raise RuntimeError("dprhot_topk_update_wide reported rows it could not update: " + str(torch.nonzero(err).flatten().tolist()[:8]))

@@ -1,6 +1,9 @@
 """TEST-ONLY stand-in for dpr_scale_amd.hotpath.HipKernels, built on the numpy oracle, so that the CPU suite
 can run the *distributed orchestration* of InBatchContrastive on gloo (gather layout, label offsets,
-reduce-scatter, loss all-reduce).  It lives under tests/ and is never importable from the product."""
+reduce-scatter, loss all-reduce).  It lives under tests/ and is never importable from the product.
+
+The product never asks a kernel set what it offers: every entry point the operator, CorpusSearch and rank_and_loss call on
+HipKernels exists here too, with HipKernels' return conventions, so the CPU suite takes the routes production takes."""
 import numpy as np
 import torch
 
@@ -13,6 +16,9 @@ def _np(t):
 
 class OracleKernels:
     name = "oracle-test-standin"
+    # what the library's plan decides per shape, here per test: the train step keeps its dScores under want_G="auto", leaves dQ as
+    # split-K slabs under defer_dq, has an epilogue for bf16 dC partials
+    keep_G, slabs, bf16_dc = True, False, True
 
     def empty(self, shape, dtype, like):
         return torch.empty(shape, dtype=dtype, device=like.device)
@@ -92,6 +98,52 @@ class OracleKernels:
         dQ, dC = self.inbatch_bwd(G, Qb, Cb, 1.0, None)
         return row_loss, lse, loss_sum, G, dQ, dC
 
+    # ---- the operator's step: forward and backward in one call, gradients scaled by the DEVICE scalar d_scale ----
+    def _train(self, q, c, Qb, Cb, y, y_offset, colmask, inv_T, grad_scale, loss_scale, d_scale, dc_dtype, defer_dq, want_G):
+        if dc_dtype != torch.float32 and not self.bf16_dc:
+            raise RuntimeError("train step: this plan has no epilogue for dc_kind 0")
+        row_loss, lse, loss_sum, G, _ = self.inbatch_fwd_f32(q, c, Qb, Cb, y, y_offset, colmask, inv_T, grad_scale)
+        dQ, dC = self.inbatch_bwd(G, Qb, Cb, 1.0, d_scale)
+        loss_out = torch.stack([loss_sum[0] * loss_scale, loss_sum[0]])
+        if defer_dq and self.slabs:  # split-K partial sums, added up by rescale_grads
+            dQ = (torch.empty_like(dQ), torch.stack([dQ * 0.25, dQ * 0.75]))
+        keep = want_G is True or (want_G == "auto" and self.keep_G)
+        return row_loss, lse, loss_out, (G if keep else None), dQ, dC.to(dc_dtype)
+
+    def train_step_f32(self, q, c, Qb, Cb, y, y_offset, colmask, inv_T, grad_scale, loss_scale, d_scale, dc_dtype=torch.float32,
+                       defer_dq=False, want_G=True):
+        return self._train(q, c, Qb, Cb, y, y_offset, colmask, inv_T, grad_scale, loss_scale, d_scale, dc_dtype, defer_dq, want_G)
+
+    def _packed_mask(self, gathered, W, n_ctx):
+        colmask = torch.empty(gathered.shape[0], dtype=torch.uint8)
+        self.unpack_mask(gathered, W, n_ctx, colmask)
+        return colmask
+
+    def train_step_packed_f32(self, q, gathered, Qb, W, rank, n_ctx, y, inv_T, grad_scale, loss_scale, d_scale, dc_dtype=torch.float32,
+                              defer_dq=False, want_G=True):
+        y_off = rank * self.packed_rows(n_ctx, gathered.shape[1])
+        return self._train(q, None, Qb, gathered, y, y_off, self._packed_mask(gathered, W, n_ctx), inv_T, grad_scale, loss_scale, d_scale,
+                           dc_dtype, defer_dq, want_G)
+
+    def inbatch_step_packed_f32(self, q, gathered, Qb, W, rank, n_ctx, y, inv_T, grad_scale, want_G=True):
+        y_off = rank * self.packed_rows(n_ctx, gathered.shape[1])
+        return self.inbatch_step_f32(q, None, Qb, gathered, y, y_off, self._packed_mask(gathered, W, n_ctx), inv_T, grad_scale)
+
+    def rescale_grads(self, dQ, dC, go, used):
+        s = float(go.item()) / float(used.item())
+        part = None
+        if isinstance(dQ, tuple):
+            dQ, part = dQ
+        if dQ is not None:
+            dQ.copy_((part.sum(0) if part is not None else dQ) * s)
+        if dC is not None:
+            dC.copy_((dC.float() * s).to(dC.dtype))
+        return torch.stack([go[0], go[0]]).float()
+
+    def widen(self, src, dst):
+        dst.copy_(src.reshape(-1)[:dst.numel()].view_as(dst).float())
+        return dst
+
     # ---- forward-only / piecewise ops (eval path, windowed branch) ----
     def sim(self, Qb, Cb, colmask=None, inv_T=1.0):
         m = None if colmask is None else colmask.numpy().astype(bool)
@@ -114,6 +166,11 @@ class OracleKernels:
     def rank_of_gold(self, S, y, y_offset=0):
         return torch.from_numpy(O.rank_of_gold(S.numpy(), y.numpy() + y_offset))
 
+    def sim_rank_loss(self, Qb, Cb, y, colmask=None, inv_T=1.0, y_offset=0):
+        m = torch.zeros(Cb.shape[0], dtype=torch.uint8) if colmask is None else colmask
+        _, _, loss_sum, _, S = self.inbatch_fwd(Qb, Cb, y, y_offset, m, inv_T, 1.0, want_logits=True, want_G=False)
+        return self.rank_of_gold(S, y, y_offset), loss_sum
+
     def topk(self, S, k):
         v, i = O.topk_stable(S.numpy(), k)
         return torch.from_numpy(v), torch.from_numpy(i)
@@ -123,6 +180,18 @@ class OracleKernels:
                             values.shape[1])
         values.copy_(torch.from_numpy(v))
         indices.copy_(torch.from_numpy(i))
+
+    # any k: the same merge (score descending then id ascending, NaN never selected, unfilled slots -inf / -1).  The workspace is one
+    # 32-byte record per row as the library's begins; all this stand-in keeps there is the error word (int32 word 5), always zero
+    def topk_wide_workspace(self, rows, k, like):
+        return torch.zeros(rows * 32, dtype=torch.uint8)
+
+    def topk_update_wide(self, S, cols, col_offset, values, indices, first, ws):
+        self.topk_update(S, cols, col_offset, values, indices, first)
+
+    @staticmethod
+    def topk_wide_errors(ws, rows):
+        return ws[: rows * 32].view(torch.int32).view(rows, 8)[:, 5]
 
     def search_workspace(self, nq, chunk, like):
         return torch.empty(0, dtype=torch.uint8)

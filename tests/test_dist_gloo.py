@@ -13,6 +13,17 @@ import torch.multiprocessing as mp
 from conftest import ROOT, load_golden
 
 
+class _Calls:
+    """The names of the kernel-set entry points the operator reaches for."""
+
+    def __init__(self, inner):
+        self._inner, self.names = inner, set()
+
+    def __getattr__(self, name):
+        self.names.add(name)
+        return getattr(self._inner, name)
+
+
 def _worker(rank, W, port, meta, q, overlapped=False):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -27,7 +38,7 @@ def _worker(rank, W, port, meta, q, overlapped=False):
     qv, cv, y, m = synth_embeddings(meta["seed"] + rank, meta["B"], meta["K"], meta["d"], meta["dist"], meta["ragged"])
     tq = torch.from_numpy(qv).requires_grad_(True)
     tc = torch.from_numpy(cv).requires_grad_(True)
-    kn = OracleKernels()
+    kn = _Calls(OracleKernels())
     if overlapped:
         # the order DenseRetrieverTask.training_step uses on several GPUs: context rows first, gather in flight under the
         # "query tower" (here an identity op that stands for it), reduce-scatter waited for by the deferred-grad node
@@ -39,7 +50,7 @@ def _worker(rank, W, port, meta, q, overlapped=False):
     else:
         loss = inbatch_contrastive_loss(tq, tc, torch.from_numpy(y), torch.from_numpy(m), meta["T"], None, kn)
     (loss * 3.0).backward()  # grad_output != 1 exercises the device-scalar path
-    q.put((rank, loss.item(), tq.grad.numpy() / 3.0, tc.grad.numpy() / 3.0))
+    q.put((rank, loss.item(), tq.grad.numpy() / 3.0, tc.grad.numpy() / 3.0, sorted(kn.names)))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -66,7 +77,10 @@ def test_ddp_branch_matches_reference(name, port, overlapped, monkeypatch):
     res = sorted([q.get(timeout=90) for _ in range(W)], key=lambda t: t[0])
     for p in procs:
         p.join(timeout=60)
-    for r, loss, dq, dc in res:
+    # the route production takes under DDP: the one-call step on the packed buffer (mask read in place), gradients fixed up in backward
+    calls = res[0][4]
+    assert "train_step_packed_f32" in calls and "rescale_grads" in calls and "unpack_mask" not in calls, calls
+    for r, loss, dq, dc, _ in res:
         assert abs(loss - g["loss_per_rank"][r]) <= 1e-3 * max(1.0, abs(g["loss_per_rank"][r]))
         # G travels as bf16 (2^-9 relative rounding per element), hence the 1e-2-of-max bar on gradients
         assert np.abs(dq - g["dq_per_rank"][r]).max() <= 1e-2 * np.abs(g["dq_per_rank"][r]).max()

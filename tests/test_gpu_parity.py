@@ -1564,28 +1564,34 @@ def test_cpp_autograd_node_equals_the_python_operator(dev):
     grad_output, and for a second backward through a retained graph."""
     from dpr_scale_amd import hotpath
 
+    from dpr_scale_amd import _lib
+
     if not getattr(hotpath, "_OPX_NODE", False):
         pytest.skip("the optional host extension _opx.so is not built")
-    meta, g = load_golden("cfg2_Ur_T0.05")
-    q, c, y, m = rank_inputs(meta)[0]
-    ty, tm = t(y, dev), t(m, dev)
+    for name in ("cfg1_Ur_T1", "cfg2_Ur_T0.05"):
+        meta, g = load_golden(name)
+        q, c, y, m = rank_inputs(meta)[0]
+        ty, tm = t(y, dev), t(m, dev)
+        shape = (q.shape[0], c.shape[0], q.shape[1])
+        # (for the record: whether this shape's plan leaves split-K slabs of dQ to the rescale, and whether it materialises the dScores)
+        print(f"{name} {shape}: train_dq_slabs={_lib.train_dq_slabs(*shape)} step_wants_g={_lib.step_wants_g(*shape)}")
 
-    def run(fn, scale, twice=False):
-        tq, tc = t(q, dev).requires_grad_(True), t(c, dev).requires_grad_(True)
-        loss = fn(tq, tc)
-        assert loss.grad_fn is not None
-        (loss * scale).backward(retain_graph=twice)
-        if twice:
-            (loss * 3.0).backward()
-        return loss.detach().clone(), tq.grad.clone(), tc.grad.clone()
+        def run(fn, scale, twice=False):
+            tq, tc = t(q, dev).requires_grad_(True), t(c, dev).requires_grad_(True)
+            loss = fn(tq, tc)
+            assert loss.grad_fn is not None
+            (loss * scale).backward(retain_graph=twice)
+            if twice:
+                (loss * 3.0).backward()
+            return loss.detach().clone(), tq.grad.clone(), tc.grad.clone()
 
-    cpp = lambda tq, tc: hotpath.inbatch_contrastive_loss(tq, tc, ty, tm, meta["T"])  # noqa: E731
-    py = lambda tq, tc: hotpath.InBatchContrastive.apply(tq, tc, ty, tm, meta["T"], None, None, None, None)  # noqa: E731
-    for scale, twice in ((1.0, False), (1024.0, False), (1024.0, False), (2.0, True), (1.0, False)):
-        a, b = run(cpp, scale, twice), run(py, scale, twice)
-        assert "InBatchFn" in cpp(t(q, dev).requires_grad_(True), t(c, dev)).grad_fn.name()
-        for x, z in zip(a, b):
-            assert torch.equal(x, z), (scale, twice)
+        cpp = lambda tq, tc: hotpath.inbatch_contrastive_loss(tq, tc, ty, tm, meta["T"])  # noqa: E731
+        py = lambda tq, tc: hotpath.InBatchContrastive.apply(tq, tc, ty, tm, meta["T"], None, None, None, None)  # noqa: E731
+        for scale, twice in ((1.0, False), (1024.0, False), (1024.0, False), (2.0, True), (1.0, False)):
+            a, b = run(cpp, scale, twice), run(py, scale, twice)
+            assert "InBatchFn" in cpp(t(q, dev).requires_grad_(True), t(c, dev)).grad_fn.name()
+            for x, z in zip(a, b):
+                assert torch.equal(x, z), (name, scale, twice)
     # no gradient wanted: the node is not taken (forward only, the general path)
     with torch.no_grad():
         loss = hotpath.inbatch_contrastive_loss(t(q, dev), t(c, dev), ty, tm, meta["T"])

@@ -2,8 +2,8 @@
 of kernel-set calls (name, tensor shapes and dtypes, scalars), the loss and the gradients against the numpy oracle, and -- for the
 routes whose gradients are computed in forward -- that the operator lets go of the gradient tensors it hands to autograd.
 
-The kernel set is tests/_oracle_kernels.OracleKernels (plus CPU forms of the train-step entry points) behind a recorder.  The
-multi-rank code path runs on a one-rank gloo world through dist.force_dist."""
+The kernel set is tests/_oracle_kernels.OracleKernels behind a recorder; a case sets what the library's plan would decide for its
+shape (keep_G, slabs, bf16_dc) on the instance.  The multi-rank code path runs on a one-rank gloo world through dist.force_dist."""
 import gc
 import os
 import sys
@@ -41,16 +41,16 @@ def _enc(a):
 
 
 class Recorder:
-    """Logs every kn.* call of the operator; `hide` removes entry points (detection is by attribute)."""
+    """Logs every kn.* call of the operator."""
 
     name = "recorder"
 
-    def __init__(self, inner, hide=()):
-        self._inner, self._hide, self.log = inner, frozenset(hide), []
+    def __init__(self, inner):
+        self._inner, self.log = inner, []
         self.handed = {}  # what the last train step returned: data pointers and weak references, never the tensors
 
     def __getattr__(self, name):
-        if name.startswith("_") or name in self._hide:
+        if name.startswith("_"):
             raise AttributeError(name)
         f = getattr(self._inner, name)
         if not callable(f):
@@ -68,75 +68,19 @@ class Recorder:
         return call
 
 
-class StepKernels(OracleKernels):
-    """OracleKernels plus CPU forms of the entry points only HipKernels has, with HipKernels' return conventions."""
-
-    def __init__(self, keep_G=True, slabs=False, bf16_dc=True):
-        self.keep_G, self.slabs, self.bf16_dc = keep_G, slabs, bf16_dc
-
-    def _train(self, q, c, Qb, Cb, y, y_offset, colmask, inv_T, grad_scale, loss_scale, d_scale, dc_dtype, defer_dq, want_G):
-        if dc_dtype != torch.float32 and not self.bf16_dc:
-            raise RuntimeError("train step: this plan has no epilogue for dc_kind 0")
-        row_loss, lse, loss_sum, G, _ = self.inbatch_fwd_f32(q, c, Qb, Cb, y, y_offset, colmask, inv_T, grad_scale)
-        dQ, dC = self.inbatch_bwd(G, Qb, Cb, 1.0, d_scale)
-        loss_out = torch.stack([loss_sum[0] * loss_scale, loss_sum[0]])
-        if defer_dq and self.slabs:  # split-K partial sums, added up by rescale_grads
-            dQ = (torch.empty_like(dQ), torch.stack([dQ * 0.25, dQ * 0.75]))
-        keep = want_G is True or (want_G == "auto" and self.keep_G)
-        return row_loss, lse, loss_out, (G if keep else None), dQ, dC.to(dc_dtype)
-
-    def train_step_f32(self, q, c, Qb, Cb, y, y_offset, colmask, inv_T, grad_scale, loss_scale, d_scale, dc_dtype=torch.float32,
-                       defer_dq=False, want_G=True):
-        return self._train(q, c, Qb, Cb, y, y_offset, colmask, inv_T, grad_scale, loss_scale, d_scale, dc_dtype, defer_dq, want_G)
-
-    def _packed_mask(self, gathered, W, n_ctx):
-        colmask = torch.empty(gathered.shape[0], dtype=torch.uint8)
-        self.unpack_mask(gathered, W, n_ctx, colmask)
-        return colmask
-
-    def train_step_packed_f32(self, q, gathered, Qb, W, rank, n_ctx, y, inv_T, grad_scale, loss_scale, d_scale, dc_dtype=torch.float32,
-                              defer_dq=False, want_G=True):
-        y_off = rank * self.packed_rows(n_ctx, gathered.shape[1])
-        return self._train(q, None, Qb, gathered, y, y_off, self._packed_mask(gathered, W, n_ctx), inv_T, grad_scale, loss_scale, d_scale,
-                           dc_dtype, defer_dq, want_G)
-
-    def inbatch_step_packed_f32(self, q, gathered, Qb, W, rank, n_ctx, y, inv_T, grad_scale, want_G=True):
-        y_off = rank * self.packed_rows(n_ctx, gathered.shape[1])
-        return self.inbatch_step_f32(q, None, Qb, gathered, y, y_off, self._packed_mask(gathered, W, n_ctx), inv_T, grad_scale)
-
-    def rescale_grads(self, dQ, dC, go, used):
-        s = float(go.item()) / float(used.item())
-        part = None
-        if isinstance(dQ, tuple):
-            dQ, part = dQ
-        if dQ is not None:
-            dQ.copy_((part.sum(0) if part is not None else dQ) * s)
-        if dC is not None:
-            dC.copy_((dC.float() * s).to(dC.dtype))
-        return torch.stack([go[0], go[0]]).float()
-
-    def widen(self, src, dst):
-        dst.copy_(src.reshape(-1)[:dst.numel()].view_as(dst).float())
-        return dst
-
-
 # ---- the cases -------------------------------------------------------------------------------------------------------------------
-# name -> dict(kn: kernel set, hide: entry points taken away, B / K: shape (d = 16), dtype: of q and c, env: variables set,
+# name -> dict(kn: the plan attributes of the kernel set, B / K: shape (d = 16), dtype: of q and c, env: variables set,
 #              multi: the multi-rank path on a one-rank world, overlap: ContextGather + defer_context_grad, grads: backward runs)
-_TRAIN_ONLY = ("train_step_f32", "train_step_packed_f32", "rescale_grads")
 CASES = {
     "single_bf16": dict(dtype=torch.bfloat16),
     "single_fp16": dict(dtype=torch.float16),
-    "single_fwd_f32_only": dict(hide=_TRAIN_ONLY + ("inbatch_step_f32",)),
-    "single_step_f32": dict(hide=_TRAIN_ONLY),
+    "single_no_grad": dict(grads=False),
     "single_train_step_G": dict(kn=dict(keep_G=True)),
     "single_train_step_noG": dict(kn=dict(keep_G=False)),
     "single_train_step_slabs_noG": dict(kn=dict(keep_G=False, slabs=True)),
     "single_padded": dict(B=3),
     "single_fp32g_debug": dict(env={"DPRHOT_FP32_G": "1"}),
     "single_fp32g_debug_bf16": dict(env={"DPRHOT_FP32_G": "1"}, dtype=torch.bfloat16),
-    "multi_step_packed": dict(multi=True, hide=_TRAIN_ONLY, env={"DPRHOT_DC_WIRE": "fp32"}),
-    "multi_step_packed_overlap": dict(multi=True, overlap=True, hide=_TRAIN_ONLY, env={"DPRHOT_DC_WIRE": "fp32"}),
     "multi_train_fp32wire_G": dict(multi=True, kn=dict(keep_G=True), env={"DPRHOT_DC_WIRE": "fp32"}),
     "multi_train_fp32wire_noG": dict(multi=True, kn=dict(keep_G=False, slabs=True), env={"DPRHOT_DC_WIRE": "fp32"}),
     "multi_train_fp32wire_noG_overlap": dict(multi=True, overlap=True, kn=dict(keep_G=False), env={"DPRHOT_DC_WIRE": "fp32"}),
@@ -145,9 +89,6 @@ CASES = {
     "multi_train_bf16wire_fallback_noG": dict(multi=True, kn=dict(keep_G=False, bf16_dc=False), env={"DPRHOT_DC_WIRE": "bf16"}),
     "multi_train_bf16wire_fallback_G_overlap": dict(multi=True, overlap=True, kn=dict(keep_G=True, bf16_dc=False),
                                                     env={"DPRHOT_DC_WIRE": "bf16"}),
-    "multi_train_bf16wire_no_widen": dict(multi=True, hide=("widen",), kn=dict(keep_G=True), env={"DPRHOT_DC_WIRE": "bf16"}),
-    "multi_train_bf16wire_no_widen_overlap": dict(multi=True, overlap=True, hide=("widen",), kn=dict(keep_G=True),
-                                                  env={"DPRHOT_DC_WIRE": "bf16"}),
     "multi_bf16_inputs": dict(multi=True, dtype=torch.bfloat16, env={"DPRHOT_DC_WIRE": "fp32"}),
     "multi_no_grad": dict(multi=True, grads=False, env={"DPRHOT_DC_WIRE": "fp32"}),
     "multi_no_grad_overlap": dict(multi=True, overlap=True, grads=False, env={"DPRHOT_DC_WIRE": "fp32"}),
@@ -176,21 +117,10 @@ EXPECTED = {
         "-- second backward",
         "inbatch_bwd(bf16[4, 8], bf16[4, 16], bf16[8, 16], 1, f32[1], True, True)",
     ],
-    "single_fwd_f32_only": [
+    "single_no_grad": [
         "empty((4, 16), bf16, f32[4, 16])",
         "empty((8, 16), bf16, f32[8, 16])",
         "inbatch_fwd_f32(f32[4, 16], f32[8, 16], bf16[4, 16], bf16[8, 16], i64[4], 0, u8[8], 1, 0.25)",
-        "-- backward",
-        "inbatch_bwd(bf16[4, 8], bf16[4, 16], bf16[8, 16], 1, f32[1], True, True)",
-        "-- second backward",
-        "inbatch_bwd(bf16[4, 8], bf16[4, 16], bf16[8, 16], 1, f32[1], True, True)",
-    ],
-    "single_step_f32": [
-        "empty((4, 16), bf16, f32[4, 16])",
-        "empty((8, 16), bf16, f32[8, 16])",
-        "inbatch_step_f32(f32[4, 16], f32[8, 16], bf16[4, 16], bf16[8, 16], i64[4], 0, u8[8], 1, 0.25)",
-        "-- backward",
-        "-- second backward",
     ],
     "single_train_step_G": [
         "empty((4, 16), bf16, f32[4, 16])",
@@ -254,31 +184,6 @@ EXPECTED = {
         "-- second backward",
         "inbatch_bwd(bf16[4, 8], bf16[4, 16], bf16[8, 16], 1, f32[1], True, True)",
         "inbatch_bwd(bf16[4, 8], bf16[4, 16], bf16[8, 16], 1, f32[1], True, True)",
-    ],
-    "multi_step_packed": [
-        "empty((4, 16), bf16, f32[4, 16])",
-        "packed_rows(8, 16)",
-        "empty((16, 16), bf16, f32[8, 16])",
-        "pack_ctx(f32[8, 16], u8[8], bf16[16, 16])",
-        "empty((16, 16), bf16, f32[8, 16])",
-        "inbatch_step_packed_f32(f32[4, 16], bf16[16, 16], bf16[4, 16], 1, 0, 8, i64[4], 1, 0.25)",
-        "-- backward",
-        "empty((16, 16), f32, f32[16, 16])",
-        "-- second backward",
-        "empty((16, 16), f32, f32[16, 16])",
-    ],
-    "multi_step_packed_overlap": [
-        "packed_rows(8, 16)",
-        "empty((16, 16), bf16, f32[8, 16])",
-        "pack_ctx(f32[8, 16], u8[8], bf16[16, 16])",
-        "empty((16, 16), bf16, f32[8, 16])",
-        "empty((4, 16), bf16, f32[4, 16])",
-        "packed_rows(8, 16)",
-        "inbatch_step_packed_f32(f32[4, 16], bf16[16, 16], bf16[4, 16], 1, 0, 8, i64[4], 1, 0.25)",
-        "-- backward",
-        "empty((16, 16), f32, f32[16, 16])",
-        "-- second backward",
-        "empty((16, 16), f32, f32[16, 16])",
     ],
     "multi_train_fp32wire_G": [
         "empty((4, 16), bf16, f32[4, 16])",
@@ -411,35 +316,6 @@ EXPECTED = {
         "empty((8, 16), f32, bf16[16, 16])",
         "widen(bf16[16, 16], f32[8, 16])",
     ],
-    "multi_train_bf16wire_no_widen": [
-        "empty((4, 16), bf16, f32[4, 16])",
-        "packed_rows(8, 16)",
-        "empty((16, 16), bf16, f32[8, 16])",
-        "pack_ctx(f32[8, 16], u8[8], bf16[16, 16])",
-        "empty((16, 16), bf16, f32[8, 16])",
-        "train_step_packed_f32(f32[4, 16], bf16[16, 16], bf16[4, 16], 1, 0, 8, i64[4], 1, 0.25, 0.25, f32[1], bf16, defer_dq=True, want_G='auto')",
-        "-- backward",
-        "rescale_grads(f32[4, 16], bf16[16, 16], f32[1], f32[1])",
-        "empty((16, 16), bf16, bf16[16, 16])",
-        "-- second backward",
-        "inbatch_bwd(bf16[4, 16], bf16[4, 16], bf16[16, 16], 1, f32[1], True, True)",
-        "empty((16, 16), bf16, f32[16, 16])",
-    ],
-    "multi_train_bf16wire_no_widen_overlap": [
-        "packed_rows(8, 16)",
-        "empty((16, 16), bf16, f32[8, 16])",
-        "pack_ctx(f32[8, 16], u8[8], bf16[16, 16])",
-        "empty((16, 16), bf16, f32[8, 16])",
-        "empty((4, 16), bf16, f32[4, 16])",
-        "packed_rows(8, 16)",
-        "train_step_packed_f32(f32[4, 16], bf16[16, 16], bf16[4, 16], 1, 0, 8, i64[4], 1, 0.25, 0.25, f32[1], bf16, defer_dq=True, want_G='auto')",
-        "-- backward",
-        "rescale_grads(f32[4, 16], bf16[16, 16], f32[1], f32[1])",
-        "empty((16, 16), bf16, bf16[16, 16])",
-        "-- second backward",
-        "inbatch_bwd(bf16[4, 16], bf16[4, 16], bf16[16, 16], 1, f32[1], True, True)",
-        "empty((16, 16), bf16, f32[16, 16])",
-    ],
     "multi_bf16_inputs": [
         "empty((4, 16), bf16, bf16[4, 16])",
         "packed_rows(8, 16)",
@@ -519,7 +395,10 @@ def run_case(name, go, monkeypatch):
     if case.get("multi"):
         monkeypatch.setattr(D, "force_dist", lambda: True)
     hotpath._ExpectedGradScale._cur.clear()
-    kn = Recorder(StepKernels(**case.get("kn", {})), case.get("hide", ()))
+    inner = OracleKernels()
+    for k, v in case.get("kn", {}).items():
+        setattr(inner, k, v)
+    kn = Recorder(inner)
     dtype = case.get("dtype", torch.float32)
     grads = case.get("grads", True)
     tq = torch.from_numpy(q).to(dtype).requires_grad_(grads)

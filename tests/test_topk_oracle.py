@@ -1,7 +1,7 @@
 """tests/_topk_oracle.py tied down on the CPU: the reference of the GPU conformance suite (test_topk_conformance_gpu.py) against
 torch's stable sort and the project's present oracle where no NaN is involved, against itself when folded in pieces, and its NaN rule
-and input generators by direct inspection.  The two CPU-side folds of the product side (CorpusSearch._fold_rows_torch of the stand-in
-path, oracle.topk_merge) are held to the same reference here."""
+and input generators by direct inspection.  The CPU-side folds (oracle.topk_merge and the stand-in kernels' topk_update_wide built on it,
+which CorpusSearch reaches beyond k = 4096) are held to the same reference here."""
 import numpy as np
 import pytest
 import torch
@@ -93,27 +93,30 @@ def test_generators_hold_what_they_promise():
 
 
 @pytest.mark.parametrize("mode", T.MODES)
-def test_cpu_side_folds_of_the_product_follow_the_reference(mode):
-    """CorpusSearch._fold_rows_torch (the fold of the stand-in kernels beyond k = 4096) and oracle.topk_merge: a NaN score is dropped,
-    not sorted first (torch.sort) or taken when there is room (lexsort)."""
+def test_stand_in_wide_fold_follows_the_reference(mode):
+    """OracleKernels.topk_update_wide (the fold CorpusSearch calls beyond k = 4096 on the stand-in kernels) and oracle.topk_merge: a NaN
+    score is dropped, not sorted first (torch.sort) or taken when there is room (lexsort); unfilled slots stay last as -inf / -1; ties
+    go to the lower id.  The error words stay zero."""
     from _oracle_kernels import OracleKernels
-    from dpr_scale_amd.hotpath import CorpusSearch
 
     rows, cols, k = 6, 900, 130
     S = T.adversarial(rows, cols, 17, mode, k=k)
     edges = [0, 100, 101, 450, cols]  # a first piece smaller than k
-    s = CorpusSearch(torch.zeros(rows, 8), k, kernels=OracleKernels())
+    kn = OracleKernels()
+    values, indices = torch.full((rows, k), 7.0), torch.full((rows, k), 7, dtype=torch.int64)  # (a first call ignores what it finds)
+    ws = kn.topk_wide_workspace(rows, k, values)
     st = None
     for a, b in zip(edges[:-1], edges[1:]):
-        s._fold_rows_torch(None, torch.from_numpy(S[:, a:b]), BIG + a)
+        kn.topk_update_wide(torch.from_numpy(S[:, a:]), b - a, BIG + a, values, indices, a == 0, ws)  # (only `cols` columns are read)
         st = O.topk_merge(st, S[:, a:b], BIG + a, k)
         want = T.fold(None, S[:, :b], BIG, k)
-        assert _same((s.values.numpy(), s.indices.numpy()), want), (mode, b, "CorpusSearch._fold_rows_torch")
+        assert _same((values.numpy(), indices.numpy()), want), (mode, b, "OracleKernels.topk_update_wide")
         assert _same(st, want), (mode, b, "oracle.topk_merge")
+        assert not bool(kn.topk_wide_errors(ws, rows).any())
 
 
 def test_stand_in_search_beyond_the_streaming_kernel_drops_a_diverged_passage():
-    """The whole stand-in path at k > 4096 (CorpusSearch._fold_wide without a library): one NaN passage, one NaN query."""
+    """The whole stand-in path at k > 4096 (CorpusSearch._fold_wide on OracleKernels.topk_update_wide): one NaN passage, one NaN query."""
     from _oracle_kernels import OracleKernels
     from dpr_scale_amd.hotpath import CorpusSearch
 
