@@ -140,6 +140,12 @@ SIGNATURES = {
                                   c_int, c_void_p, c_int64, c_void_p]),
     "dprhot_spar_search": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, POINTER(c_float), c_int, c_int64,
                                    c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "dprhot_fp8_encode": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dprhot_dense_fp8_workspace_bytes": (c_int, [c_int, c_int, POINTER(c_size_t)]),
+    "dprhot_dense_fp8_score": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int, c_void_p, c_int64,
+                                       c_void_p]),
+    "dprhot_dense_fp8_search": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, c_int, c_int,
+                                        c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "dprhot_router_head_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int, c_int, POINTER(c_size_t)]),
     "dprhot_router_head_fwd": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int64, c_int64, c_void_p, c_int, c_int, c_int, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
@@ -261,6 +267,12 @@ def colbert_workspace_bytes(nq: int, chunk: int) -> int:
 def spar_workspace_bytes(nq: int, W: int, chunk: int) -> int:
     out = c_size_t(0)
     check(lib.dprhot_spar_workspace_bytes(int(nq), int(W), int(chunk), ctypes.byref(out)), "dprhot_spar_workspace_bytes")
+    return out.value
+
+
+def dense_fp8_workspace_bytes(nq: int, chunk: int) -> int:
+    out = c_size_t(0)
+    check(lib.dprhot_dense_fp8_workspace_bytes(int(nq), int(chunk), ctypes.byref(out)), "dprhot_dense_fp8_workspace_bytes")
     return out.value
 
 

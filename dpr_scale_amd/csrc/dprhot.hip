@@ -39,6 +39,7 @@
 #include "colbert.h"
 #include "colbert_pq.h"
 #include "spar.h"
+#include "dense_fp8.h"
 
 using namespace dprhot;
 
@@ -3012,6 +3013,117 @@ int dprhot_spar_search(const dprhot_bf16* Q1, const dprhot_bf16* Q2, int nq, int
     if (int rc = launch<spar_kernel<true>>(spar_grid(nq, cols), dim3(256), 0, st, a)) return rc;
     TopkArgs p{S, rows, cols, (long long)ld, (long long)j0, k, values, indices, 0, cand_j, cnt};
     if (int rc = launch_topk(p, rows, st)) return rc;
+  }
+  return DPRHOT_OK;
+}
+
+// ---- the fp8 dense index: e4m3fn rows, one power-of-two scale per row (csrc/dense_fp8.h) ----
+int dprhot_fp8_encode(const void* rows, int is_bf16, int64_t n, int d, int dp, uint8_t* codes, float* scale, void* stream) {
+  REQUIRE(rows && codes && scale, "NULL pointer (rows, codes and scale are required)");
+  REQUIRE(aligned16(codes) && (reinterpret_cast<uintptr_t>(rows) & (is_bf16 ? 1u : 3u)) == 0 && (reinterpret_cast<uintptr_t>(scale) & 3u) == 0,
+          "codes must be 16-byte aligned, rows and scale aligned to their elements");
+  REQUIRE(dp > 0 && dp % 32 == 0, "dp=%d must be a positive multiple of 32", dp);
+  REQUIRE(d > 0 && d <= dp, "d=%d out of range (1 .. dp=%d)", d, dp);
+  REQUIRE(n > 0 && n < (1ll << 31), "n=%lld rows out of range (1 .. 2^31 - 1)", (long long)n);
+  const dim3 grid((unsigned)((n + 3) / 4));
+  if (is_bf16) return launch<fp8_encode_kernel<true>>(grid, dim3(256), 0, (hipStream_t)stream, rows, (long long)n, d, dp, codes, scale);
+  return launch<fp8_encode_kernel<false>>(grid, dim3(256), 0, (hipStream_t)stream, rows, (long long)n, d, dp, codes, scale);
+}
+
+static int dfp8_check(const void* Qc, const void* qs, int nq, const void* Cc, const void* cs, int64_t n_ctx, int dp) {
+  REQUIRE(Qc && qs && Cc && cs, "NULL pointer (Qc, qs, Cc and cs are required)");
+  REQUIRE(aligned16(Qc) && aligned16(Cc), "code rows must be 16-byte aligned");
+  REQUIRE((reinterpret_cast<uintptr_t>(qs) & 3u) == 0 && (reinterpret_cast<uintptr_t>(cs) & 3u) == 0, "scales must be 4-byte aligned");
+  REQUIRE(dp > 0 && dp % 32 == 0, "dp=%d must be a positive multiple of 32 (pad with code 0)", dp);
+  REQUIRE(nq > 0 && nq <= 65535 * F8_B, "nq=%d queries out of range (1 .. %d)", nq, 65535 * F8_B);
+  REQUIRE(n_ctx > 0 && n_ctx < (1ll << 31), "n_ctx=%lld out of range (1 .. 2^31 - 1)", (long long)n_ctx);
+  return DPRHOT_OK;
+}
+
+// one launch of dfp8_kernel over passage ids j0 .. j0 + cols (checked by the callers)
+static Dfp8Args dfp8_args(const uint8_t* Qc, const float* qs, int nq, const uint8_t* Cc, const float* cs, int dp, int64_t j0, int cols) {
+  Dfp8Args a{};
+  a.Qc = Qc; a.qs = qs;
+  a.Cc = Cc + (size_t)j0 * dp;
+  a.cs = cs + j0;
+  a.nq = nq; a.cols = cols; a.dp = dp;
+  return a;
+}
+// at most F8_TM_SHORT queries: the short query tile (a score's bits do not depend on the tile)
+extern "C++" {
+template <bool FILTER>
+static int dfp8_launch(const Dfp8Args& a, hipStream_t st) {
+  if (a.nq <= F8_TM_SHORT) return launch<dfp8_kernel<FILTER, F8_TM_SHORT>>(dim3((unsigned)cdiv(a.cols, F8_B), 1), dim3(256), 0, st, a);
+  return launch<dfp8_kernel<FILTER, F8_B>>(dim3((unsigned)cdiv(a.cols, F8_B), (unsigned)cdiv(a.nq, F8_B)), dim3(256), 0, st, a);
+}
+}  // extern "C++"
+
+int dprhot_dense_fp8_workspace_bytes(int nq, int chunk, size_t* bytes) {
+  REQUIRE(bytes != nullptr, "NULL out pointer");
+  REQUIRE(nq > 0, "nq=%d queries out of range (1 .. 2^31 - 1)", nq);
+  REQUIRE(chunk > 0 && chunk % 8 == 0, "chunk=%d must be a positive multiple of 8", chunk);
+  REQUIRE((long long)nq * chunk < (1ll << 40), "nq * chunk = %d * %d candidate slots out of range (< 2^40)", nq, chunk);
+  *bytes = search_ws_bytes(nq, chunk);
+  return DPRHOT_OK;
+}
+
+int dprhot_dense_fp8_score(const uint8_t* Qc, const float* qs, int nq, const uint8_t* Cc, const float* cs, int64_t n_ctx, int dp,
+                           int64_t doc_begin, int cols, float* S, int64_t ld, void* stream) {
+  if (int rc = dfp8_check(Qc, qs, nq, Cc, cs, n_ctx, dp)) return rc;
+  if (int rc = check_score_window(S, cols, ld, doc_begin, n_ctx)) return rc;
+  REQUIRE(ld % 8 == 0 && aligned16(S), "S must be 16-byte aligned with ld=%lld a multiple of 8", (long long)ld);
+  Dfp8Args a = dfp8_args(Qc, qs, nq, Cc, cs, dp, doc_begin, cols);
+  a.S = S;
+  a.ld = (long long)ld;
+  return dfp8_launch<false>(a, (hipStream_t)stream);
+}
+
+int dprhot_dense_fp8_search(const uint8_t* Qc, const float* qs, int nq, const uint8_t* Cc, const float* cs, int64_t n_ctx, int dp,
+                            int64_t id_begin, int64_t id_end, int k, int chunk, float* values, int64_t* indices, int first, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+  if (int rc = dfp8_check(Qc, qs, nq, Cc, cs, n_ctx, dp)) return rc;
+  REQUIRE(values && indices, "NULL pointer");
+  REQUIRE(k >= 1 && k <= n_ctx, "topk=%d out of range (1 .. n_ctx=%lld)", k, (long long)n_ctx);
+  REQUIRE(0 <= id_begin && id_begin < id_end && id_end <= n_ctx, "bad passage-id range [%lld, %lld) of %lld", (long long)id_begin,
+          (long long)id_end, (long long)n_ctx);
+  REQUIRE(chunk > 0 && chunk % 8 == 0, "chunk=%d must be a positive multiple of 8", chunk);
+  REQUIRE((long long)nq * chunk < (1ll << 40), "nq * chunk = %d * %d candidate slots out of range (< 2^40)", nq, chunk);
+  const bool wide = k > TK_KWIDE;
+  const size_t need = search_ws_bytes(nq, chunk) + (wide ? wsel_ws_bytes(nq, k) : 0);
+  if (workspace == nullptr || workspace_bytes < need)
+    return fail(DPRHOT_E_WORKSPACE, "dense_fp8_search needs %zu workspace bytes (dprhot_dense_fp8_workspace_bytes%s), got %zu", need,
+                wide ? " + dprhot_topk_wide_workspace_bytes" : "", workspace_bytes);
+  REQUIRE(aligned16(workspace), "workspace must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  if (k > TK_KMAX) {  // beyond the candidate-list merge: every chunk materialised, the chunk driver's selection
+    auto fill = [&](int64_t j0, int cols, float* S, int ld) {
+      return dprhot_dense_fp8_score(Qc, qs, nq, Cc, cs, n_ctx, dp, j0, cols, S, ld, stream);
+    };
+    return topk_search_chunks("dense_fp8", fill, nq, n_ctx, id_begin, id_end, k, chunk, values, indices, first, workspace, workspace_bytes,
+                              stream);
+  }
+  // the layout of dprhot_search: scores of the first chunk / candidate values, candidate columns, candidate counts
+  float* S = static_cast<float*>(workspace);
+  int* cand_j = reinterpret_cast<int*>(static_cast<char*>(workspace) + (size_t)nq * chunk * 4);
+  int* cnt = reinterpret_cast<int*>(static_cast<char*>(workspace) + (size_t)nq * chunk * 8);
+  HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)nq * sizeof(int), st));
+  for (int64_t j0 = id_begin; j0 < id_end; j0 += chunk) {
+    const int cols = (int)(id_end - j0 < chunk ? id_end - j0 : chunk);
+    const int ld = (cols + 7) / 8 * 8;  // (<= chunk: chunk is a multiple of 8)
+    Dfp8Args a = dfp8_args(Qc, qs, nq, Cc, cs, dp, j0, cols);
+    if (first && j0 == id_begin) {  // nothing to filter against yet: materialise this chunk's scores and select from them
+      a.S = S;
+      a.ld = ld;
+      if (int rc = dfp8_launch<false>(a, st)) return rc;
+      if (int rc = dprhot_topk_update(S, nq, cols, ld, j0, k, values, indices, 1, stream)) return rc;
+      continue;
+    }
+    // scores that cannot enter a row's top-k never leave the tile; at most `cols` candidates per row and chunk
+    a.kth_val = values; a.kth_idx = indices; a.k = k; a.col_offset = (long long)j0;
+    a.cnt = cnt; a.cand_v = S; a.cand_j = cand_j; a.ldc = ld;
+    if (int rc = dfp8_launch<true>(a, st)) return rc;
+    TopkArgs p{S, nq, cols, (long long)ld, (long long)j0, k, values, indices, 0, cand_j, cnt};
+    if (int rc = launch_topk(p, nq, st)) return rc;
   }
   return DPRHOT_OK;
 }

@@ -629,6 +629,41 @@ class HipKernels:
                                                     *self._topk_tail(id_begin, id_end, values, indices, first, chunk, ws)),
                         "dprhot_spar_search")
 
+    # -- the fp8 dense index: e4m3fn rows, one power-of-two scale per row (csrc/dense_fp8.h; dense_fp8.py) ----
+    def fp8_encode(self, rows, codes, scale):
+        """codes uint8 [n, dp] and scale fp32 [n] (both contiguous, written in full) <- rows fp32 or bf16 [n, d] (dprhot_fp8_encode)."""
+        self._require_gpu(rows, codes, scale)
+        assert rows.dtype in (torch.float32, _BF16) and rows.dim() == 2 and rows.is_contiguous(), "rows: contiguous fp32 or bf16 [n, d]"
+        n, d = rows.shape
+        assert codes.dtype == torch.uint8 and codes.is_contiguous() and codes.shape[0] == n and scale.dtype == torch.float32
+        assert scale.is_contiguous() and scale.shape == (n,)
+        self._lib.check(self.lib.dprhot_fp8_encode(_ptr(rows), int(rows.dtype == _BF16), n, d, codes.shape[1], _ptr(codes), _ptr(scale),
+                                                   self._stream()), "dprhot_fp8_encode")
+
+    def dense_fp8_workspace(self, nq, chunk, k, like):
+        return self._chunk_workspace(self._lib.dense_fp8_workspace_bytes(nq, chunk), nq, k, like)
+
+    def _dense_fp8_operands(self, index, qc, qs):
+        """Qc, qs, nq, Cc, cs, n_ctx, dp: what both entry points of the fp8 dense index begin with."""
+        self._require_gpu(qc, qs, index.codes, index.scale)
+        assert qc.dtype == torch.uint8 and qs.dtype == torch.float32 and qc.is_contiguous() and qs.shape == (qc.shape[0],)
+        assert qc.shape[1] == index.codes.shape[1], "query codes must have the index's padded width"
+        return _ptr(qc), _ptr(qs), qc.shape[0], _ptr(index.codes), _ptr(index.scale), index.corpus_len, qc.shape[1]
+
+    def dense_fp8_score(self, index, qc, qs, doc_begin, cols, S):
+        """Writes s[i][j] = (<value(qc[i]), value(codes[j])> * qs[i]) * scale[j] of passages doc_begin .. doc_begin + cols into
+        S [nq, >= cols] fp32 (dprhot_dense_fp8_score)."""
+        self._require_gpu(S)
+        self._lib.check(self.lib.dprhot_dense_fp8_score(*self._dense_fp8_operands(index, qc, qs), int(doc_begin), int(cols), _ptr(S),
+                                                        S.stride(0), self._stream()), "dprhot_dense_fp8_score")
+
+    def dense_fp8_search(self, index, qc, qs, id_begin, id_end, values, indices, first, chunk, ws):
+        """Folds passage ids [id_begin, id_end) into the running top-k, values / indices [nq, k] (dprhot_dense_fp8_search)."""
+        self._require_gpu(values, indices, ws)
+        self._lib.check(self.lib.dprhot_dense_fp8_search(*self._dense_fp8_operands(index, qc, qs),
+                                                         *self._topk_tail(id_begin, id_end, values, indices, first, chunk, ws)),
+                        "dprhot_dense_fp8_search")
+
     # -- product-quantised postings (csrc/ivf_pq.h; DESIGN.md section 10.2; dpr_scale_amd/ivf.py owns training and the index) ----
     def pq_encode(self, vec, codebook, entry="dprhot_pq_encode"):
         """codes uint8 [n, m] of the rows vec bf16 [n, dp] under codebook bf16 [m, 256, dsub] (dprhot_pq_encode)."""

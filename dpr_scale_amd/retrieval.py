@@ -43,11 +43,31 @@ def build_index(paths, device):
     return index.to(device)
 
 
-def search_shards(query_embs, ctx_embeddings_dir, topk, shard=1, device=None, chunk=None, kernels=None):
+def search_shards(query_embs, ctx_embeddings_dir, topk, shard=1, device=None, chunk=None, kernels=None, quantizer=None):
     """(scores [nq, topk] fp32, indexes [nq, topk] int64) over all `reps_*` files, passage ids counted as the reference
-    counts them (offset += len(index) per shard).  Order: score descending, ties by lower id."""
+    counts them (offset += len(index) per shard).  Order: score descending, ties by lower id.
+
+    quantizer=None streams the bf16 rows through hotpath.CorpusSearch.  quantizer="fp8" encodes every shard into e4m3fn codes
+    with one scale per row as it is read, joins them into ONE resident dense_fp8.DenseFP8Index with the same ids (the zero
+    vectors behind a short last file included) and searches that: queries and passages quantised, DESIGN.md section 14."""
     q = _load(query_embs) if isinstance(query_embs, (str, os.PathLike)) else torch.as_tensor(query_embs)
     device = torch.device(device) if device is not None else torch.device("cuda", 0)
+    if quantizer == "fp8":
+        from . import dense_fp8
+        from ._chunked import _default_kernels
+
+        kernels = _default_kernels(kernels)
+        pieces, width = [], None
+        for paths in shard_files(ctx_embeddings_dir, shard):
+            index = build_index(paths, device)
+            width = index.shape[1]
+            pieces.append(dense_fp8.encode_rows(kernels, index, dense_fp8.padded_width(width), device))
+            del index
+        codes, scale = torch.cat([c for c, _ in pieces], dim=0), torch.cat([s for _, s in pieces], dim=0)
+        del pieces
+        return dense_fp8.DenseFP8Index.from_codes(codes, scale, width, device, chunk=chunk, kernels=kernels).search(q.float(), topk)
+    if quantizer is not None:
+        raise ValueError(f"quantizer={quantizer!r}: None or 'fp8'")
     search = hotpath.CorpusSearch(q.float().to(device), topk, chunk=chunk, kernels=kernels)
     offset = 0
     for paths in shard_files(ctx_embeddings_dir, shard):

@@ -513,6 +513,38 @@ int dprhot_spar_search(const dprhot_bf16* Q1, const dprhot_bf16* Q2, int nq, int
                        int64_t n_ctx, const float* lam, int W, int64_t id_begin, int64_t id_end, int k, int chunk, float* values,
                        int64_t* indices, int first, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The fp8 dense index (csrc/dense_fp8.h; dpr_scale_amd/dense_fp8.py): a dense corpus as OCP e4m3fn codes
+ * (NOT the fnuz form) with one power-of-two fp32 scale per row, d + 4 bytes per passage instead of 2 d.  codes uint8 [n, dp],
+ * dp = round_up(d, 32), the features behind d are code 0x00; scale fp32 [n].  With amax = max |x_t| = f * 2^p (1 <= f < 2):
+ * e = p - 8 + (f > 1.75 ? 1 : 0) clamped to [-64, 64] and scale = 2^e, the smallest power of two with amax <= 448 * scale, read off the
+ * float's bits; code_t = e4m3fn(x_t / scale), an exact division, rounded to nearest even, saturating at +-448 (which only the clamp can
+ * make happen); -0 stays -0; a row with amax == 0 has scale 1; a row with a non-finite element has scale NaN and codes 0x00.  Every
+ * decoded value value(code) * scale of a finite row is exact in bf16.
+ * dprhot_fp8_encode: rows fp32 (is_bf16 = 0) or bf16 (1) [n, d], row-major without padding -> codes [n, dp] (the zero padding included)
+ * and scale [n].  Queries are quantised by the same rule.
+ *   s[i][j] = (acc[i][j] * qs[i]) * cs[j],   acc[i][j] = sum_t value(Qc[i][t]) * value(Cc[j][t])
+ * acc is accumulated in fp32 by the MFMA unit, t ascending; two fp32 multiplies follow.  A score depends on its two code rows and its two
+ * scales only, and has the same bits whether dprhot_dense_fp8_score stores it or dprhot_dense_fp8_search ranks it.  A NaN scale or a NaN
+ * code (0x7F / 0xFF) makes its scores NaN; a NaN is never selected.
+ * dprhot_dense_fp8_score WRITES S[i][j - doc_begin] for doc_begin <= j < doc_begin + cols <= n_ctx, every cell and nothing else of
+ * S [nq, ld] (ld >= cols, ld % 8 == 0).
+ * dprhot_dense_fp8_search folds passage ids [id_begin, id_end) into values / indices [nq, k]: total order, `first`, the -inf / -1
+ * unfilled tail and "a NaN is never selected" as in dprhot_topk_update; disjoint id ranges may be folded into one result, which equals
+ * dprhot_topk over the dprhot_dense_fp8_score matrix of those ranges bit for bit.  k <= 1024: the first chunk of an empty state is
+ * materialised and selected from, every other chunk leaves the tile as candidate lists which the streaming top-k merges; k > 1024: every
+ * chunk is materialised (k > 4096: the HBM-resident selection).  workspace: dprhot_dense_fp8_workspace_bytes(nq, chunk), which equals
+ * dprhot_search_workspace_bytes(nq, chunk) (+ dprhot_topk_wide_workspace_bytes(nq, k) behind it when k > 4096); DPRHOT_E_WORKSPACE when
+ * smaller.
+ * Limits (DPRHOT_E_INVALID): NULL pointers, code rows / S / workspace not 16-byte aligned, dp % 32, d outside 1 .. dp, nq < 1,
+ * nq * chunk >= 2^40, not 0 <= id_begin < id_end <= n_ctx < 2^31, not 1 <= k <= n_ctx, chunk % 8. */
+int dprhot_fp8_encode(const void* rows, int is_bf16, int64_t n, int d, int dp, uint8_t* codes, float* scale, void* stream);
+int dprhot_dense_fp8_workspace_bytes(int nq, int chunk, size_t* bytes);
+int dprhot_dense_fp8_score(const uint8_t* Qc, const float* qs, int nq, const uint8_t* Cc, const float* cs, int64_t n_ctx, int dp,
+                           int64_t doc_begin, int cols, float* S, int64_t ld, void* stream);
+int dprhot_dense_fp8_search(const uint8_t* Qc, const float* qs, int nq, const uint8_t* Cc, const float* cs, int64_t n_ctx, int dp,
+                            int64_t id_begin, int64_t id_end, int k, int chunk, float* values, int64_t* indices, int first, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 /* The CITADEL / SPLADE encoder head behind the MLM logits (dpr_scale/models/citadel_models/citadel_model.py:46-82, splade_model.py:26-32;
  * csrc/router_head.h), forward and backward without a [B, T, V] temporary.  logits [B, T1, V] of `dtype` (0 bf16,
  * 1 fp16, 2 fp32) with unit column stride and ELEMENT strides stride_b / stride_t (a [:, 1:, :] view or a column slice of a wider buffer
