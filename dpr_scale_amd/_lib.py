@@ -130,6 +130,11 @@ SIGNATURES = {
                                      c_int64, c_void_p]),
     "dprhot_colbert_search": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_int64, c_int64, c_int,
                                       c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "dprhot_colbert_cand_workspace_bytes": (c_int, [c_int, c_int, POINTER(c_size_t)]),
+    "dprhot_colbert_cand_score": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                          c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "dprhot_colbert_cand_search": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                           c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dprhot_colbert_pq_encode": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "dprhot_colbert_pq_score": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int, c_int,
                                         c_int64, c_int, c_void_p, c_int64, c_void_p]),
@@ -261,6 +266,12 @@ def ivf_workspace_bytes(nq: int, n_entries: int, chunk: int, has_cls: bool) -> i
 def colbert_workspace_bytes(nq: int, chunk: int) -> int:
     out = c_size_t(0)
     check(lib.dprhot_colbert_workspace_bytes(int(nq), int(chunk), ctypes.byref(out)), "dprhot_colbert_workspace_bytes")
+    return out.value
+
+
+def colbert_cand_workspace_bytes(nq: int, chunk: int) -> int:
+    out = c_size_t(0)
+    check(lib.dprhot_colbert_cand_workspace_bytes(int(nq), int(chunk), ctypes.byref(out)), "dprhot_colbert_cand_workspace_bytes")
     return out.value
 
 

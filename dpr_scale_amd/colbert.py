@@ -24,8 +24,16 @@ features under one bf16 codebook (64, 32 or 16 bytes per token at d = 128 instea
 token rows of every block.  Its search returns, bit for bit, the dense search over the decoded rows (`ColBERTPQIndex.decode`).  The
 two builders encode file by file / part by part: the dense index is never needed to make the quantised one.
 
-Not supported (out of scope): residual token vectors, centroid pruning (PLAID-style candidate generation), an index across several
-GPUs, a CPU index.
+Centroid pruning: `ColBERTIndex.build_centroids` assigns every stored token to its nearest of C unit-norm
+centroids and keeps, per centroid, the sorted list of passages with a token there.  `search_pruned(q, topk, nprobe)` probes the
+`nprobe` best centroids of every query token, unites their lists into one sorted candidate list per query and scores ONLY those
+passages -- with the exhaustive score, bit for bit (dprhot_colbert_cand_search) -- so its result is the exhaustive top-k restricted to
+the candidate set; what it may lose is a passage none of whose tokens lies in a probed centroid.  Assignment and probing are exact bf16
+top-k searches on the MFMA path (hotpath.CorpusSearch), ties to the lower centroid id.
+
+Not supported (out of scope): residual token vectors, compressed candidates (a candidate kernel over the product-quantised rows),
+PLAID's centroid-interaction stage (pruning the candidates by approximate scores from per-passage centroid codes; `tok_centroid` is
+kept so that it can follow), an index across several GPUs, a CPU index.
 """
 import glob
 import os
@@ -193,12 +201,15 @@ class ColBERTIndex(_TokenSearch):
         self.n_blk = int(tok.shape[0]) // BLOCK
         assert blk_rows is None or (blk_rows.dtype == torch.uint8 and blk_rows.shape == (self.n_blk,))
         self._blk_rows = blk_rows
+        self.centroids = self.tok_centroid = self.cen_off = self.cen_doc = None  # build_centroids / load_centroids
         self._init_search(chunk, kernels)
 
     @property
     def nbytes(self):
-        """Bytes of device memory the index holds (token rows and block offsets)."""
-        return sum(t.numel() * t.element_size() for t in (self.tok, self.doc_blk))
+        """Bytes of device memory the index holds (token rows and block offsets; with centroids: those, the tokens' assignment and the
+        inverted lists)."""
+        held = (self.tok, self.doc_blk, self.centroids, self.tok_centroid, self.cen_off, self.cen_doc)
+        return sum(t.numel() * t.element_size() for t in held if t is not None)
 
     @property
     def blk_rows(self):
@@ -227,6 +238,202 @@ class ColBERTIndex(_TokenSearch):
             part = real[lo:lo + (1 << 22)]
             codes[part] = kn.colbert_pq_encode(self.tok[part], codebook)
         return ColBERTPQIndex.from_packed(codes, blk_rows, codebook, self.doc_blk, self.corpus_len, self.d, chunk=self.chunk, kernels=kn)
+
+    # ---- centroid pruning ----
+    def build_centroids(self, n_centroids, iters=10, train_size=1 << 18, seed=0, centroids=None):
+        """Gives the index `n_centroids` unit-norm centroids (spherical k-means on a seeded sample of `train_size` stored token rows --
+        train_centroids -- unless `centroids` [n_centroids, d] are given), assigns every stored token row to argmax_c <tok, centroid_c>
+        (bf16 MFMA path, ties to the lower centroid id) and builds the inverted lists.  The index then holds
+          centroids     bf16 [C, dp]
+          tok_centroid  int32 [n_blk * 16], -1 on padding rows
+          cen_off int64 [C + 1], cen_doc int32: per centroid the sorted, duplicate-free doc ids with at least one token there
+        The lists come from one device sort (torch.unique of centroid * corpus_len + doc): no host loop over centroids or passages."""
+        C, kn = int(n_centroids), self._kernels()
+        real = torch.nonzero(_real_rows(self.blk_rows)).reshape(-1)
+        if centroids is None:
+            if not 1 <= C <= int(real.shape[0]):
+                raise ValueError(f"n_centroids={C} out of range (1 .. the index's {int(real.shape[0])} token rows)")
+            pick = _sample(int(real.shape[0]), train_size, seed)
+            cen = train_centroids(self.tok[real if pick is None else real[pick.to(self.device)]], C, iters=iters, seed=seed, kernels=kn)
+        else:
+            cen = torch.as_tensor(centroids)
+            if cen.dim() != 2 or cen.shape[0] != C or C < 1 or cen.shape[1] != self.d:
+                raise ValueError(f"centroids {tuple(cen.shape)}; [{C}, {self.d}] expected")
+            cen = _bf16_padded(cen.to(self.device), self.dp)
+        tok_centroid = torch.full((self.n_blk * BLOCK,), -1, dtype=torch.int32, device=self.device)
+        for lo in range(0, int(real.shape[0]), 1 << 22):
+            part = real[lo:lo + (1 << 22)]
+            tok_centroid[part] = _nearest(kn, self.tok[part], cen, 1)[:, 0].to(torch.int32)
+        self._set_centroids(cen.contiguous(), tok_centroid, *_centroid_lists(tok_centroid, self.doc_blk, C, self.corpus_len))
+        return self
+
+    def _set_centroids(self, centroids, tok_centroid, cen_off, cen_doc):
+        C = int(centroids.shape[0])
+        assert centroids.dtype == _BF16 and centroids.shape == (C, self.dp) and C >= 1
+        assert tok_centroid.dtype == torch.int32 and tok_centroid.shape == (self.n_blk * BLOCK,)
+        assert cen_off.dtype == torch.int64 and cen_off.shape == (C + 1,) and cen_doc.dtype == torch.int32 and cen_doc.dim() == 1
+        self.centroids, self.tok_centroid, self.cen_off, self.cen_doc = centroids, tok_centroid, cen_off, cen_doc
+
+    def _need_centroids(self):
+        if self.centroids is None:
+            raise ValueError("the index has no centroids: build_centroids or load_centroids first")
+        return int(self.centroids.shape[0])
+
+    def save_centroids(self, path):
+        """A protocol-4 pickle of (centroids, tok_centroid, cen_off, cen_doc) on the CPU; load_centroids reads it back."""
+        self._need_centroids()
+        with open(path, "wb") as f:
+            pickle.dump(tuple(t.cpu() for t in (self.centroids, self.tok_centroid, self.cen_off, self.cen_doc)), f, protocol=4)
+        return path
+
+    def load_centroids(self, path):
+        """The centroids save_centroids wrote for an index of the same layout: it then probes and searches bit-identically."""
+        with open(path, "rb") as f:
+            blob = pickle.load(f)
+        if not isinstance(blob, tuple) or len(blob) != 4:
+            raise ValueError(f"{path}: not a centroid file")
+        cen, tc, off, doc = (torch.as_tensor(t).contiguous().to(self.device) for t in blob)
+        if cen.dim() != 2 or cen.shape[1] != self.dp or tc.shape != (self.n_blk * BLOCK,) or off.shape != (cen.shape[0] + 1,):
+            raise ValueError(f"{path}: centroids {tuple(cen.shape)} over {tuple(tc.shape)} token rows do not belong to this index "
+                             f"(dp={self.dp}, {self.n_blk * BLOCK} rows)")
+        self._set_centroids(cen, tc, off, doc)
+        return self
+
+    def _probe(self, qb, nprobe):
+        C, nprobe = self._need_centroids(), int(nprobe)
+        if not 1 <= nprobe <= C:
+            raise ValueError(f"nprobe={nprobe} out of range (1 .. n_centroids={C})")
+        nq, LQ, dp = qb.shape
+        return _nearest(self._kernels(), qb.reshape(nq * LQ, dp), self.centroids, nprobe).view(nq, LQ, nprobe)
+
+    def probe(self, q, nprobe):
+        """int64 [nq, LQ, nprobe]: the exact top-`nprobe` centroids of every query token by inner product (bf16 MFMA path), best first,
+        ties to the lower centroid id.  An all-zero (padding) query token gets ids too; `candidates` drops it."""
+        return self._probe(self._queries(q), nprobe)
+
+    def _candidates(self, qb, nprobe):
+        return self._union(qb, self._probe(qb, nprobe))
+
+    def _union(self, qb, cids):
+        """(cand_off, cand_doc, n_cand, max_count) of `candidates` from the probed centroid ids [nq, LQ, nprobe]; ONE host read of its
+        own (the two counts) -- torch.unique and repeat_interleave size their outputs on the host themselves."""
+        C, dev = self._need_centroids(), self.device
+        nq = int(qb.shape[0])
+        live = (qb != 0).any(2).unsqueeze(2) & (cids >= 0)                           # padded query tokens probe nothing (-1: a NaN token)
+        qid = torch.arange(nq, device=dev).view(nq, 1, 1).expand_as(cids)[live]
+        pair = torch.unique(qid * C + cids[live])                                    # a query names a centroid once
+        qid, cid = pair // C, pair % C
+        lens = self.cen_off[cid + 1] - self.cen_off[cid]
+        seg = torch.repeat_interleave(torch.arange(pair.shape[0], device=dev), lens)
+        within = torch.arange(seg.shape[0], device=dev) - (torch.cumsum(lens, 0) - lens)[seg]
+        docs = self.cen_doc[self.cen_off[cid][seg] + within].to(torch.int64)
+        key = torch.unique(qid[seg] * self.corpus_len + docs)                        # sorted: by query, then by doc id
+        counts = torch.bincount(key // self.corpus_len, minlength=nq)
+        cand_off = torch.zeros(nq + 1, dtype=torch.int64, device=dev)
+        torch.cumsum(counts, 0, out=cand_off[1:])
+        n_cand, max_count = torch.stack([cand_off[-1], counts.max()]).tolist()
+        return cand_off, (key % self.corpus_len).to(torch.int32), int(n_cand), int(max_count)
+
+    def candidates(self, q, nprobe):
+        """(cand_off int64 [nq + 1], cand_doc int32 [n_cand]): per query the sorted, duplicate-free union of the inverted lists of the
+        centroids its (non-padding) tokens probe, built on the device."""
+        return self._candidates(self._queries(q), nprobe)[:2]
+
+    def score_candidates(self, q, cand_off, cand_doc, query_pool="sum"):
+        """fp32 [nq, max_count]: cell [n, p] is the exhaustive score of query n and its p-th candidate, bit for bit; a cell at or behind
+        the query's count (or whose doc id lies outside the corpus) is NaN, "no candidate"."""
+        pool, qb = self._pool(query_pool), self._queries(q)
+        cand_off = cand_off.to(self.device, torch.int64).contiguous()
+        cand_doc = cand_doc.to(self.device, torch.int32).contiguous()
+        if cand_off.shape != (qb.shape[0] + 1,):
+            raise ValueError(f"cand_off {tuple(cand_off.shape)} for {qb.shape[0]} queries")
+        off = cand_off.clamp(0, int(cand_doc.shape[0]))  # the kernel's own reading of a pair of offsets
+        max_count = int((off[1:] - off[:-1]).max().clamp(min=0))
+        S = torch.empty((qb.shape[0], max_count), dtype=torch.float32, device=self.device)
+        if max_count:
+            self._kernels().colbert_cand_score(self, qb, pool, cand_off, cand_doc, 0, max_count, S)
+        return S
+
+    def search_pruned(self, q, topk, nprobe, query_pool="sum", chunk=None):
+        """`search` over the candidates of `candidates(q, nprobe)` only: (scores fp32 [nq, topk], ids int64 [nq, topk]), score
+        descending with ties to the lower doc id -- the exhaustive top-k restricted to the candidate set, bit for bit.  A query with
+        fewer than topk candidates ends in -inf / -1.  latency: encode_time, candidate_time (probe and union), search_time."""
+        pool, topk = self._pool(query_pool), int(topk)
+        if not 1 <= topk <= self.corpus_len:
+            raise ValueError(f"topk={topk} out of range (1 .. corpus_len={self.corpus_len})")
+        tic = time.perf_counter()
+        qb = self._queries(q)
+        self.latency["encode_time"] += time.perf_counter() - tic
+        tic = time.perf_counter()
+        cand_off, cand_doc, _, max_count = self._candidates(qb, nprobe)
+        self.latency["candidate_time"] += time.perf_counter() - tic
+        tic = time.perf_counter()
+        out = self._search_candidates(qb, pool, topk, cand_off, cand_doc, max_count, chunk)
+        self.latency["search_time"] += time.perf_counter() - tic
+        return out
+
+    def _search_candidates(self, qb, pool, topk, cand_off, cand_doc, max_count, chunk=None):
+        nq, kn = int(qb.shape[0]), self._kernels()
+        values = torch.full((nq, topk), float("-inf"), dtype=torch.float32, device=self.device)
+        indices = torch.full((nq, topk), -1, dtype=torch.int64, device=self.device)
+        if max_count:
+            chunk = self.default_chunk(nq) if chunk is None else int(chunk)
+            chunk = max(8, min(chunk, (max_count + 7) // 8 * 8))
+            ws = kn.colbert_cand_workspace(nq, chunk, topk, self.doc_blk)
+            kn.colbert_cand_search(self, qb, pool, cand_off, cand_doc, max_count, values, indices, chunk, ws)
+        return values, indices
+
+
+def _nearest(kn, rows, centroids, k):
+    """int64 [n, k]: the exact top-k rows of `centroids` bf16 [C, dp] for every row of `rows` bf16 [n, dp] by inner product, best
+    first, ties to the lower id: hotpath.CorpusSearch (dprhot_search, bf16 MFMA) in batches of 16384 rows."""
+    from . import hotpath
+
+    n, C = int(rows.shape[0]), int(centroids.shape[0])
+    out = torch.empty((n, int(k)), dtype=torch.int64, device=rows.device)
+    chunk = min((C + 7) // 8 * 8, 4096)  # the search workspace is 16384 x chunk x 8 bytes
+    for lo in range(0, n, 1 << 14):
+        s = hotpath.CorpusSearch(rows[lo:lo + (1 << 14)], int(k), chunk=chunk, kernels=kn)
+        s.add(centroids)
+        out[lo:lo + (1 << 14)] = s.result()[1]
+    return out
+
+
+def _centroid_lists(tok_centroid, doc_blk, n_centroids, corpus_len):
+    """(cen_off int64 [C + 1], cen_doc int32): per centroid the sorted, duplicate-free doc ids with a token assigned to it."""
+    dev = tok_centroid.device
+    doc_of_blk = torch.repeat_interleave(torch.arange(corpus_len, device=dev), doc_blk[1:] - doc_blk[:-1])
+    real = torch.nonzero(tok_centroid >= 0).reshape(-1)
+    key = torch.unique(tok_centroid[real].to(torch.int64) * corpus_len + doc_of_blk[real // BLOCK])
+    cen_off = torch.zeros(n_centroids + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(torch.bincount(key // corpus_len, minlength=n_centroids), 0, out=cen_off[1:])
+    return cen_off, (key % corpus_len).to(torch.int32)
+
+
+def train_centroids(rows, n_centroids, iters=10, seed=0, kernels=None):
+    """Unit-norm centroids bf16 [C, dp] of bf16 token rows [n, dp] by spherical k-means, deterministic for a seed:
+      init    C rows of a seeded permutation of the sample, normalised
+      assign  argmax_c <row, centroid_c> on the bf16 centroids (CorpusSearch, k = 1; ties to the lower id)
+      update  fp32 sum of a centroid's rows in sample order by ONE owner (stable sort by centroid, torch.segment_reduce: no floating-point
+              atomics), renormalised; an empty cluster is re-seeded with the next unused row of the permutation (wrapping around)."""
+    kn = _default_kernels(kernels)
+    n, C, dev = int(rows.shape[0]), int(n_centroids), rows.device
+    if rows.dtype != _BF16 or rows.dim() != 2 or not 1 <= C <= n:
+        raise ValueError(f"rows {rows.dtype} {tuple(rows.shape)} for {C} centroids; bf16 [n >= C, dp] expected")
+    order = torch.randperm(n, generator=torch.Generator().manual_seed(int(seed))).to(dev)
+    unit = lambda x: x / x.norm(dim=1, keepdim=True).clamp(min=1e-30)
+    x = rows.float()
+    cen, used = unit(x[order[:C]]).to(_BF16), C
+    for _ in range(int(iters)):
+        assign = _nearest(kn, rows, cen, 1)[:, 0]
+        counts = torch.bincount(assign, minlength=C)
+        sums = torch.segment_reduce(x[torch.sort(assign, stable=True).indices], "sum", lengths=counts, axis=0, unsafe=True)
+        empty = torch.nonzero(counts == 0).reshape(-1)
+        if empty.numel():
+            sums[empty] = x[order[(used + torch.arange(empty.numel(), device=dev)) % n]]
+            used += int(empty.numel())
+        cen = unit(sums).to(_BF16)
+    return cen
 
 
 # ---- product-quantised token rows (DESIGN.md section 12.1) ---------------------------------------------------------------------------
@@ -296,6 +503,9 @@ class ColBERTPQIndex(_TokenSearch):
 
     def quantize(self, *args, **kwargs):
         raise TypeError("the index is quantised already")
+
+    def search_pruned(self, *args, **kwargs):
+        raise NotImplementedError("centroid pruning: dense rows only (the candidate kernel reads ColBERTIndex.tok; decode() gives one)")
 
     def save(self, path):
         """One torch.save of the tensors (on the CPU) and sizes; load_pq_index reads it back."""

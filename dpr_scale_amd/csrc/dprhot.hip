@@ -37,6 +37,7 @@
 #include "ivf_pq.h"
 #include "router_head.h"
 #include "colbert.h"
+#include "colbert_cand.h"
 #include "colbert_pq.h"
 #include "spar.h"
 #include "dense_fp8.h"
@@ -2842,6 +2843,59 @@ int dprhot_colbert_search(const dprhot_bf16* tok, const int64_t* doc_blk, int64_
                             stream);
 }
 
+// ---- MaxSim over candidate lists (csrc/colbert_cand.h) ----
+static int cbc_check(const void* cand_off, const void* cand_doc, int64_t n_cand, int nq) {
+  REQUIRE(n_cand >= 0 && n_cand < (1ll << 40), "n_cand=%lld out of range (< 2^40)", (long long)n_cand);
+  REQUIRE(cand_off && (n_cand == 0 || cand_doc), "NULL pointer (cand_off and cand_doc are required)");
+  REQUIRE(nq <= 65535, "nq=%d: too many queries for one launch", nq);
+  return DPRHOT_OK;
+}
+
+int dprhot_colbert_cand_workspace_bytes(int nq, int chunk, size_t* bytes) { return dprhot_colbert_workspace_bytes(nq, chunk, bytes); }
+
+int dprhot_colbert_cand_score(const dprhot_bf16* tok, const int64_t* doc_blk, int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok,
+                              int nq, int LQ, int pool, const int64_t* cand_off, const int32_t* cand_doc, int64_t n_cand, int64_t pos_begin,
+                              int cols, float* S, int64_t ld, void* stream) {
+  if (int rc = cb_check(tok, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool)) return rc;
+  if (int rc = cbc_check(cand_off, cand_doc, n_cand, nq)) return rc;
+  if (int rc = check_score_window(S, cols, ld, pos_begin, 1ll << 31)) return rc;  // candidate positions, not doc ids: below 2^31
+  const int FQ = cdiv(LQ, 16);
+  CbcArgs a{reinterpret_cast<const uint16_t*>(tok), reinterpret_cast<const long long*>(doc_blk), (long long)n_blk, (long long)corpus_len, dp,
+            reinterpret_cast<const uint16_t*>(q_tok), nq, LQ, pool, reinterpret_cast<const long long*>(cand_off), cand_doc, (long long)n_cand,
+            (long long)pos_begin, cols, S, (long long)ld, FQ};
+  const dim3 grid((unsigned)cdiv(cols, CBC_RUNP), (unsigned)nq), block(256);
+  const size_t lds = (size_t)CBC_RUNP * (FQ * 16 + 1) * sizeof(float);  // the term table
+  hipStream_t st = (hipStream_t)stream;
+  switch (dp) {
+    case 32: return launch<cbc_score_kernel<1>>(grid, block, lds, st, a);
+    case 64: return launch<cbc_score_kernel<2>>(grid, block, lds, st, a);
+    case 96: return launch<cbc_score_kernel<3>>(grid, block, lds, st, a);
+    case 128: return launch<cbc_score_kernel<4>>(grid, block, lds, st, a);
+    default: return launch<cbc_score_kernel<0>>(grid, block, lds, st, a);
+  }
+}
+
+int dprhot_colbert_cand_search(const dprhot_bf16* tok, const int64_t* doc_blk, int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok,
+                               int nq, int LQ, int pool, const int64_t* cand_off, const int32_t* cand_doc, int64_t n_cand, int64_t max_count,
+                               int k, int chunk, float* values, int64_t* indices, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = cb_check(tok, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool)) return rc;
+  if (int rc = cbc_check(cand_off, cand_doc, n_cand, nq)) return rc;
+  REQUIRE(max_count > 0 && max_count < (1ll << 31), "max_count=%lld out of range (1 .. 2^31 - 1)", (long long)max_count);
+  REQUIRE(k >= 1 && k <= corpus_len, "topk=%d out of range (1 .. corpus_len=%lld)", k, (long long)corpus_len);
+  REQUIRE((long long)nq * k <= 0x7fffffffLL * 256, "nq=%d k=%d: too many result cells for one launch", nq, k);
+  auto fill = [&](int64_t j0, int cols, float* S, int ld) {
+    return dprhot_colbert_cand_score(tok, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool, cand_off, cand_doc, n_cand, j0, cols, S, ld,
+                                     stream);
+  };
+  // the driver walks candidate POSITIONS [0, max_count): its id space is the longer of the corpus and the longest list
+  if (int rc = topk_search_chunks("colbert_cand", fill, nq, max_count > corpus_len ? max_count : corpus_len, 0, max_count, k, chunk, values,
+                                  indices, 1, workspace, workspace_bytes, stream))
+    return rc;
+  const long long cells = (long long)nq * k;
+  return launch<cbc_map_kernel>(dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                                reinterpret_cast<const long long*>(cand_off), cand_doc, (long long)n_cand, nq, k,
+                                reinterpret_cast<long long*>(indices));
+}
 
 // ---- product-quantised token index of the ColBERT search (csrc/colbert_pq.h) ----
 static int cbpq_check_shape(int dp, int dsub) {

@@ -602,6 +602,33 @@ class HipKernels:
                                                        int(pool), *self._topk_tail(id_begin, id_end, values, indices, first, chunk, ws)),
                         "dprhot_colbert_search")
 
+    # -- MaxSim over candidate lists (csrc/colbert_cand.h) ---------------------------------------------
+    def colbert_cand_workspace(self, nq, chunk, k, like):
+        return self._chunk_workspace(self._lib.colbert_cand_workspace_bytes(nq, chunk), nq, k, like)
+
+    def _colbert_cand_head(self, index, q, pool, cand_off, cand_doc):
+        """tok .. n_cand: the arguments both candidate entry points begin with; cand_off int64 [nq + 1], cand_doc int32 [n_cand]."""
+        self._require_gpu(index.tok, index.doc_blk, q, cand_off, cand_doc)
+        nq, LQ, dp = q.shape
+        assert cand_off.dtype == torch.int64 and cand_doc.dtype == torch.int32 and cand_off.shape == (nq + 1,)
+        assert cand_off.is_contiguous() and cand_doc.is_contiguous()
+        return (_ptr(index.tok), _ptr(index.doc_blk), index.n_blk, index.corpus_len, dp, _ptr(q), nq, LQ, int(pool), _ptr(cand_off),
+                _ptr(cand_doc), int(cand_doc.shape[0]))
+
+    def colbert_cand_score(self, index, q, pool, cand_off, cand_doc, pos_begin, cols, S):
+        """Writes the scores of candidate positions pos_begin .. pos_begin + cols of every query's list into S [nq, >= cols] fp32; a
+        position without a candidate is NaN (dprhot_colbert_cand_score)."""
+        self._require_gpu(S)
+        self._lib.check(self.lib.dprhot_colbert_cand_score(*self._colbert_cand_head(index, q, pool, cand_off, cand_doc), int(pos_begin),
+                                                           int(cols), _ptr(S), S.stride(0), self._stream()), "dprhot_colbert_cand_score")
+
+    def colbert_cand_search(self, index, q, pool, cand_off, cand_doc, max_count, values, indices, chunk, ws):
+        """The top-k of every query's candidate list, as doc ids (dprhot_colbert_cand_search); always from an empty state."""
+        self._require_gpu(values, indices, ws)
+        self._lib.check(self.lib.dprhot_colbert_cand_search(*self._colbert_cand_head(index, q, pool, cand_off, cand_doc), int(max_count),
+                                                            values.shape[1], int(chunk), _ptr(values), _ptr(indices), _ptr(ws), ws.numel(),
+                                                            self._stream()), "dprhot_colbert_cand_search")
+
     # -- SPAR: two resident indexes, a grid of weights in one pass (csrc/spar.h; DESIGN.md section 13; dpr_scale_amd/spar.py) ----
     def spar_workspace(self, nq, W, chunk, k, like):
         return self._chunk_workspace(self._lib.spar_workspace_bytes(nq, W, chunk), W * nq, k, like)

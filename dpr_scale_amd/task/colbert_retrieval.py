@@ -11,6 +11,10 @@ ColBERTRetrievalTask            CITADELRetrievalTask's constructor, refusals, me
                                 encoder returns (padded query tokens are zero rows), with `query_pool` and `topk`.
 ColBERTPQRetrievalTask          ColBERTRetrievalTask over a product-quantised token index (colbert.ColBERTPQIndex, DESIGN.md section
                                 12.1): the same kwargs plus `sub_vec_dim` (8) and `save_quantized` (False).
+ColBERTPrunedRetrievalTask      ColBERTRetrievalTask with centroid pruning: the same kwargs plus `nprobe` and
+                                `n_centroids`; with both set the index gets centroids and queries go through search_pruned.  The two
+                                are class attributes of ColBERTRetrievalTask (None: exhaustive), whose constructor stays
+                                CITADELRetrievalTask's.  Over a product-quantised index pruning is refused (dense rows only).
 `kernels` (default: the HIP kernels) is the kernel object colbert.py takes.
 """
 import os
@@ -40,15 +44,42 @@ class GenerateColBERTEmbeddingsTask(GenerateMultiVecEmbeddingsTask):
 
 class ColBERTRetrievalTask(CITADELRetrievalTask):
     kernels = None
+    # centroid pruning: with BOTH set, `setup` gives the index centroids -- `centroids.pkl` beside the token
+    # files when present (ColBERTIndex.load_centroids), else build_centroids(n_centroids) -- and the task retrieves with search_pruned;
+    # with either None it is the exhaustive task.  The constructor is CITADELRetrievalTask's: ColBERTPrunedRetrievalTask takes the two
+    # as keyword arguments.
+    nprobe = None
+    n_centroids = None
+    CENTROID_FILE = "centroids.pkl"
+
+    def _pruned(self):
+        return self.nprobe is not None and self.n_centroids is not None
 
     def _load_index(self, device):
-        return colbert.load_index(self.ctx_embeddings_dir, len(self.ctxs), device, kernels=self.kernels)
+        index = colbert.load_index(self.ctx_embeddings_dir, len(self.ctxs), device, kernels=self.kernels)
+        if self._pruned():
+            path = os.path.join(self.ctx_embeddings_dir, self.CENTROID_FILE)
+            if os.path.exists(path):
+                index.load_centroids(path)
+            else:
+                index.build_centroids(int(self.n_centroids))
+        return index
 
     def _search(self, queries_repr, n, tic):
         if "expert_ids" in queries_repr:
             raise NotImplementedError("an encoder with expert_ids (COIL / CITADEL) is searched by CITADELRetrievalTask")
         self.latency["encode_time"] += time.perf_counter() - tic
+        if self._pruned():
+            return self.index.search_pruned(queries_repr["expert_repr"][:n], self.topk, int(self.nprobe), query_pool=self.query_pool)
         return self.index.search(queries_repr["expert_repr"][:n], self.topk, query_pool=self.query_pool)
+
+
+class ColBERTPrunedRetrievalTask(ColBERTRetrievalTask):
+    """ColBERTRetrievalTask with `nprobe` and `n_centroids` as constructor kwargs (both None: the exhaustive task)."""
+
+    def __init__(self, *args, nprobe=None, n_centroids=None, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.nprobe, self.n_centroids = nprobe, n_centroids
 
 
 class ColBERTPQRetrievalTask(ColBERTRetrievalTask):

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DPRHOT_VERSION 174 /* 0.1.74: + dprhot_ivf_workspace_bytes / _score / _search (inverted-index retrieval for CITADEL / COIL); dprhot_router_head_*, dprhot_ivf_compact / _gather, dprhot_maxsim_score and dprhot_pq_encode / dprhot_ivf_pq_score / _search, dprhot_colbert_* and dprhot_colbert_pq_* joined without a bump: tests/test_ivf.py pins this number */
+#define DPRHOT_VERSION 174 /* 0.1.74: + dprhot_ivf_workspace_bytes / _score / _search (inverted-index retrieval for CITADEL / COIL); dprhot_router_head_*, dprhot_ivf_compact / _gather, dprhot_maxsim_score and dprhot_pq_encode / dprhot_ivf_pq_score / _search, dprhot_colbert_*, dprhot_colbert_pq_* and dprhot_colbert_cand_* joined without a bump: tests/test_ivf.py pins this number */
 
 #define DPRHOT_OK 0
 #define DPRHOT_E_INVALID (-1)     /* bad argument (NULL pointer, non-positive or misaligned size) */
@@ -465,6 +465,38 @@ int dprhot_colbert_score(const dprhot_bf16* tok, const int64_t* doc_blk, int64_t
 int dprhot_colbert_search(const dprhot_bf16* tok, const int64_t* doc_blk, int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok,
                           int nq, int LQ, int pool, int64_t id_begin, int64_t id_end, int k, int chunk, float* values, int64_t* indices,
                           int first, void* workspace, size_t workspace_bytes, void* stream);
+
+/* MaxSim over candidate lists (csrc/colbert_cand.h): the score above for a different, ragged list of passages per
+ * query -- the hot path of ColBERT search with centroid pruning.  Index and queries as for dprhot_colbert_score.  Query n owns the
+ * entries cand_off[n] .. cand_off[n + 1] of cand_doc int32 [n_cand] (cand_off int64 [nq + 1]); its candidate at POSITION p is
+ * cand_doc[cand_off[n] + p].
+ * dprhot_colbert_cand_score WRITES S[n][j] for n < nq, j < cols, every cell and nothing else of S [nq, ld].  With p = pos_begin + j: where
+ * p is below the query's count and the doc id lies in [0, corpus_len), the cell is score(n, doc), bit for bit the cell
+ * dprhot_colbert_score writes for the same query rows and passage rows (the same MFMA operands, k order, fmaxf chain from 0, one owner
+ * pooling in ascending token order; no floating-point atomics).  Every other cell is a quiet NaN, "no candidate": both streaming top-k
+ * entry points never select a NaN.  A cell depends on its query's and its passage's rows only: not on the window, the rest of the list
+ * or the other queries; two runs are bit-identical.
+ * Bounds: a query's pair of cand_off is clamped to [0, n_cand] and an end below its begin counts as the begin; a doc id outside the
+ * corpus is never used as an index; block offsets are clamped to [0, n_blk], an end below its begin counts as the begin.  Nothing
+ * behind tok[n_blk * 16 * dp - 1], cand_doc[n_cand - 1] or doc_blk[corpus_len] is read whatever the lists hold.  n_cand == 0 (cand_doc
+ * may then be NULL), a query without candidates and a passage without tokens (score 0) are ordinary inputs.
+ * dprhot_colbert_cand_search runs positions [0, max_count) in chunks of `chunk` (a multiple of 8): the chunk's scores into the
+ * workspace, then the streaming top-k (dprhot_topk_update; dprhot_topk_update_wide for k > 4096) with col_offset = the chunk's first
+ * position, always from an empty state; ONE final launch replaces every selected position of row n by cand_doc[cand_off[n] + position]
+ * (-1 stays -1).  Lists sorted ascending and free of duplicates therefore give score descending with ties to the lower doc id; for any
+ * other list ties go to the lower POSITION, and a doc id listed twice may be returned twice.  A query with fewer than k candidates ends
+ * in -inf / -1.  max_count is the longest list's length (a shorter one only leaves the positions behind it unsearched).
+ * workspace: dprhot_colbert_cand_workspace_bytes(nq, chunk) (+ dprhot_topk_wide_workspace_bytes(nq, k) behind it when k > 4096);
+ * DPRHOT_E_WORKSPACE when smaller.
+ * Limits (DPRHOT_E_INVALID): those of dprhot_colbert_score, plus 0 <= n_cand < 2^40, nq <= 65535, 0 < max_count < 2^31,
+ * 0 <= pos_begin, pos_begin + cols < 2^31, 1 <= k <= corpus_len, chunk % 8 == 0; dp > 768: DPRHOT_E_UNSUPPORTED. */
+int dprhot_colbert_cand_workspace_bytes(int nq, int chunk, size_t* bytes);
+int dprhot_colbert_cand_score(const dprhot_bf16* tok, const int64_t* doc_blk, int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok,
+                              int nq, int LQ, int pool, const int64_t* cand_off, const int32_t* cand_doc, int64_t n_cand, int64_t pos_begin,
+                              int cols, float* S, int64_t ld, void* stream);
+int dprhot_colbert_cand_search(const dprhot_bf16* tok, const int64_t* doc_blk, int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok,
+                               int nq, int LQ, int pool, const int64_t* cand_off, const int32_t* cand_doc, int64_t n_cand, int64_t max_count,
+                               int k, int chunk, float* values, int64_t* indices, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Product-quantised token index for the ColBERT search (csrc/colbert_pq.h).  dsub in {2, 4, 8}, m = dp / dsub,
  * dp in {32, 64, 96, 128}, ONE codebook bf16 [m, 256, dsub] per index (the layout and the decode rule of the product-quantised postings
