@@ -135,6 +135,12 @@ SIGNATURES = {
                                           c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p]),
     "dprhot_colbert_cand_search": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                            c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dprhot_colbert_cen_table": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "dprhot_colbert_cen_workspace_bytes": (c_int, [c_int, c_int, POINTER(c_size_t)]),
+    "dprhot_colbert_cen_score": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                         c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "dprhot_colbert_cen_search": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                          c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dprhot_colbert_pq_encode": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "dprhot_colbert_pq_score": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int, c_int,
                                         c_int64, c_int, c_void_p, c_int64, c_void_p]),
@@ -272,6 +278,12 @@ def colbert_workspace_bytes(nq: int, chunk: int) -> int:
 def colbert_cand_workspace_bytes(nq: int, chunk: int) -> int:
     out = c_size_t(0)
     check(lib.dprhot_colbert_cand_workspace_bytes(int(nq), int(chunk), ctypes.byref(out)), "dprhot_colbert_cand_workspace_bytes")
+    return out.value
+
+
+def colbert_cen_workspace_bytes(nq: int, chunk: int) -> int:
+    out = c_size_t(0)
+    check(lib.dprhot_colbert_cen_workspace_bytes(int(nq), int(chunk), ctypes.byref(out)), "dprhot_colbert_cen_workspace_bytes")
     return out.value
 
 

@@ -31,9 +31,18 @@ passages -- with the exhaustive score, bit for bit (dprhot_colbert_cand_search) 
 the candidate set; what it may lose is a passage none of whose tokens lies in a probed centroid.  Assignment and probing are exact bf16
 top-k searches on the MFMA path (hotpath.CorpusSearch), ties to the lower centroid id.
 
+Centroid interaction: `search_pruned(..., ndocs=n)` first scores every candidate approximately, each passage
+token replaced by its centroid --
+
+    approx(n, doc) = POOL over query tokens i < LQ of  max(0, max over c in doc's centroid list of <q[n, i], centroid_c>)
+
+from a per-query table of query-token x centroid products (`centroid_table`) and the passages' sorted centroid lists (`doc_centroids`,
+built from `tok_centroid` on first use), keeps the best `ndocs` per query (dprhot_colbert_cen_search) and runs the exact score on those
+only: the result is the exhaustive top-k restricted to the survivors, bit for bit.  `approx` is, bit for bit, the exhaustive score of
+the index whose token rows are `centroids[tok_centroid]`.  No token row is read by the approximate stage.
+
 Not supported (out of scope): residual token vectors, compressed candidates (a candidate kernel over the product-quantised rows),
-PLAID's centroid-interaction stage (pruning the candidates by approximate scores from per-passage centroid codes; `tok_centroid` is
-kept so that it can follow), an index across several GPUs, a CPU index.
+PLAID's centroid-score threshold, an index across several GPUs, a CPU index.
 """
 import glob
 import os
@@ -49,6 +58,7 @@ _BF16 = torch.bfloat16
 _POOL = {"sum": 0, "max": 1}  # DPRHOT_POOL_SUM / DPRHOT_POOL_MAX
 BLOCK = 16                    # token rows per block: one MFMA fragment, one passage
 MAX_QUERY_LEN = 512           # DPRHOT_MAXSIM_MAX_LEN
+CEN_TABLE_BYTES = 1 << 28     # centroid interaction: queries go through in batches whose table fp32 [b, C, LT] stays under this (b >= 1)
 PQ_MAX_DP = 128               # dprhot_colbert_pq_score keeps the codebook (dp * 512 bytes) in LDS and the query fragments in registers
 
 
@@ -202,13 +212,14 @@ class ColBERTIndex(_TokenSearch):
         assert blk_rows is None or (blk_rows.dtype == torch.uint8 and blk_rows.shape == (self.n_blk,))
         self._blk_rows = blk_rows
         self.centroids = self.tok_centroid = self.cen_off = self.cen_doc = None  # build_centroids / load_centroids
+        self._doc_cen = None                                                      # doc_centroids, on first use
         self._init_search(chunk, kernels)
 
     @property
     def nbytes(self):
         """Bytes of device memory the index holds (token rows and block offsets; with centroids: those, the tokens' assignment and the
-        inverted lists)."""
-        held = (self.tok, self.doc_blk, self.centroids, self.tok_centroid, self.cen_off, self.cen_doc)
+        inverted lists; the per-passage centroid lists once doc_centroids has built them)."""
+        held = (self.tok, self.doc_blk, self.centroids, self.tok_centroid, self.cen_off, self.cen_doc) + (self._doc_cen or ())
         return sum(t.numel() * t.element_size() for t in held if t is not None)
 
     @property
@@ -273,6 +284,7 @@ class ColBERTIndex(_TokenSearch):
         assert tok_centroid.dtype == torch.int32 and tok_centroid.shape == (self.n_blk * BLOCK,)
         assert cen_off.dtype == torch.int64 and cen_off.shape == (C + 1,) and cen_doc.dtype == torch.int32 and cen_doc.dim() == 1
         self.centroids, self.tok_centroid, self.cen_off, self.cen_doc = centroids, tok_centroid, cen_off, cen_doc
+        self._doc_cen = None
 
     def _need_centroids(self):
         if self.centroids is None:
@@ -343,30 +355,115 @@ class ColBERTIndex(_TokenSearch):
         """fp32 [nq, max_count]: cell [n, p] is the exhaustive score of query n and its p-th candidate, bit for bit; a cell at or behind
         the query's count (or whose doc id lies outside the corpus) is NaN, "no candidate"."""
         pool, qb = self._pool(query_pool), self._queries(q)
-        cand_off = cand_off.to(self.device, torch.int64).contiguous()
-        cand_doc = cand_doc.to(self.device, torch.int32).contiguous()
-        if cand_off.shape != (qb.shape[0] + 1,):
-            raise ValueError(f"cand_off {tuple(cand_off.shape)} for {qb.shape[0]} queries")
-        off = cand_off.clamp(0, int(cand_doc.shape[0]))  # the kernel's own reading of a pair of offsets
-        max_count = int((off[1:] - off[:-1]).max().clamp(min=0))
+        cand_off, cand_doc, max_count = self._lists(qb, cand_off, cand_doc)
         S = torch.empty((qb.shape[0], max_count), dtype=torch.float32, device=self.device)
         if max_count:
             self._kernels().colbert_cand_score(self, qb, pool, cand_off, cand_doc, 0, max_count, S)
         return S
 
-    def search_pruned(self, q, topk, nprobe, query_pool="sum", chunk=None):
+    # ---- centroid interaction (DESIGN.md section 12.3) ----
+    def doc_centroids(self):
+        """(doc_cen_off int64 [corpus_len + 1], doc_cen int32): per passage the sorted, duplicate-free centroid ids of its stored tokens
+        -- the transpose of cen_off / cen_doc -- built on first use from tok_centroid (one torch.unique of doc * C + centroid) and kept;
+        a passage without tokens has an empty list."""
+        C = self._need_centroids()
+        if self._doc_cen is None:
+            self._doc_cen = _doc_centroid_lists(self.tok_centroid, self.doc_blk, C, self.corpus_len)
+        return self._doc_cen
+
+    def _centroid_table(self, qb):
+        nq, LQ, _ = qb.shape
+        T = torch.empty((nq, self._need_centroids(), (LQ + BLOCK - 1) // BLOCK * BLOCK), dtype=torch.float32, device=self.device)
+        self._kernels().colbert_cen_table(self, qb, T)
+        return T
+
+    def centroid_table(self, q):
+        """T fp32 [nq, C, LT], LT = 16 * ceil(LQ / 16): T[n, c, i] = <q[n, i], centroid_c> as the exhaustive kernel computes a token's
+        product; the columns behind LQ are 0."""
+        return self._centroid_table(self._queries(q))
+
+    def _cen_batches(self, qb):
+        """(lo, hi) query ranges whose centroid table stays under CEN_TABLE_BYTES, at least one query each."""
+        nq, LQ, _ = qb.shape
+        per_query = self._need_centroids() * ((LQ + BLOCK - 1) // BLOCK * BLOCK) * 4
+        step = max(1, CEN_TABLE_BYTES // per_query)
+        return [(lo, min(lo + step, nq)) for lo in range(0, nq, step)]
+
+    def _lists(self, qb, cand_off, cand_doc):
+        cand_off = cand_off.to(self.device, torch.int64).contiguous()
+        cand_doc = cand_doc.to(self.device, torch.int32).contiguous()
+        if cand_off.shape != (qb.shape[0] + 1,):
+            raise ValueError(f"cand_off {tuple(cand_off.shape)} for {qb.shape[0]} queries")
+        off = cand_off.clamp(0, int(cand_doc.shape[0]))  # the kernel's own reading of a pair of offsets
+        return cand_off, cand_doc, int((off[1:] - off[:-1]).max().clamp(min=0))
+
+    def approx_candidates(self, q, cand_off, cand_doc, query_pool="sum"):
+        """fp32 [nq, max_count]: cell [n, p] is approx(n, the query's p-th candidate); a cell at or behind the query's count (or whose
+        doc id lies outside the corpus) is NaN, "no candidate".  The mirror of score_candidates."""
+        pool, qb = self._pool(query_pool), self._queries(q)
+        cand_off, cand_doc, max_count = self._lists(qb, cand_off, cand_doc)
+        S = torch.empty((qb.shape[0], max_count), dtype=torch.float32, device=self.device)
+        if max_count:
+            kn = self._kernels()
+            for lo, hi in self._cen_batches(qb):
+                kn.colbert_cen_score(self, self._centroid_table(qb[lo:hi]), qb.shape[1], pool, cand_off[lo:hi + 1].contiguous(), cand_doc, 0,
+                                     max_count, S[lo:hi])
+        return S
+
+    def prune_candidates(self, q, cand_off, cand_doc, ndocs, query_pool="sum"):
+        """int32 [nq, ndocs]: per query its best `ndocs` candidates by approx (ties to the lower position of its list: the lower doc id
+        of a sorted list), the row sorted ascending with its -1 entries (fewer than ndocs candidates) first."""
+        pool, qb = self._pool(query_pool), self._queries(q)
+        cand_off, cand_doc, max_count = self._lists(qb, cand_off, cand_doc)
+        return self._prune(qb, pool, cand_off, cand_doc, max_count, int(ndocs))
+
+    def _prune(self, qb, pool, cand_off, cand_doc, max_count, ndocs, chunk=None):
+        if ndocs < 1:
+            raise ValueError(f"ndocs={ndocs} out of range (>= 1)")
+        nq, LQ, kn = int(qb.shape[0]), int(qb.shape[1]), self._kernels()
+        keep = torch.full((nq, ndocs), -1, dtype=torch.int64, device=self.device)
+        k = min(ndocs, self.corpus_len)
+        if max_count:
+            for lo, hi in self._cen_batches(qb):
+                T = self._centroid_table(qb[lo:hi])
+                c = self.default_chunk(hi - lo) if chunk is None else int(chunk)
+                c = max(8, min(c, (max_count + 7) // 8 * 8))
+                values = torch.empty((hi - lo, k), dtype=torch.float32, device=self.device)
+                indices = torch.empty((hi - lo, k), dtype=torch.int64, device=self.device)
+                ws = kn.colbert_cen_workspace(hi - lo, c, k, self.doc_blk)
+                kn.colbert_cen_search(self, T, LQ, pool, cand_off[lo:hi + 1].contiguous(), cand_doc, max_count, values, indices, c, ws)
+                keep[lo:hi, :k] = indices
+        return torch.sort(keep.to(torch.int32), dim=1).values
+
+    def search_pruned(self, q, topk, nprobe, query_pool="sum", chunk=None, ndocs=None):
         """`search` over the candidates of `candidates(q, nprobe)` only: (scores fp32 [nq, topk], ids int64 [nq, topk]), score
         descending with ties to the lower doc id -- the exhaustive top-k restricted to the candidate set, bit for bit.  A query with
-        fewer than topk candidates ends in -inf / -1.  latency: encode_time, candidate_time (probe and union), search_time."""
+        fewer than topk candidates ends in -inf / -1.  latency: encode_time, candidate_time (probe and union), search_time.
+
+        ndocs (>= topk; None: every candidate is scored exactly): the centroid-interaction stage keeps every query's best `ndocs`
+        candidates by approximate score (prune_candidates) and the exact score runs on those only -- the exhaustive top-k restricted
+        to the survivors, bit for bit.  The stage is skipped when no query has more than `ndocs` candidates.  latency gains
+        interaction_time."""
         pool, topk = self._pool(query_pool), int(topk)
         if not 1 <= topk <= self.corpus_len:
             raise ValueError(f"topk={topk} out of range (1 .. corpus_len={self.corpus_len})")
+        if ndocs is not None:
+            ndocs = int(ndocs)
+            if topk > ndocs:
+                raise ValueError(f"topk={topk} above ndocs={ndocs}: the exact stage scores ndocs candidates per query")
         tic = time.perf_counter()
         qb = self._queries(q)
         self.latency["encode_time"] += time.perf_counter() - tic
         tic = time.perf_counter()
         cand_off, cand_doc, _, max_count = self._candidates(qb, nprobe)
         self.latency["candidate_time"] += time.perf_counter() - tic
+        if ndocs is not None and ndocs < max_count:
+            tic = time.perf_counter()
+            # the survivors, sorted, ARE the exact stage's lists: -1 entries score NaN there, so nothing is compacted or read back
+            cand_doc = self._prune(qb, pool, cand_off, cand_doc, max_count, ndocs, chunk).reshape(-1)
+            cand_off = torch.arange(qb.shape[0] + 1, dtype=torch.int64, device=self.device) * ndocs
+            max_count = ndocs
+            self.latency["interaction_time"] += time.perf_counter() - tic
         tic = time.perf_counter()
         out = self._search_candidates(qb, pool, topk, cand_off, cand_doc, max_count, chunk)
         self.latency["search_time"] += time.perf_counter() - tic
@@ -408,6 +505,17 @@ def _centroid_lists(tok_centroid, doc_blk, n_centroids, corpus_len):
     cen_off = torch.zeros(n_centroids + 1, dtype=torch.int64, device=dev)
     torch.cumsum(torch.bincount(key // corpus_len, minlength=n_centroids), 0, out=cen_off[1:])
     return cen_off, (key % corpus_len).to(torch.int32)
+
+
+def _doc_centroid_lists(tok_centroid, doc_blk, n_centroids, corpus_len):
+    """(doc_cen_off int64 [corpus_len + 1], doc_cen int32): per passage the sorted, duplicate-free centroid ids of its stored tokens."""
+    dev = tok_centroid.device
+    doc_of_blk = torch.repeat_interleave(torch.arange(corpus_len, device=dev), doc_blk[1:] - doc_blk[:-1])
+    real = torch.nonzero(tok_centroid >= 0).reshape(-1)
+    key = torch.unique(doc_of_blk[real // BLOCK] * n_centroids + tok_centroid[real].to(torch.int64))
+    doc_cen_off = torch.zeros(corpus_len + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(torch.bincount(key // n_centroids, minlength=corpus_len), 0, out=doc_cen_off[1:])
+    return doc_cen_off, (key % n_centroids).to(torch.int32)
 
 
 def train_centroids(rows, n_centroids, iters=10, seed=0, kernels=None):

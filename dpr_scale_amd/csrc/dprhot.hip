@@ -38,6 +38,7 @@
 #include "router_head.h"
 #include "colbert.h"
 #include "colbert_cand.h"
+#include "colbert_cen.h"
 #include "colbert_pq.h"
 #include "spar.h"
 #include "dense_fp8.h"
@@ -2875,26 +2876,104 @@ int dprhot_colbert_cand_score(const dprhot_bf16* tok, const int64_t* doc_blk, in
   }
 }
 
-int dprhot_colbert_cand_search(const dprhot_bf16* tok, const int64_t* doc_blk, int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok,
-                               int nq, int LQ, int pool, const int64_t* cand_off, const int32_t* cand_doc, int64_t n_cand, int64_t max_count,
-                               int k, int chunk, float* values, int64_t* indices, void* workspace, size_t workspace_bytes, void* stream) {
-  if (int rc = cb_check(tok, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool)) return rc;
-  if (int rc = cbc_check(cand_off, cand_doc, n_cand, nq)) return rc;
+extern "C++" {
+// dprhot_colbert_cand_search and dprhot_colbert_cen_search behind their own checks: the chunk driver over candidate POSITIONS
+// [0, max_count), fill(j0, cols, S, ld) scoring a window of them, then the one launch from positions to doc ids
+template <class Fill>
+static int cbc_search_with(const char* who, Fill fill, int nq, int64_t corpus_len, const int64_t* cand_off, const int32_t* cand_doc,
+                           int64_t n_cand, int64_t max_count, int k, int chunk, float* values, int64_t* indices, void* workspace,
+                           size_t workspace_bytes, void* stream) {
   REQUIRE(max_count > 0 && max_count < (1ll << 31), "max_count=%lld out of range (1 .. 2^31 - 1)", (long long)max_count);
   REQUIRE(k >= 1 && k <= corpus_len, "topk=%d out of range (1 .. corpus_len=%lld)", k, (long long)corpus_len);
   REQUIRE((long long)nq * k <= 0x7fffffffLL * 256, "nq=%d k=%d: too many result cells for one launch", nq, k);
-  auto fill = [&](int64_t j0, int cols, float* S, int ld) {
-    return dprhot_colbert_cand_score(tok, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool, cand_off, cand_doc, n_cand, j0, cols, S, ld,
-                                     stream);
-  };
-  // the driver walks candidate POSITIONS [0, max_count): its id space is the longer of the corpus and the longest list
-  if (int rc = topk_search_chunks("colbert_cand", fill, nq, max_count > corpus_len ? max_count : corpus_len, 0, max_count, k, chunk, values,
-                                  indices, 1, workspace, workspace_bytes, stream))
+  // the driver's id space is the longer of the corpus and the longest list
+  if (int rc = topk_search_chunks(who, fill, nq, max_count > corpus_len ? max_count : corpus_len, 0, max_count, k, chunk, values, indices, 1,
+                                  workspace, workspace_bytes, stream))
     return rc;
   const long long cells = (long long)nq * k;
   return launch<cbc_map_kernel>(dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                                 reinterpret_cast<const long long*>(cand_off), cand_doc, (long long)n_cand, nq, k,
                                 reinterpret_cast<long long*>(indices));
+}
+}  // extern "C++"
+
+int dprhot_colbert_cand_search(const dprhot_bf16* tok, const int64_t* doc_blk, int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok,
+                               int nq, int LQ, int pool, const int64_t* cand_off, const int32_t* cand_doc, int64_t n_cand, int64_t max_count,
+                               int k, int chunk, float* values, int64_t* indices, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = cb_check(tok, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool)) return rc;
+  if (int rc = cbc_check(cand_off, cand_doc, n_cand, nq)) return rc;
+  auto fill = [&](int64_t j0, int cols, float* S, int ld) {
+    return dprhot_colbert_cand_score(tok, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool, cand_off, cand_doc, n_cand, j0, cols, S, ld,
+                                     stream);
+  };
+  return cbc_search_with("colbert_cand", fill, nq, corpus_len, cand_off, cand_doc, n_cand, max_count, k, chunk, values, indices, workspace,
+                         workspace_bytes, stream);
+}
+
+// ---- centroid interaction: approximate scores over candidate lists (csrc/colbert_cen.h) ----
+static int cbi_check_query(int nq, int LQ, int C) {
+  REQUIRE(LQ >= 1 && LQ <= DPRHOT_MAXSIM_MAX_LEN, "LQ=%d out of range (1 .. %d)", LQ, DPRHOT_MAXSIM_MAX_LEN);
+  REQUIRE(C >= 1, "C=%d out of range (1 .. 2^31 - 1)", C);
+  REQUIRE(nq > 0 && nq <= 65535, "bad shape nq=%d (1 .. 65535 queries in one launch)", nq);
+  return DPRHOT_OK;
+}
+
+static int cbi_check(const void* doc_cen_off, const void* doc_cen, int64_t n_pairs, int64_t corpus_len, int C, const void* T, int nq, int LQ,
+                     int pool) {
+  REQUIRE(corpus_len > 0 && corpus_len < (1ll << 31), "corpus_len=%lld out of range (1 .. 2^31 - 1)", (long long)corpus_len);
+  REQUIRE(n_pairs >= 0 && n_pairs < (1ll << 40), "n_pairs=%lld out of range (< 2^40)", (long long)n_pairs);
+  if (int rc = cbi_check_query(nq, LQ, C)) return rc;
+  REQUIRE(pool == DPRHOT_POOL_SUM || pool == DPRHOT_POOL_MAX, "unknown pool %d", pool);
+  REQUIRE(doc_cen_off && T && (n_pairs == 0 || doc_cen), "NULL pointer (doc_cen_off, doc_cen and T are required)");
+  REQUIRE(aligned16(T), "the centroid table must be 16-byte aligned");
+  return DPRHOT_OK;
+}
+
+int dprhot_colbert_cen_table(const dprhot_bf16* centroids, int C, int dp, const dprhot_bf16* q_tok, int nq, int LQ, float* T, void* stream) {
+  REQUIRE(dp > 0 && dp % 32 == 0, "dp=%d must be a positive multiple of 32 (pad with zeros)", dp);
+  if (int rc = cbi_check_query(nq, LQ, C)) return rc;
+  REQUIRE(centroids && q_tok && T, "NULL pointer (centroids, q_tok and T are required)");
+  REQUIRE(aligned16(centroids) && aligned16(q_tok), "centroid and token rows must be 16-byte aligned");
+  if (dp > CB_MAX_DP) return fail(DPRHOT_E_UNSUPPORTED, "dp=%d: the ColBERT search is built for dp <= %d", dp, CB_MAX_DP);
+  CbiTableArgs a{reinterpret_cast<const uint16_t*>(centroids), C, dp, reinterpret_cast<const uint16_t*>(q_tok), nq, LQ, cdiv(LQ, 16), T};
+  const dim3 grid((unsigned)(((long long)C + 63) / 64), (unsigned)nq), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  switch (dp) {
+    case 32: return launch<cbi_table_kernel<1>>(grid, block, 0, st, a);
+    case 64: return launch<cbi_table_kernel<2>>(grid, block, 0, st, a);
+    case 96: return launch<cbi_table_kernel<3>>(grid, block, 0, st, a);
+    case 128: return launch<cbi_table_kernel<4>>(grid, block, 0, st, a);
+    default: return launch<cbi_table_kernel<0>>(grid, block, 0, st, a);
+  }
+}
+
+int dprhot_colbert_cen_workspace_bytes(int nq, int chunk, size_t* bytes) { return dprhot_colbert_workspace_bytes(nq, chunk, bytes); }
+
+int dprhot_colbert_cen_score(const int64_t* doc_cen_off, const int32_t* doc_cen, int64_t n_pairs, int64_t corpus_len, int C, const float* T,
+                             int nq, int LQ, int pool, const int64_t* cand_off, const int32_t* cand_doc, int64_t n_cand, int64_t pos_begin,
+                             int cols, float* S, int64_t ld, void* stream) {
+  if (int rc = cbi_check(doc_cen_off, doc_cen, n_pairs, corpus_len, C, T, nq, LQ, pool)) return rc;
+  if (int rc = cbc_check(cand_off, cand_doc, n_cand, nq)) return rc;
+  if (int rc = check_score_window(S, cols, ld, pos_begin, 1ll << 31)) return rc;  // candidate positions, not doc ids: below 2^31
+  const int LT = cdiv(LQ, 16) * 16;
+  CbiArgs a{reinterpret_cast<const long long*>(doc_cen_off), doc_cen, (long long)n_pairs, (long long)corpus_len, C, T, nq, LQ, pool,
+            reinterpret_cast<const long long*>(cand_off), cand_doc, (long long)n_cand, (long long)pos_begin, cols, S, (long long)ld, LT};
+  const dim3 grid((unsigned)cdiv(cols, CBC_RUNP), (unsigned)nq), block(256);
+  const size_t lds = (size_t)CBC_RUNP * (LT + 1) * sizeof(float);  // the term table
+  return launch<cbi_score_kernel>(grid, block, lds, (hipStream_t)stream, a);
+}
+
+int dprhot_colbert_cen_search(const int64_t* doc_cen_off, const int32_t* doc_cen, int64_t n_pairs, int64_t corpus_len, int C, const float* T,
+                              int nq, int LQ, int pool, const int64_t* cand_off, const int32_t* cand_doc, int64_t n_cand, int64_t max_count,
+                              int k, int chunk, float* values, int64_t* indices, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = cbi_check(doc_cen_off, doc_cen, n_pairs, corpus_len, C, T, nq, LQ, pool)) return rc;
+  if (int rc = cbc_check(cand_off, cand_doc, n_cand, nq)) return rc;
+  auto fill = [&](int64_t j0, int cols, float* S, int ld) {
+    return dprhot_colbert_cen_score(doc_cen_off, doc_cen, n_pairs, corpus_len, C, T, nq, LQ, pool, cand_off, cand_doc, n_cand, j0, cols, S, ld,
+                                    stream);
+  };
+  return cbc_search_with("colbert_cen", fill, nq, corpus_len, cand_off, cand_doc, n_cand, max_count, k, chunk, values, indices, workspace,
+                         workspace_bytes, stream);
 }
 
 // ---- product-quantised token index of the ColBERT search (csrc/colbert_pq.h) ----

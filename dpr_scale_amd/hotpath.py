@@ -629,6 +629,46 @@ class HipKernels:
                                                             values.shape[1], int(chunk), _ptr(values), _ptr(indices), _ptr(ws), ws.numel(),
                                                             self._stream()), "dprhot_colbert_cand_search")
 
+    # -- centroid interaction over candidate lists (csrc/colbert_cen.h) --------------------------------
+    def colbert_cen_workspace(self, nq, chunk, k, like):
+        return self._chunk_workspace(self._lib.colbert_cen_workspace_bytes(nq, chunk), nq, k, like)
+
+    def colbert_cen_table(self, index, q, T):
+        """Writes T fp32 [nq, C, LT], LT = 16 * ceil(LQ / 16): T[n, c, i] = <q[n, i], centroid_c>, zeros behind LQ
+        (dprhot_colbert_cen_table); q bf16 [nq, LQ, dp]."""
+        self._require_gpu(index.centroids, q, T)
+        nq, LQ, dp = q.shape
+        C = int(index.centroids.shape[0])
+        assert T.dtype == torch.float32 and T.is_contiguous() and T.shape == (nq, C, (LQ + 15) // 16 * 16)
+        self._lib.check(self.lib.dprhot_colbert_cen_table(_ptr(index.centroids), C, dp, _ptr(q), nq, LQ, _ptr(T), self._stream()),
+                        "dprhot_colbert_cen_table")
+
+    def _colbert_cen_head(self, index, T, LQ, pool, cand_off, cand_doc):
+        """doc_cen_off .. n_cand: the arguments both centroid-interaction entry points begin with; T fp32 [nq, C, LT]."""
+        doc_cen_off, doc_cen = index.doc_centroids()
+        self._require_gpu(doc_cen_off, doc_cen, T, cand_off, cand_doc)
+        nq, C, LT = T.shape
+        assert T.dtype == torch.float32 and T.is_contiguous() and LT == (int(LQ) + 15) // 16 * 16
+        assert cand_off.dtype == torch.int64 and cand_doc.dtype == torch.int32 and cand_off.shape == (nq + 1,)
+        assert cand_off.is_contiguous() and cand_doc.is_contiguous()
+        return (_ptr(doc_cen_off), _ptr(doc_cen), int(doc_cen.shape[0]), index.corpus_len, C, _ptr(T), nq, int(LQ), int(pool),
+                _ptr(cand_off), _ptr(cand_doc), int(cand_doc.shape[0]))
+
+    def colbert_cen_score(self, index, T, LQ, pool, cand_off, cand_doc, pos_begin, cols, S):
+        """Writes the approximate scores of candidate positions pos_begin .. pos_begin + cols of every query's list into S [nq, >= cols]
+        fp32; a position without a candidate is NaN (dprhot_colbert_cen_score)."""
+        self._require_gpu(S)
+        self._lib.check(self.lib.dprhot_colbert_cen_score(*self._colbert_cen_head(index, T, LQ, pool, cand_off, cand_doc), int(pos_begin),
+                                                          int(cols), _ptr(S), S.stride(0), self._stream()), "dprhot_colbert_cen_score")
+
+    def colbert_cen_search(self, index, T, LQ, pool, cand_off, cand_doc, max_count, values, indices, chunk, ws):
+        """The top-k of every query's candidate list by approximate score, as doc ids (dprhot_colbert_cen_search); always from an empty
+        state."""
+        self._require_gpu(values, indices, ws)
+        self._lib.check(self.lib.dprhot_colbert_cen_search(*self._colbert_cen_head(index, T, LQ, pool, cand_off, cand_doc), int(max_count),
+                                                           values.shape[1], int(chunk), _ptr(values), _ptr(indices), _ptr(ws), ws.numel(),
+                                                           self._stream()), "dprhot_colbert_cen_search")
+
     # -- SPAR: two resident indexes, a grid of weights in one pass (csrc/spar.h; DESIGN.md section 13; dpr_scale_amd/spar.py) ----
     def spar_workspace(self, nq, W, chunk, k, like):
         return self._chunk_workspace(self._lib.spar_workspace_bytes(nq, W, chunk), W * nq, k, like)

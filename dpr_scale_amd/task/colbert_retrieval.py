@@ -12,8 +12,9 @@ ColBERTRetrievalTask            CITADELRetrievalTask's constructor, refusals, me
 ColBERTPQRetrievalTask          ColBERTRetrievalTask over a product-quantised token index (colbert.ColBERTPQIndex, DESIGN.md section
                                 12.1): the same kwargs plus `sub_vec_dim` (8) and `save_quantized` (False).
 ColBERTPrunedRetrievalTask      ColBERTRetrievalTask with centroid pruning: the same kwargs plus `nprobe` and
-                                `n_centroids`; with both set the index gets centroids and queries go through search_pruned.  The two
-                                are class attributes of ColBERTRetrievalTask (None: exhaustive), whose constructor stays
+                                `n_centroids`; with both set the index gets centroids and queries go through search_pruned, with
+                                `ndocs` (None: every candidate is scored exactly) as its centroid-interaction stage (section 12.3).
+                                The three are class attributes of ColBERTRetrievalTask (None: exhaustive), whose constructor stays
                                 CITADELRetrievalTask's.  Over a product-quantised index pruning is refused (dense rows only).
 `kernels` (default: the HIP kernels) is the kernel object colbert.py takes.
 """
@@ -50,6 +51,7 @@ class ColBERTRetrievalTask(CITADELRetrievalTask):
     # as keyword arguments.
     nprobe = None
     n_centroids = None
+    ndocs = None  # with pruning on: search_pruned keeps the best ndocs candidates per query by approximate score
     CENTROID_FILE = "centroids.pkl"
 
     def _pruned(self):
@@ -70,16 +72,17 @@ class ColBERTRetrievalTask(CITADELRetrievalTask):
             raise NotImplementedError("an encoder with expert_ids (COIL / CITADEL) is searched by CITADELRetrievalTask")
         self.latency["encode_time"] += time.perf_counter() - tic
         if self._pruned():
-            return self.index.search_pruned(queries_repr["expert_repr"][:n], self.topk, int(self.nprobe), query_pool=self.query_pool)
+            stage = {} if self.ndocs is None else dict(ndocs=int(self.ndocs))
+            return self.index.search_pruned(queries_repr["expert_repr"][:n], self.topk, int(self.nprobe), query_pool=self.query_pool, **stage)
         return self.index.search(queries_repr["expert_repr"][:n], self.topk, query_pool=self.query_pool)
 
 
 class ColBERTPrunedRetrievalTask(ColBERTRetrievalTask):
-    """ColBERTRetrievalTask with `nprobe` and `n_centroids` as constructor kwargs (both None: the exhaustive task)."""
+    """ColBERTRetrievalTask with `nprobe`, `n_centroids` and `ndocs` as constructor kwargs (the first two None: the exhaustive task)."""
 
-    def __init__(self, *args, nprobe=None, n_centroids=None, **kwargs):
+    def __init__(self, *args, nprobe=None, n_centroids=None, ndocs=None, **kwargs):
         super().__init__(*args, **kwargs)
-        self.nprobe, self.n_centroids = nprobe, n_centroids
+        self.nprobe, self.n_centroids, self.ndocs = nprobe, n_centroids, ndocs
 
 
 class ColBERTPQRetrievalTask(ColBERTRetrievalTask):

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DPRHOT_VERSION 174 /* 0.1.74: + dprhot_ivf_workspace_bytes / _score / _search (inverted-index retrieval for CITADEL / COIL); dprhot_router_head_*, dprhot_ivf_compact / _gather, dprhot_maxsim_score and dprhot_pq_encode / dprhot_ivf_pq_score / _search, dprhot_colbert_*, dprhot_colbert_pq_* and dprhot_colbert_cand_* joined without a bump: tests/test_ivf.py pins this number */
+#define DPRHOT_VERSION 174 /* 0.1.74: + dprhot_ivf_workspace_bytes / _score / _search (inverted-index retrieval for CITADEL / COIL); dprhot_router_head_*, dprhot_ivf_compact / _gather, dprhot_maxsim_score and dprhot_pq_encode / dprhot_ivf_pq_score / _search, dprhot_colbert_*, dprhot_colbert_pq_*, dprhot_colbert_cand_* and dprhot_colbert_cen_* joined without a bump: tests/test_ivf.py pins this number */
 
 #define DPRHOT_OK 0
 #define DPRHOT_E_INVALID (-1)     /* bad argument (NULL pointer, non-positive or misaligned size) */
@@ -497,6 +497,41 @@ int dprhot_colbert_cand_score(const dprhot_bf16* tok, const int64_t* doc_blk, in
 int dprhot_colbert_cand_search(const dprhot_bf16* tok, const int64_t* doc_blk, int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok,
                                int nq, int LQ, int pool, const int64_t* cand_off, const int32_t* cand_doc, int64_t n_cand, int64_t max_count,
                                int k, int chunk, float* values, int64_t* indices, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Centroid interaction (csrc/colbert_cen.h): every candidate of a list scored approximately, each passage token
+ * replaced by its centroid, so that the exact score above is computed for the best few only.  centroids bf16 [C, dp]; per passage the
+ * sorted, duplicate-free centroid ids of its stored tokens, doc_cen int32 [n_pairs] under doc_cen_off int64 [corpus_len + 1].
+ * dprhot_colbert_cen_table WRITES every cell of T fp32 [nq, C, LT], LT = 16 * ceil(LQ / 16), and nothing else:
+ *   T[n][c][i] = <q_tok[n, i], centroid_c> for i < LQ, 0 for LQ <= i < LT
+ * each product computed as dprhot_colbert_score computes a token's (the centroid block is the MFMA's A operand, 16 query tokens are B,
+ * k-steps ascending from a zero accumulator).
+ * dprhot_colbert_cen_score has the window contract of dprhot_colbert_cand_score: it WRITES S[n][j] for n < nq, j < cols, every cell and
+ * nothing else of S [nq, ld].  With p = pos_begin + j: where p is below the query's count and the doc id lies in [0, corpus_len), the
+ * cell is
+ *   approx(n, doc) = POOL over i < LQ of max(0, max over c in doc's list of T[n][c][i])
+ * every maximum an fmaxf from a start of 0, ONE owner pooling the LQ terms in ascending token order, no floating-point atomics: bit for
+ * bit the cell dprhot_colbert_score writes for an index of the same doc_blk whose token rows are centroids[tok_centroid] (zero rows on
+ * padding).  Every other cell is the quiet NaN of dprhot_colbert_cand_score.  A cell depends on its query's table and its passage's
+ * list only; two runs are bit-identical.
+ * Bounds: a pair of cand_off is clamped to [0, n_cand] and a pair of doc_cen_off to [0, n_pairs], an end below its begin counts as the
+ * begin; a doc id outside the corpus is never used as an index; a centroid id outside [0, C) is skipped and never used as an index; an
+ * empty list scores 0.  Nothing behind doc_cen[n_pairs - 1], doc_cen_off[corpus_len], cand_doc[n_cand - 1] or T[nq * C * LT - 1] is
+ * read whatever the lists hold.  n_pairs == 0 and n_cand == 0 are ordinary inputs (doc_cen / cand_doc may then be NULL).
+ * dprhot_colbert_cen_search is dprhot_colbert_cand_search with this score: positions [0, max_count) in chunks, the streaming top-k from
+ * an empty state, ONE final launch from positions to doc ids; approx descending, ties to the lower position, -inf / -1 tails.
+ * workspace: dprhot_colbert_cen_workspace_bytes(nq, chunk) = dprhot_colbert_workspace_bytes(nq, chunk) (+
+ * dprhot_topk_wide_workspace_bytes(nq, k) behind it when k > 4096); DPRHOT_E_WORKSPACE when smaller.
+ * Limits (DPRHOT_E_INVALID): 1 <= LQ <= DPRHOT_MAXSIM_MAX_LEN, 1 <= C < 2^31, 1 <= nq <= 65535, dp % 32 == 0 (table), corpus_len < 2^31,
+ * 0 <= n_pairs < 2^40, 0 <= n_cand < 2^40, T 16-byte aligned, 0 < max_count < 2^31, 0 <= pos_begin, pos_begin + cols < 2^31,
+ * 1 <= k <= corpus_len, chunk % 8 == 0, pool one of DPRHOT_POOL_SUM / DPRHOT_POOL_MAX; dp > 768: DPRHOT_E_UNSUPPORTED. */
+int dprhot_colbert_cen_table(const dprhot_bf16* centroids, int C, int dp, const dprhot_bf16* q_tok, int nq, int LQ, float* T, void* stream);
+int dprhot_colbert_cen_workspace_bytes(int nq, int chunk, size_t* bytes);
+int dprhot_colbert_cen_score(const int64_t* doc_cen_off, const int32_t* doc_cen, int64_t n_pairs, int64_t corpus_len, int C, const float* T,
+                             int nq, int LQ, int pool, const int64_t* cand_off, const int32_t* cand_doc, int64_t n_cand, int64_t pos_begin,
+                             int cols, float* S, int64_t ld, void* stream);
+int dprhot_colbert_cen_search(const int64_t* doc_cen_off, const int32_t* doc_cen, int64_t n_pairs, int64_t corpus_len, int C, const float* T,
+                              int nq, int LQ, int pool, const int64_t* cand_off, const int32_t* cand_doc, int64_t n_cand, int64_t max_count,
+                              int k, int chunk, float* values, int64_t* indices, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Product-quantised token index for the ColBERT search (csrc/colbert_pq.h).  dsub in {2, 4, 8}, m = dp / dsub,
  * dp in {32, 64, 96, 128}, ONE codebook bf16 [m, 256, dsub] per index (the layout and the decode rule of the product-quantised postings
