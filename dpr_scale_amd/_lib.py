@@ -141,6 +141,12 @@ SIGNATURES = {
                                          c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p]),
     "dprhot_colbert_cen_search": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                           c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dprhot_colbert_res_encode": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "dprhot_colbert_res_score": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p,
+                                         c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "dprhot_colbert_res_search": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p,
+                                          c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_int, c_int, c_void_p, c_void_p,
+                                          c_void_p, c_size_t, c_void_p]),
     "dprhot_colbert_pq_encode": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "dprhot_colbert_pq_score": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int, c_int, c_int,
                                         c_int64, c_int, c_void_p, c_int64, c_void_p]),

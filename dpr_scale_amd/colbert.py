@@ -41,8 +41,15 @@ built from `tok_centroid` on first use), keeps the best `ndocs` per query (dprho
 only: the result is the exhaustive top-k restricted to the survivors, bit for bit.  `approx` is, bit for bit, the exhaustive score of
 the index whose token rows are `centroids[tok_centroid]`.  No token row is read by the approximate stage.
 
-Not supported (out of scope): residual token vectors, compressed candidates (a candidate kernel over the product-quantised rows),
-PLAID's centroid-score threshold, an index across several GPUs, a CPU index.
+Residual compression: `ColBERTIndex.compress(nbits)` / `load_index(..., quantizer="residual")` /
+`TokenIndexBuilder.finish(quantizer="residual")` give a `ColBERTResidualIndex`, the ColBERTv2 format: per token its centroid id (the
+`tok_centroid` the pruned search already holds) plus 1, 2 or 4 bits per feature of row - centroid under one bucket set (20, 36 or 68
+bytes per token at d = 128 instead of 256).  It is searched with centroid pruning only: probing, the inverted lists and the centroid
+interaction are shared with the dense index (the `_CentroidPruning` mixin) and the exact stage decodes the surviving candidates at the
+MFMA's operand read (dprhot_colbert_res_search).  Every result is, bit for bit, that of `ColBERTResidualIndex.decode()`.
+
+Not supported (out of scope): a residual index searched exhaustively, a candidate kernel over the product-quantised rows, per-dimension
+buckets, PLAID's centroid-score threshold, an index across several GPUs, a CPU index.
 """
 import glob
 import os
@@ -160,123 +167,14 @@ class _TokenSearch(ChunkedIndex):
         return S
 
 
-class ColBERTIndex(_TokenSearch):
-    """Device-resident token index of a ColBERT corpus; `search` is the exhaustive MaxSim top-k."""
+class _CentroidPruning:
+    """The pruned search that the dense and the residual token index share (DESIGN.md sections 12.2 to 12.4): centroids, probing, the
+    union of inverted lists, the centroid-interaction stage and `search_pruned`.  A class mixes it into a _TokenSearch that sets device,
+    doc_blk, corpus_len, d, dp and n_blk, calls `_set_centroids`, and supplies the exact stage as two hooks:
+      _score_lists(kn, qb, pool, cand_off, cand_doc, pos_begin, cols, S)                       a window of candidate positions into S
+      _search_lists(kn, qb, pool, cand_off, cand_doc, max_count, values, indices, chunk)      the top-k of every list, as doc ids"""
 
-    _SEARCH, _SCORE = "colbert_search", "colbert_score"
-
-    def __init__(self, doc_ids, lengths, rows, corpus_len, device, chunk=None, kernels=None):
-        """From unpadded token rows grouped by passage: doc_ids int64 [n], lengths [n] (tokens of each passage), rows [sum(lengths), d]
-        in the order of doc_ids.  Ids that never appear get zero blocks; an id given twice is a ValueError."""
-        corpus_len = int(corpus_len)
-        if not 0 < corpus_len < 2 ** 31:
-            raise ValueError(f"corpus_len={corpus_len} out of range (1 .. 2^31 - 1)")
-        device = torch.device(device)
-        rows = torch.as_tensor(rows).to(device)
-        if rows.dim() != 2:
-            raise ValueError(f"rows {tuple(rows.shape)}; [sum(lengths), d] expected")
-        ids, lens, doc_len, doc_blk = _layout(doc_ids, lengths, corpus_len, device)
-        if int(lens.sum()) != rows.shape[0]:
-            raise ValueError(f"{rows.shape[0]} token rows for lengths that sum to {int(lens.sum())}")
-        d = int(rows.shape[1])
-        dp = (max(d, 1) + 31) // 32 * 32
-        n_blk = int(doc_blk[-1])
-        tok = torch.zeros((n_blk * BLOCK, dp), dtype=_BF16, device=device)
-        if rows.shape[0]:
-            tok[_dest_rows(doc_blk, ids, lens), :d] = rows.to(_BF16)
-        self._set(tok, doc_blk, corpus_len, d, chunk, kernels, _blk_rows(doc_len, doc_blk))
-
-    @classmethod
-    def from_packed(cls, tok, doc_blk, corpus_len, d, chunk=None, kernels=None, blk_rows=None):
-        """From tensors already in the device layout (csrc/colbert.h), on their device: tok bf16 [n_blk * 16, dp], doc_blk int64
-        [corpus_len + 1].  blk_rows uint8 [n_blk] (the real token rows of every block; only `quantize` reads it) defaults to the rows
-        up to a block's last non-zero one."""
-        self = cls.__new__(cls)
-        self._set(tok, doc_blk, int(corpus_len), int(d), chunk, kernels, blk_rows)
-        return self
-
-    @classmethod
-    def from_repr(cls, expert_repr, attention, corpus_ids, corpus_len, device=None, chunk=None, kernels=None):
-        """From a padded batch: expert_repr [N, LD, d], attention [N, LD]; the slots with attention > 0 are kept, in order."""
-        device = expert_repr.device if device is None else device
-        ids, lens, rows = _kept_rows(expert_repr, attention, corpus_ids)
-        return cls(ids, lens, rows, corpus_len, device, chunk=chunk, kernels=kernels)
-
-    def _set(self, tok, doc_blk, corpus_len, d, chunk, kernels, blk_rows=None):
-        assert tok.dtype == _BF16 and doc_blk.dtype == torch.int64 and tok.dim() == 2 and tok.shape[1] % 32 == 0 and tok.shape[0] % BLOCK == 0
-        assert doc_blk.shape[0] == corpus_len + 1 and tok.is_contiguous() and doc_blk.is_contiguous()
-        self.device = doc_blk.device
-        self.tok, self.doc_blk = tok, doc_blk
-        self.corpus_len, self.d, self.dp = corpus_len, d, int(tok.shape[1])
-        self.n_blk = int(tok.shape[0]) // BLOCK
-        assert blk_rows is None or (blk_rows.dtype == torch.uint8 and blk_rows.shape == (self.n_blk,))
-        self._blk_rows = blk_rows
-        self.centroids = self.tok_centroid = self.cen_off = self.cen_doc = None  # build_centroids / load_centroids
-        self._doc_cen = None                                                      # doc_centroids, on first use
-        self._init_search(chunk, kernels)
-
-    @property
-    def nbytes(self):
-        """Bytes of device memory the index holds (token rows and block offsets; with centroids: those, the tokens' assignment and the
-        inverted lists; the per-passage centroid lists once doc_centroids has built them)."""
-        held = (self.tok, self.doc_blk, self.centroids, self.tok_centroid, self.cen_off, self.cen_doc) + (self._doc_cen or ())
-        return sum(t.numel() * t.element_size() for t in held if t is not None)
-
-    @property
-    def blk_rows(self):
-        """uint8 [n_blk]: the real token rows of every block."""
-        if self._blk_rows is None:
-            used = (self.tok.view(self.n_blk, BLOCK, self.dp) != 0).any(2)
-            last = (used * torch.arange(1, BLOCK + 1, device=self.device)).amax(1) if self.n_blk else used.sum(1)
-            self._blk_rows = last.to(torch.uint8)
-        return self._blk_rows
-
-    def quantize(self, dsub=8, codebook=None, **train_kwargs):
-        """The ColBERTPQIndex of this index: token rows replaced by 8-bit codes over sub-vectors of `dsub` features (DESIGN.md section
-        12.1).  Trains a codebook on the index's own token rows (train_pq(**train_kwargs)) unless one is given; the result shares
-        doc_blk with this index and keeps no reference to the dense rows.  The code bytes of a padding row are 0."""
-        kn = self._kernels()
-        blk_rows = self.blk_rows
-        real = torch.nonzero(_real_rows(blk_rows)).reshape(-1)
-        if codebook is None:
-            pick = _sample(int(real.shape[0]), train_kwargs.get("train_size", 65536), train_kwargs.get("seed", 0))
-            codebook = train_pq(self.tok[real if pick is None else real[pick.to(self.device)]], dsub=dsub, kernels=kn, **train_kwargs)
-        elif train_kwargs:
-            raise TypeError(f"a codebook was given: nothing to train with {sorted(train_kwargs)}")
-        codebook = ivf._check_codebook(codebook, self.dp, dsub, PQ_MAX_DP).to(self.device).contiguous()
-        codes = torch.zeros((self.n_blk * BLOCK, self.dp // int(dsub)), dtype=torch.uint8, device=self.device)
-        for lo in range(0, int(real.shape[0]), 1 << 22):
-            part = real[lo:lo + (1 << 22)]
-            codes[part] = kn.colbert_pq_encode(self.tok[part], codebook)
-        return ColBERTPQIndex.from_packed(codes, blk_rows, codebook, self.doc_blk, self.corpus_len, self.d, chunk=self.chunk, kernels=kn)
-
-    # ---- centroid pruning (DESIGN.md section 12.2) ----
-    def build_centroids(self, n_centroids, iters=10, train_size=1 << 18, seed=0, centroids=None):
-        """Gives the index `n_centroids` unit-norm centroids (spherical k-means on a seeded sample of `train_size` stored token rows --
-        train_centroids -- unless `centroids` [n_centroids, d] are given), assigns every stored token row to argmax_c <tok, centroid_c>
-        (bf16 MFMA path, ties to the lower centroid id) and builds the inverted lists.  The index then holds
-          centroids     bf16 [C, dp]
-          tok_centroid  int32 [n_blk * 16], -1 on padding rows
-          cen_off int64 [C + 1], cen_doc int32: per centroid the sorted, duplicate-free doc ids with at least one token there
-        The lists come from one device sort (torch.unique of centroid * corpus_len + doc): no host loop over centroids or passages."""
-        C, kn = int(n_centroids), self._kernels()
-        real = torch.nonzero(_real_rows(self.blk_rows)).reshape(-1)
-        if centroids is None:
-            if not 1 <= C <= int(real.shape[0]):
-                raise ValueError(f"n_centroids={C} out of range (1 .. the index's {int(real.shape[0])} token rows)")
-            pick = _sample(int(real.shape[0]), train_size, seed)
-            cen = train_centroids(self.tok[real if pick is None else real[pick.to(self.device)]], C, iters=iters, seed=seed, kernels=kn)
-        else:
-            cen = torch.as_tensor(centroids)
-            if cen.dim() != 2 or cen.shape[0] != C or C < 1 or cen.shape[1] != self.d:
-                raise ValueError(f"centroids {tuple(cen.shape)}; [{C}, {self.d}] expected")
-            cen = _bf16_padded(cen.to(self.device), self.dp)
-        tok_centroid = torch.full((self.n_blk * BLOCK,), -1, dtype=torch.int32, device=self.device)
-        for lo in range(0, int(real.shape[0]), 1 << 22):
-            part = real[lo:lo + (1 << 22)]
-            tok_centroid[part] = _nearest(kn, self.tok[part], cen, 1)[:, 0].to(torch.int32)
-        self._set_centroids(cen.contiguous(), tok_centroid, *_centroid_lists(tok_centroid, self.doc_blk, C, self.corpus_len))
-        return self
+    centroids = tok_centroid = cen_off = cen_doc = _doc_cen = None
 
     def _set_centroids(self, centroids, tok_centroid, cen_off, cen_doc):
         C = int(centroids.shape[0])
@@ -358,7 +256,7 @@ class ColBERTIndex(_TokenSearch):
         cand_off, cand_doc, max_count = self._lists(qb, cand_off, cand_doc)
         S = torch.empty((qb.shape[0], max_count), dtype=torch.float32, device=self.device)
         if max_count:
-            self._kernels().colbert_cand_score(self, qb, pool, cand_off, cand_doc, 0, max_count, S)
+            self._score_lists(self._kernels(), qb, pool, cand_off, cand_doc, 0, max_count, S)
         return S
 
     # ---- centroid interaction ----
@@ -368,7 +266,10 @@ class ColBERTIndex(_TokenSearch):
         a passage without tokens has an empty list."""
         C = self._need_centroids()
         if self._doc_cen is None:
-            self._doc_cen = _doc_centroid_lists(self.tok_centroid, self.doc_blk, C, self.corpus_len)
+            # ids >= C belong to no list (as the kernels skip them): unmasked, doc * C + id would land in another passage's list.  No
+            # index that build_centroids made holds one; from_packed and a loaded centroid file may.
+            tc = self.tok_centroid
+            self._doc_cen = _doc_centroid_lists(torch.where(tc < C, tc, torch.full_like(tc, -1)), self.doc_blk, C, self.corpus_len)
         return self._doc_cen
 
     def _centroid_table(self, qb):
@@ -476,9 +377,154 @@ class ColBERTIndex(_TokenSearch):
         if max_count:
             chunk = self.default_chunk(nq) if chunk is None else int(chunk)
             chunk = max(8, min(chunk, (max_count + 7) // 8 * 8))
-            ws = kn.colbert_cand_workspace(nq, chunk, topk, self.doc_blk)
-            kn.colbert_cand_search(self, qb, pool, cand_off, cand_doc, max_count, values, indices, chunk, ws)
+            self._search_lists(kn, qb, pool, cand_off, cand_doc, max_count, values, indices, chunk)
         return values, indices
+
+
+class ColBERTIndex(_CentroidPruning, _TokenSearch):
+    """Device-resident token index of a ColBERT corpus; `search` is the exhaustive MaxSim top-k."""
+
+    _SEARCH, _SCORE = "colbert_search", "colbert_score"
+
+    def __init__(self, doc_ids, lengths, rows, corpus_len, device, chunk=None, kernels=None):
+        """From unpadded token rows grouped by passage: doc_ids int64 [n], lengths [n] (tokens of each passage), rows [sum(lengths), d]
+        in the order of doc_ids.  Ids that never appear get zero blocks; an id given twice is a ValueError."""
+        corpus_len = int(corpus_len)
+        if not 0 < corpus_len < 2 ** 31:
+            raise ValueError(f"corpus_len={corpus_len} out of range (1 .. 2^31 - 1)")
+        device = torch.device(device)
+        rows = torch.as_tensor(rows).to(device)
+        if rows.dim() != 2:
+            raise ValueError(f"rows {tuple(rows.shape)}; [sum(lengths), d] expected")
+        ids, lens, doc_len, doc_blk = _layout(doc_ids, lengths, corpus_len, device)
+        if int(lens.sum()) != rows.shape[0]:
+            raise ValueError(f"{rows.shape[0]} token rows for lengths that sum to {int(lens.sum())}")
+        d = int(rows.shape[1])
+        dp = (max(d, 1) + 31) // 32 * 32
+        n_blk = int(doc_blk[-1])
+        tok = torch.zeros((n_blk * BLOCK, dp), dtype=_BF16, device=device)
+        if rows.shape[0]:
+            tok[_dest_rows(doc_blk, ids, lens), :d] = rows.to(_BF16)
+        self._set(tok, doc_blk, corpus_len, d, chunk, kernels, _blk_rows(doc_len, doc_blk))
+
+    @classmethod
+    def from_packed(cls, tok, doc_blk, corpus_len, d, chunk=None, kernels=None, blk_rows=None):
+        """From tensors already in the device layout (csrc/colbert.h), on their device: tok bf16 [n_blk * 16, dp], doc_blk int64
+        [corpus_len + 1].  blk_rows uint8 [n_blk] (the real token rows of every block; only `quantize` reads it) defaults to the rows
+        up to a block's last non-zero one."""
+        self = cls.__new__(cls)
+        self._set(tok, doc_blk, int(corpus_len), int(d), chunk, kernels, blk_rows)
+        return self
+
+    @classmethod
+    def from_repr(cls, expert_repr, attention, corpus_ids, corpus_len, device=None, chunk=None, kernels=None):
+        """From a padded batch: expert_repr [N, LD, d], attention [N, LD]; the slots with attention > 0 are kept, in order."""
+        device = expert_repr.device if device is None else device
+        ids, lens, rows = _kept_rows(expert_repr, attention, corpus_ids)
+        return cls(ids, lens, rows, corpus_len, device, chunk=chunk, kernels=kernels)
+
+    def _set(self, tok, doc_blk, corpus_len, d, chunk, kernels, blk_rows=None):
+        assert tok.dtype == _BF16 and doc_blk.dtype == torch.int64 and tok.dim() == 2 and tok.shape[1] % 32 == 0 and tok.shape[0] % BLOCK == 0
+        assert doc_blk.shape[0] == corpus_len + 1 and tok.is_contiguous() and doc_blk.is_contiguous()
+        self.device = doc_blk.device
+        self.tok, self.doc_blk = tok, doc_blk
+        self.corpus_len, self.d, self.dp = corpus_len, d, int(tok.shape[1])
+        self.n_blk = int(tok.shape[0]) // BLOCK
+        assert blk_rows is None or (blk_rows.dtype == torch.uint8 and blk_rows.shape == (self.n_blk,))
+        self._blk_rows = blk_rows
+        self.centroids = self.tok_centroid = self.cen_off = self.cen_doc = None  # build_centroids / load_centroids
+        self._doc_cen = None                                                      # doc_centroids, on first use
+        self._init_search(chunk, kernels)
+
+    @property
+    def nbytes(self):
+        """Bytes of device memory the index holds (token rows and block offsets; with centroids: those, the tokens' assignment and the
+        inverted lists; the per-passage centroid lists once doc_centroids has built them)."""
+        held = (self.tok, self.doc_blk, self.centroids, self.tok_centroid, self.cen_off, self.cen_doc) + (self._doc_cen or ())
+        return sum(t.numel() * t.element_size() for t in held if t is not None)
+
+    @property
+    def blk_rows(self):
+        """uint8 [n_blk]: the real token rows of every block."""
+        if self._blk_rows is None:
+            used = (self.tok.view(self.n_blk, BLOCK, self.dp) != 0).any(2)
+            last = (used * torch.arange(1, BLOCK + 1, device=self.device)).amax(1) if self.n_blk else used.sum(1)
+            self._blk_rows = last.to(torch.uint8)
+        return self._blk_rows
+
+    def quantize(self, dsub=8, codebook=None, **train_kwargs):
+        """The ColBERTPQIndex of this index: token rows replaced by 8-bit codes over sub-vectors of `dsub` features (DESIGN.md section
+        12.1).  Trains a codebook on the index's own token rows (train_pq(**train_kwargs)) unless one is given; the result shares
+        doc_blk with this index and keeps no reference to the dense rows.  The code bytes of a padding row are 0."""
+        kn = self._kernels()
+        blk_rows = self.blk_rows
+        real = torch.nonzero(_real_rows(blk_rows)).reshape(-1)
+        if codebook is None:
+            pick = _sample(int(real.shape[0]), train_kwargs.get("train_size", 65536), train_kwargs.get("seed", 0))
+            codebook = train_pq(self.tok[real if pick is None else real[pick.to(self.device)]], dsub=dsub, kernels=kn, **train_kwargs)
+        elif train_kwargs:
+            raise TypeError(f"a codebook was given: nothing to train with {sorted(train_kwargs)}")
+        codebook = ivf._check_codebook(codebook, self.dp, dsub, PQ_MAX_DP).to(self.device).contiguous()
+        codes = torch.zeros((self.n_blk * BLOCK, self.dp // int(dsub)), dtype=torch.uint8, device=self.device)
+        for lo in range(0, int(real.shape[0]), 1 << 22):
+            part = real[lo:lo + (1 << 22)]
+            codes[part] = kn.colbert_pq_encode(self.tok[part], codebook)
+        return ColBERTPQIndex.from_packed(codes, blk_rows, codebook, self.doc_blk, self.corpus_len, self.d, chunk=self.chunk, kernels=kn)
+
+    def compress(self, nbits=2, buckets=None, train_size=65536, seed=0):
+        """The ColBERTResidualIndex of this index: every token row replaced by its centroid id -- tok_centroid
+        as it is, nothing is re-assigned -- plus `nbits` in {1, 2, 4} bits per feature of row - centroid under ONE bucket set.
+        `buckets` = (cutoffs [2^nbits - 1], weights [2^nbits]) trains nothing; otherwise train_buckets on the residuals of a seeded
+        sample of `train_size` stored token rows (at most 2^24 / dp of them: torch.quantile's limit of 2^24 elements).  The result
+        shares doc_blk, the centroids, tok_centroid and the inverted lists with this index and keeps no reference to the dense rows.
+        ValueError without centroids."""
+        C, kn, nbits = self._need_centroids(), self._kernels(), _check_res_shape(nbits, self.dp)
+        if buckets is None:
+            real = torch.nonzero((self.tok_centroid >= 0) & (self.tok_centroid < C)).reshape(-1)
+            if not real.numel():
+                raise ValueError("no token row with a centroid to train buckets on")
+            pick = _sample(int(real.shape[0]), min(int(train_size), QUANTILE_MAX // self.dp), seed)
+            rows = real if pick is None else real[pick.to(self.device)]
+            buckets = train_buckets(_residuals(self.tok[rows], self.tok_centroid[rows], self.centroids)[:, :self.d], nbits)
+        cutoffs, weights = _check_buckets(buckets, nbits, self.device)
+        codes = kn.colbert_res_encode(self, cutoffs, nbits)
+        return ColBERTResidualIndex.from_packed(codes, self.tok_centroid, self.centroids, cutoffs, weights, self.doc_blk, self.corpus_len,
+                                                self.d, cen_off=self.cen_off, cen_doc=self.cen_doc, chunk=self.chunk, kernels=kn)
+
+    # ---- centroid pruning (DESIGN.md section 12.2) ----
+    def build_centroids(self, n_centroids, iters=10, train_size=1 << 18, seed=0, centroids=None):
+        """Gives the index `n_centroids` unit-norm centroids (spherical k-means on a seeded sample of `train_size` stored token rows --
+        train_centroids -- unless `centroids` [n_centroids, d] are given), assigns every stored token row to argmax_c <tok, centroid_c>
+        (bf16 MFMA path, ties to the lower centroid id) and builds the inverted lists.  The index then holds
+          centroids     bf16 [C, dp]
+          tok_centroid  int32 [n_blk * 16], -1 on padding rows
+          cen_off int64 [C + 1], cen_doc int32: per centroid the sorted, duplicate-free doc ids with at least one token there
+        The lists come from one device sort (torch.unique of centroid * corpus_len + doc): no host loop over centroids or passages."""
+        C, kn = int(n_centroids), self._kernels()
+        real = torch.nonzero(_real_rows(self.blk_rows)).reshape(-1)
+        if centroids is None:
+            if not 1 <= C <= int(real.shape[0]):
+                raise ValueError(f"n_centroids={C} out of range (1 .. the index's {int(real.shape[0])} token rows)")
+            pick = _sample(int(real.shape[0]), train_size, seed)
+            cen = train_centroids(self.tok[real if pick is None else real[pick.to(self.device)]], C, iters=iters, seed=seed, kernels=kn)
+        else:
+            cen = torch.as_tensor(centroids)
+            if cen.dim() != 2 or cen.shape[0] != C or C < 1 or cen.shape[1] != self.d:
+                raise ValueError(f"centroids {tuple(cen.shape)}; [{C}, {self.d}] expected")
+            cen = _bf16_padded(cen.to(self.device), self.dp)
+        tok_centroid = torch.full((self.n_blk * BLOCK,), -1, dtype=torch.int32, device=self.device)
+        for lo in range(0, int(real.shape[0]), 1 << 22):
+            part = real[lo:lo + (1 << 22)]
+            tok_centroid[part] = _nearest(kn, self.tok[part], cen, 1)[:, 0].to(torch.int32)
+        self._set_centroids(cen.contiguous(), tok_centroid, *_centroid_lists(tok_centroid, self.doc_blk, C, self.corpus_len))
+        return self
+
+    def _score_lists(self, kn, qb, pool, cand_off, cand_doc, pos_begin, cols, S):
+        kn.colbert_cand_score(self, qb, pool, cand_off, cand_doc, pos_begin, cols, S)
+
+    def _search_lists(self, kn, qb, pool, cand_off, cand_doc, max_count, values, indices, chunk):
+        ws = kn.colbert_cand_workspace(int(qb.shape[0]), chunk, values.shape[1], self.doc_blk)
+        kn.colbert_cand_search(self, qb, pool, cand_off, cand_doc, max_count, values, indices, chunk, ws)
 
 
 def _nearest(kn, rows, centroids, k):
@@ -634,14 +680,239 @@ def load_pq_index(path, device=None, chunk=None, kernels=None):
                                       blob["corpus_len"], blob["d"], chunk=chunk, kernels=kernels)
 
 
+# ---- residual-compressed token rows under the pruned search ------------------------------------------------
+
+RES_NBITS = (1, 2, 4)         # bits per feature of row - centroid
+RES_MAX_DP = 128              # dprhot_colbert_res_score keeps the query fragments and a block's raw operands in registers
+QUANTILE_MAX = 1 << 24        # torch.quantile's limit on the elements of its input
+
+
+def _check_res_shape(nbits, dp):
+    if nbits not in RES_NBITS:
+        raise ValueError(f"nbits={nbits!r}: {RES_NBITS} bits per feature")
+    if dp > RES_MAX_DP:
+        raise NotImplementedError(f"dp={dp}: the residual index is built for dp <= {RES_MAX_DP}")
+    return int(nbits)
+
+
+def _check_buckets(buckets, nbits, device):
+    """(cutoffs fp32 [2^nbits - 1], weights fp32 [2^nbits]) on `device`, contiguous."""
+    cutoffs, weights = (torch.as_tensor(t).detach().to(device, torch.float32).contiguous() for t in buckets)
+    if cutoffs.shape != ((1 << nbits) - 1,) or weights.shape != (1 << nbits,):
+        raise ValueError(f"buckets {tuple(cutoffs.shape)} / {tuple(weights.shape)}; cutoffs [{(1 << nbits) - 1}] and weights [{1 << nbits}] "
+                         f"expected for nbits={nbits}")
+    return cutoffs, weights
+
+
+def _residuals(rows, tok_centroid, centroids):
+    """fp32 [n, dp]: float(row) - float(its centroid), one fp32 subtraction; the ids must lie in [0, C)."""
+    return rows.float() - centroids[tok_centroid.long()].float()
+
+
+def train_buckets(residuals, nbits):
+    """(cutoffs fp32 [2^nbits - 1], weights fp32 [2^nbits]) of fp32 residuals (any shape, flattened; at most 2^24 elements) by
+    torch.quantile: the cutoffs are the quantiles j / 2^nbits, j = 1 .. 2^nbits - 1, the weights the quantiles (j + 1/2) / 2^nbits,
+    j = 0 .. 2^nbits - 1 -- ColBERTv2's one bucket set per index."""
+    if nbits not in RES_NBITS:
+        raise ValueError(f"nbits={nbits!r}: {RES_NBITS} bits per feature")
+    x = torch.as_tensor(residuals).detach().float().reshape(-1)
+    if not 0 < x.numel() <= QUANTILE_MAX:
+        raise ValueError(f"{x.numel()} residuals; 1 .. 2^24 (torch.quantile's limit) expected")
+    nb = 1 << int(nbits)
+    cutoffs = torch.quantile(x, torch.arange(1, nb, device=x.device, dtype=torch.float32) / nb)
+    weights = torch.quantile(x, (torch.arange(nb, device=x.device, dtype=torch.float32) + 0.5) / nb)
+    return cutoffs, weights
+
+
+def res_unpack(res_code, nbits):
+    """int64 [n, rb * 8 / nbits]: code(r, t) = (res_code[r, t * nbits / 8] >> (nbits * (t mod (8 / nbits)))) & (2^nbits - 1)."""
+    per = 8 // nbits
+    shifts = torch.arange(per, device=res_code.device, dtype=torch.int64) * nbits
+    return ((res_code.to(torch.int64).unsqueeze(2) >> shifts) & ((1 << nbits) - 1)).reshape(res_code.shape[0], -1)
+
+
+class ColBERTResidualIndex(_CentroidPruning, _TokenSearch):
+    """Token index in the ColBERTv2 format: per row its centroid id (tok_centroid int32 [n_blk * 16]) and `nbits` bits per feature of
+    row - centroid (res_code uint8 [n_blk * 16, dp * nbits / 8]) under ONE bucket set (cutoffs, weights) instead of tok.  Searched with
+    centroid pruning only -- probe, candidates, score_candidates, approx_candidates, prune_candidates, search_pruned -- and every
+    result is, bit for bit, what `decode()` returns for the same call."""
+
+    FORMAT = "dpr_scale_amd.colbert_res/1"
+
+    def __init__(self, *args, **kwargs):
+        raise TypeError("a ColBERTResidualIndex comes from ColBERTIndex.compress, ColBERTResidualIndex.from_packed, load_residual_index "
+                        "or a quantizer='residual' build")
+
+    @classmethod
+    def from_packed(cls, res_code, tok_centroid, centroids, cutoffs, weights, doc_blk, corpus_len, d, cen_off=None, cen_doc=None,
+                    chunk=None, kernels=None):
+        """From tensors in the device layout (csrc/colbert_res.h), on their device.  The inverted lists default to the lists of
+        tok_centroid (ids outside [0, C) belong to no list)."""
+        self = cls.__new__(cls)
+        corpus_len, C, dp = int(corpus_len), int(centroids.shape[0]), int(centroids.shape[1])
+        assert cutoffs.dtype == torch.float32 and weights.dtype == torch.float32 and weights.dim() == 1
+        nbits = int(weights.shape[0]).bit_length() - 1
+        _check_res_shape(nbits, dp)
+        _check_buckets((cutoffs, weights), nbits, weights.device)
+        assert res_code.dtype == torch.uint8 and res_code.dim() == 2 and res_code.shape[1] == dp * nbits // 8 and dp % 32 == 0
+        assert res_code.shape[0] % BLOCK == 0 and doc_blk.dtype == torch.int64 and doc_blk.shape[0] == corpus_len + 1
+        assert all(t.is_contiguous() for t in (res_code, tok_centroid, centroids, cutoffs, weights, doc_blk))
+        self.device = doc_blk.device
+        self.res_code, self.cutoffs, self.weights, self.doc_blk = res_code, cutoffs, weights, doc_blk
+        self.corpus_len, self.d, self.dp, self.nbits = corpus_len, int(d), dp, nbits
+        self.n_blk = int(res_code.shape[0]) // BLOCK
+        if cen_off is None:
+            inside = torch.where(tok_centroid < C, tok_centroid, torch.full_like(tok_centroid, -1))
+            cen_off, cen_doc = _centroid_lists(inside, doc_blk, C, corpus_len)
+        self._set_centroids(centroids, tok_centroid, cen_off, cen_doc)
+        self._init_search(chunk, kernels)
+        return self
+
+    def _tensors(self):
+        return dict(res_code=self.res_code, tok_centroid=self.tok_centroid, centroids=self.centroids, cutoffs=self.cutoffs,
+                    weights=self.weights, doc_blk=self.doc_blk, cen_off=self.cen_off, cen_doc=self.cen_doc)
+
+    @property
+    def nbytes(self):
+        """Bytes of device memory the index holds: codes, centroid ids, centroids, inverted lists, buckets and block offsets (and the
+        per-passage centroid lists once doc_centroids has built them)."""
+        return sum(t.numel() * t.element_size() for t in tuple(self._tensors().values()) + (self._doc_cen or ()))
+
+    def decode(self, rows_per_pass=1 << 20):
+        """The ColBERTIndex this one searches, by definition: tok[r, t] = bf16(float(centroids[tok_centroid[r], t]) + weights[code(r, t)])
+        -- one fp32 addition, round to nearest even -- and an exact zero row where tok_centroid[r] lies outside [0, C); the same four
+        centroid tensors, nothing re-assigned."""
+        C = int(self.centroids.shape[0])
+        tok = torch.zeros((self.n_blk * BLOCK, self.dp), dtype=_BF16, device=self.device)
+        for lo in range(0, self.n_blk * BLOCK, int(rows_per_pass)):
+            tc = self.tok_centroid[lo:lo + rows_per_pass].long()
+            ok = (tc >= 0) & (tc < C)
+            part = (self.centroids[tc.clamp(0, C - 1)].float() + self.weights[res_unpack(self.res_code[lo:lo + rows_per_pass], self.nbits)])
+            tok[lo:lo + rows_per_pass] = torch.where(ok.unsqueeze(1), part.to(_BF16), torch.zeros((), dtype=_BF16, device=self.device))
+        dense = ColBERTIndex.from_packed(tok, self.doc_blk, self.corpus_len, self.d, chunk=self.chunk, kernels=self.kn)
+        dense._set_centroids(self.centroids, self.tok_centroid, self.cen_off, self.cen_doc)
+        return dense
+
+    def _score_lists(self, kn, qb, pool, cand_off, cand_doc, pos_begin, cols, S):
+        kn.colbert_res_score(self, qb, pool, cand_off, cand_doc, pos_begin, cols, S)
+
+    def _search_lists(self, kn, qb, pool, cand_off, cand_doc, max_count, values, indices, chunk):
+        ws = kn.colbert_res_workspace(int(qb.shape[0]), chunk, values.shape[1], self.doc_blk)
+        kn.colbert_res_search(self, qb, pool, cand_off, cand_doc, max_count, values, indices, chunk, ws)
+
+    def _exhaustive(self, *args, **kwargs):
+        raise NotImplementedError("the residual index is searched with centroid pruning only (search_pruned); decode() gives the dense "
+                                  "index it stands for")
+
+    search = score = compress = quantize = _exhaustive
+
+    def save(self, path):
+        """One torch.save of the tensors (on the CPU) and sizes; load_residual_index reads it back."""
+        blob = {k: t.cpu() for k, t in self._tensors().items()}
+        blob.update(format=self.FORMAT, corpus_len=self.corpus_len, d=self.d, nbits=self.nbits)
+        torch.save(blob, path)
+        return path
+
+
+def load_residual_index(path, device=None, chunk=None, kernels=None):
+    """The ColBERTResidualIndex that ColBERTResidualIndex.save wrote, placed on `device`."""
+    device = torch.device(device) if device is not None else torch.device("cuda", 0)
+    blob = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(blob, dict) or blob.get("format") != ColBERTResidualIndex.FORMAT:
+        raise ValueError(f"{path}: not a residual ColBERT index file")
+    t = {k: blob[k].contiguous().to(device) for k in ("res_code", "tok_centroid", "centroids", "cutoffs", "weights", "doc_blk", "cen_off",
+                                                       "cen_doc")}
+    return ColBERTResidualIndex.from_packed(t["res_code"], t["tok_centroid"], t["centroids"], t["cutoffs"], t["weights"], t["doc_blk"],
+                                            blob["corpus_len"], blob["d"], cen_off=t["cen_off"], cen_doc=t["cen_doc"], chunk=chunk,
+                                            kernels=kernels)
+
+
+def _walk_parts(parts, need_sample, train_size, gen):
+    """One walk over parts(): (ids, lengths, d, sample) -- the layout's inputs and, when asked for, a seeded sample of at most
+    train_size token rows (bf16, on the host; the train_size smallest of one uniform key per row, in corpus order)."""
+    ids, lens, keys, sample, d = [], [], [], [], None
+    for i, n, r in parts():
+        i, n, r = torch.as_tensor(i).reshape(-1).long().cpu(), torch.as_tensor(n).reshape(-1).long().cpu(), torch.as_tensor(r)
+        if r.dim() != 2 or i.shape != n.shape or int(n.sum()) != r.shape[0] or (d is not None and r.shape[1] != d):
+            raise ValueError(f"ids {tuple(i.shape)}, lengths {tuple(n.shape)} and rows {tuple(r.shape)} do not belong together")
+        d = int(r.shape[1])
+        ids.append(i)
+        lens.append(n)
+        if need_sample and r.shape[0]:
+            key = torch.rand(r.shape[0], generator=gen, dtype=torch.float64)
+            keep = torch.sort(key, stable=True).indices[:train_size].sort().values
+            keys.append(key[keep])
+            sample.append(r[keep.to(r.device)].to(_BF16).cpu())
+    if d is None:
+        raise ValueError("no token rows to build an index from")
+    rows = torch.cat(sample, 0) if sample else torch.zeros((0, d), dtype=_BF16)
+    if rows.shape[0] > train_size:
+        rows = rows[torch.sort(torch.cat(keys), stable=True).indices[:train_size].sort().values]
+    return torch.cat(ids), torch.cat(lens), d, rows
+
+
+def _build_residual(parts, corpus_len, device, nbits, n_centroids, centroids, buckets, train_kwargs, chunk, kernels):
+    """The ColBERTResidualIndex of the passages that parts() yields as (ids, lengths, rows) pieces -- in every tensor
+    ColBERTIndex(all of them).build_centroids(C, centroids=the centroids).compress(nbits, buckets=the buckets) -- with never more than
+    ONE piece's dense rows on the device.  parts() is walked twice: layout and one seeded sample of token rows, on which the centroids
+    (train_centroids) and the buckets (train_buckets, on at most 2^24 / dp of its rows) are trained unless given; then every piece is
+    assigned and encoded, and the inverted lists are built from tok_centroid."""
+    corpus_len, device = int(corpus_len), torch.device(device)
+    if not 0 < corpus_len < 2 ** 31:
+        raise ValueError(f"corpus_len={corpus_len} out of range (1 .. 2^31 - 1)")
+    if n_centroids is None and centroids is None:
+        raise ValueError("quantizer='residual' needs n_centroids (or centroids)")
+    kn = _default_kernels(kernels)
+    unknown = sorted(set(train_kwargs) - {"train_size", "seed", "iters"})
+    if unknown or (centroids is not None and buckets is not None and train_kwargs):
+        raise TypeError(f"nothing to train with {unknown or sorted(train_kwargs)}")
+    train_size, seed = int(train_kwargs.get("train_size", 65536)), int(train_kwargs.get("seed", 0))
+    ids, lens, d, sample = _walk_parts(parts, centroids is None or buckets is None, train_size, torch.Generator().manual_seed(seed))
+    dp = (max(d, 1) + 31) // 32 * 32
+    nbits = _check_res_shape(nbits, dp)
+    sample = _bf16_padded(sample.to(device), dp)
+    if centroids is None:
+        C = int(n_centroids)
+        if not 1 <= C <= int(sample.shape[0]):
+            raise ValueError(f"n_centroids={C} out of range (1 .. the sample's {int(sample.shape[0])} token rows)")
+        cen = train_centroids(sample, C, iters=int(train_kwargs.get("iters", 10)), seed=seed, kernels=kn)
+    else:
+        cen = torch.as_tensor(centroids)
+        C = int(cen.shape[0]) if n_centroids is None else int(n_centroids)
+        if cen.dim() != 2 or cen.shape[0] != C or C < 1 or cen.shape[1] != d:
+            raise ValueError(f"centroids {tuple(cen.shape)}; [{C}, {d}] expected")
+        cen = _bf16_padded(cen.to(device), dp)
+    cen = cen.contiguous()
+    if buckets is None:
+        if not sample.shape[0]:
+            raise ValueError("no token row to train buckets on")
+        pick = _sample(int(sample.shape[0]), QUANTILE_MAX // dp, seed)
+        rows = sample if pick is None else sample[pick.to(device)]
+        buckets = train_buckets(_residuals(rows, _nearest(kn, rows, cen, 1)[:, 0], cen)[:, :d], nbits)
+    cutoffs, weights = _check_buckets(buckets, nbits, device)
+    _, _, _, doc_blk = _layout(ids, lens, corpus_len, device)
+    n_rows = int(doc_blk[-1]) * BLOCK
+    res_code = torch.zeros((n_rows, dp * nbits // 8), dtype=torch.uint8, device=device)
+    tok_centroid = torch.full((n_rows,), -1, dtype=torch.int32, device=device)
+    for i, n, r in parts():
+        r = torch.as_tensor(r)
+        if r.shape[0]:
+            dest = _dest_rows(doc_blk, torch.as_tensor(i).reshape(-1).to(device, torch.int64), torch.as_tensor(n).reshape(-1).to(device, torch.int64))
+            rows = _bf16_padded(r.to(device), dp)
+            tc = _nearest(kn, rows, cen, 1)[:, 0].to(torch.int32)
+            res_code[dest] = kn.colbert_res_encode(rows, cutoffs, nbits, tc, cen)
+            tok_centroid[dest] = tc
+    return ColBERTResidualIndex.from_packed(res_code, tok_centroid, cen, cutoffs, weights, doc_blk, corpus_len, d, chunk=chunk, kernels=kn)
+
+
 def _plain(quantizer, codebook, train_kwargs):
-    """True for quantizer=None (with nothing to quantise with), False for "pq"."""
+    """True for quantizer=None (with nothing to quantise with), False for "pq" and "residual"."""
     if quantizer in (None, "None"):
         if codebook is not None or train_kwargs:
             raise TypeError(f"quantizer=None takes no codebook and no training arguments {sorted(train_kwargs)}")
         return True
-    if quantizer != "pq":
-        raise NotImplementedError(f"quantizer={quantizer!r}: None or 'pq'")
+    if quantizer not in ("pq", "residual"):
+        raise NotImplementedError(f"quantizer={quantizer!r}: None, 'pq' or 'residual'")
     return False
 
 
@@ -736,15 +1007,21 @@ class TokenIndexBuilder:
             pickle.dump((ids.cpu(), lens.to(torch.int32).cpu(), rows.cpu()), f, protocol=4)
         return path
 
-    def finish(self, chunk=None, quantizer=None, sub_vec_dim=8, codebook=None, **train_kwargs):
+    def finish(self, chunk=None, quantizer=None, sub_vec_dim=8, codebook=None, nbits=2, n_centroids=None, centroids=None, buckets=None,
+               **train_kwargs):
         """The index of the batches added so far.  quantizer="pq": a ColBERTPQIndex (sub_vec_dim in {2, 4, 8}; a codebook, or
-        train_pq(**train_kwargs) on a seeded sample), encoded batch by batch -- the batches are never concatenated."""
+        train_pq(**train_kwargs) on a seeded sample), encoded batch by batch -- the batches are never concatenated.
+        quantizer="residual": a ColBERTResidualIndex (nbits in {1, 2, 4}; n_centroids trained on a seeded sample, or `centroids`;
+        `buckets` or trained ones), assigned and encoded batch by batch."""
         if self.corpus_len is None:
             raise ValueError("corpus_len is needed to build the index")
-        if not _plain(quantizer, codebook, train_kwargs):
+        if not _plain(quantizer, codebook, _residual_args(quantizer, train_kwargs, n_centroids, centroids, buckets)):
             if not self.parts:
                 raise ValueError("no context batch was added")
             device = self.parts[0][2].device if self.device is None else self.device
+            if quantizer == "residual":
+                return _build_residual(lambda: iter(self.parts), self.corpus_len, device, nbits, n_centroids, centroids, buckets, train_kwargs,
+                                       chunk, self.kn)
             return _build_pq(lambda: iter(self.parts), self.corpus_len, device, sub_vec_dim, codebook, train_kwargs, chunk, self.kn)
         ids, lens, rows = self._cat()
         return ColBERTIndex(ids, lens, rows, self.corpus_len, rows.device if self.device is None else self.device, chunk=chunk, kernels=self.kn)
@@ -774,16 +1051,33 @@ def read_tokens(ctx_embeddings_dir):
     return torch.cat(ids), torch.cat(lens), torch.cat(rows, 0)
 
 
+def _residual_args(quantizer, train_kwargs, n_centroids, centroids, buckets):
+    """train_kwargs as _plain judges them: with any other quantizer the residual build's arguments count as training arguments."""
+    if quantizer == "residual":
+        return train_kwargs
+    given = {k: v for k, v in dict(n_centroids=n_centroids, centroids=centroids, buckets=buckets).items() if v is not None}
+    if given and quantizer not in (None, "None"):
+        raise TypeError(f"quantizer={quantizer!r} takes no {sorted(given)}")
+    return dict(train_kwargs, **given)
+
+
 def load_index(ctx_embeddings_dir, corpus_len, device=None, chunk=None, kernels=None, quantizer=None, sub_vec_dim=8, codebook=None,
-               **train_kwargs):
+               nbits=2, n_centroids=None, centroids=None, buckets=None, **train_kwargs):
     """Reads every `tokens_{rank:04}.pkl` under `ctx_embeddings_dir` and merges all ranks' passages by doc id into ONE index on `device`.
 
     quantizer="pq" (sub_vec_dim in {2, 4, 8}): a ColBERTPQIndex under `codebook`, or under train_pq(**train_kwargs) of a seeded sample
     of token rows taken across the files; the files are read one at a time (twice) and encoded one at a time, so the device never holds
-    more than one file's dense rows."""
+    more than one file's dense rows.
+
+    quantizer="residual" (nbits in {1, 2, 4}): a ColBERTResidualIndex over `n_centroids` centroids trained on
+    a seeded sample of token rows taken across the files (train_size, seed, iters), or over `centroids`; the buckets are `buckets` or
+    trained on the same sample.  The files are read one at a time (twice), assigned and encoded one at a time."""
     device = torch.device(device) if device is not None else torch.device("cuda", 0)
-    if not _plain(quantizer, codebook, train_kwargs):
+    if not _plain(quantizer, codebook, _residual_args(quantizer, train_kwargs, n_centroids, centroids, buckets)):
         files = _token_files(ctx_embeddings_dir)
+        if quantizer == "residual":
+            return _build_residual(lambda: (_read_token_file(path) for path in files), corpus_len, device, nbits, n_centroids, centroids,
+                                   buckets, train_kwargs, chunk, kernels)
         return _build_pq(lambda: (_read_token_file(path) for path in files), corpus_len, device, sub_vec_dim, codebook, train_kwargs, chunk,
                          kernels)
     ids, lens, rows = read_tokens(ctx_embeddings_dir)

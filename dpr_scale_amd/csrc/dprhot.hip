@@ -39,6 +39,7 @@
 #include "colbert.h"
 #include "colbert_cand.h"
 #include "colbert_cen.h"
+#include "colbert_res.h"
 #include "colbert_pq.h"
 #include "spar.h"
 #include "dense_fp8.h"
@@ -2973,6 +2974,89 @@ int dprhot_colbert_cen_search(const int64_t* doc_cen_off, const int32_t* doc_cen
                                     stream);
   };
   return cbc_search_with("colbert_cen", fill, nq, corpus_len, cand_off, cand_doc, n_cand, max_count, k, chunk, values, indices, workspace,
+                         workspace_bytes, stream);
+}
+
+// ---- residual-compressed token index under the pruned search (csrc/colbert_res.h) ----
+static int cbr_check_shape(int dp, int nbits, int C) {
+  REQUIRE(nbits == 1 || nbits == 2 || nbits == 4, "nbits=%d: 1, 2 or 4 bits per feature", nbits);
+  REQUIRE(C >= 1, "C=%d out of range (1 .. 2^31 - 1)", C);
+  REQUIRE(dp > 0 && dp % 32 == 0, "dp=%d must be a positive multiple of 32 (pad with zeros)", dp);
+  if (dp > CBR_MAX_DP) return fail(DPRHOT_E_UNSUPPORTED, "dp=%d: the residual ColBERT index is built for dp <= %d", dp, CBR_MAX_DP);
+  return DPRHOT_OK;
+}
+
+static int cbr_check(const void* res_code, const void* tok_centroid, const void* centroids, int C, const void* weights, int nbits,
+                     const void* doc_blk, int64_t n_blk, int64_t corpus_len, int dp, const void* q_tok, int nq, int LQ, int pool) {
+  // the index's own limits first, so that a refusal names the residual index and its tensors
+  if (int rc = cbr_check_shape(dp, nbits, C)) return rc;
+  REQUIRE(n_blk <= 0 || (res_code && centroids && weights && tok_centroid),
+          "NULL pointer (res_code, centroids, weights and tok_centroid are required)");
+  REQUIRE(aligned16(res_code) && aligned16(centroids), "res_code and the centroid rows must be 16-byte aligned");
+  return cb_check(res_code, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool);
+}
+
+int dprhot_colbert_res_encode(const dprhot_bf16* tok, const int32_t* tok_centroid, int64_t n_rows, int dp, const dprhot_bf16* centroids,
+                              int C, const float* cutoffs, int nbits, uint8_t* res_code, void* stream) {
+  REQUIRE(n_rows >= 0 && n_rows < (1ll << 40), "n_rows=%lld out of range (0 .. 2^40 - 1)", (long long)n_rows);
+  if (int rc = cbr_check_shape(dp, nbits, C)) return rc;
+  REQUIRE(n_rows == 0 || (tok && tok_centroid && centroids && cutoffs && res_code),
+          "NULL pointer (tok, tok_centroid, centroids, cutoffs and res_code are required)");
+  REQUIRE(aligned16(tok) && aligned16(centroids) && aligned16(res_code), "token rows, centroid rows and res_code must be 16-byte aligned");
+  if (n_rows == 0) return DPRHOT_OK;
+  CbrEncArgs a{reinterpret_cast<const uint16_t*>(tok), tok_centroid, (long long)n_rows, dp, reinterpret_cast<const uint16_t*>(centroids), C,
+               cutoffs, res_code};
+  const long long want = (n_rows * (dp / 8) + CBR_ENC_THREADS - 1) / CBR_ENC_THREADS;
+  const dim3 grid((unsigned)(want < (1 << 20) ? want : (1 << 20))), block(CBR_ENC_THREADS);  // (pieces beyond: grid stride)
+  hipStream_t st = (hipStream_t)stream;
+  if (nbits == 1) return launch<cbr_encode_kernel<1>>(grid, block, 0, st, a);
+  if (nbits == 2) return launch<cbr_encode_kernel<2>>(grid, block, 0, st, a);
+  return launch<cbr_encode_kernel<4>>(grid, block, 0, st, a);
+}
+
+extern "C++" {
+template <int NB>
+static int cbr_launch(int dp, dim3 grid, size_t lds, hipStream_t st, const CbrArgs& a) {
+  const dim3 block(256);
+  switch (dp) {
+    case 32: return launch<cbr_score_kernel<NB, 1>>(grid, block, lds, st, a);
+    case 64: return launch<cbr_score_kernel<NB, 2>>(grid, block, lds, st, a);
+    case 96: return launch<cbr_score_kernel<NB, 3>>(grid, block, lds, st, a);
+    default: return launch<cbr_score_kernel<NB, 4>>(grid, block, lds, st, a);  // (dp = 128: cbr_check_shape)
+  }
+}
+}  // extern "C++"
+
+int dprhot_colbert_res_score(const uint8_t* res_code, const int32_t* tok_centroid, const dprhot_bf16* centroids, int C, const float* weights,
+                             int nbits, const int64_t* doc_blk, int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok, int nq,
+                             int LQ, int pool, const int64_t* cand_off, const int32_t* cand_doc, int64_t n_cand, int64_t pos_begin, int cols,
+                             float* S, int64_t ld, void* stream) {
+  if (int rc = cbr_check(res_code, tok_centroid, centroids, C, weights, nbits, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool)) return rc;
+  if (int rc = cbc_check(cand_off, cand_doc, n_cand, nq)) return rc;
+  if (int rc = check_score_window(S, cols, ld, pos_begin, 1ll << 31)) return rc;  // candidate positions, not doc ids: below 2^31
+  const int FQ = cdiv(LQ, 16);
+  CbrArgs a{res_code, tok_centroid, reinterpret_cast<const uint16_t*>(centroids), C, weights, reinterpret_cast<const long long*>(doc_blk),
+            (long long)n_blk, (long long)corpus_len, dp, reinterpret_cast<const uint16_t*>(q_tok), nq, LQ, pool,
+            reinterpret_cast<const long long*>(cand_off), cand_doc, (long long)n_cand, (long long)pos_begin, cols, S, (long long)ld, FQ};
+  const dim3 grid((unsigned)cdiv(cols, CBC_RUNP), (unsigned)nq);
+  const size_t lds = (size_t)CBC_RUNP * (FQ * 16 + 1) * sizeof(float);  // the term table
+  hipStream_t st = (hipStream_t)stream;
+  if (nbits == 1) return cbr_launch<1>(dp, grid, lds, st, a);
+  if (nbits == 2) return cbr_launch<2>(dp, grid, lds, st, a);
+  return cbr_launch<4>(dp, grid, lds, st, a);
+}
+
+int dprhot_colbert_res_search(const uint8_t* res_code, const int32_t* tok_centroid, const dprhot_bf16* centroids, int C, const float* weights,
+                              int nbits, const int64_t* doc_blk, int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok, int nq,
+                              int LQ, int pool, const int64_t* cand_off, const int32_t* cand_doc, int64_t n_cand, int64_t max_count, int k,
+                              int chunk, float* values, int64_t* indices, void* workspace, size_t workspace_bytes, void* stream) {
+  if (int rc = cbr_check(res_code, tok_centroid, centroids, C, weights, nbits, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool)) return rc;
+  if (int rc = cbc_check(cand_off, cand_doc, n_cand, nq)) return rc;
+  auto fill = [&](int64_t j0, int cols, float* S, int ld) {
+    return dprhot_colbert_res_score(res_code, tok_centroid, centroids, C, weights, nbits, doc_blk, n_blk, corpus_len, dp, q_tok, nq, LQ, pool,
+                                    cand_off, cand_doc, n_cand, j0, cols, S, ld, stream);
+  };
+  return cbc_search_with("colbert_res", fill, nq, corpus_len, cand_off, cand_doc, n_cand, max_count, k, chunk, values, indices, workspace,
                          workspace_bytes, stream);
 }
 

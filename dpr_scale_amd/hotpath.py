@@ -669,6 +669,50 @@ class HipKernels:
                                                            values.shape[1], int(chunk), _ptr(values), _ptr(indices), _ptr(ws), ws.numel(),
                                                            self._stream()), "dprhot_colbert_cen_search")
 
+    # -- residual-compressed token index under the pruned search (csrc/colbert_res.h) -------------------
+    def colbert_res_workspace(self, nq, chunk, k, like):
+        return self._chunk_workspace(self._lib.colbert_cand_workspace_bytes(nq, chunk), nq, k, like)
+
+    def colbert_res_encode(self, rows, cutoffs, nbits, tok_centroid=None, centroids=None):
+        """uint8 [n, dp * nbits / 8]: the residual codes of bf16 rows [n, dp] under their centroid ids int32 [n] among centroids bf16
+        [C, dp] (dprhot_colbert_res_encode); a row whose id lies outside [0, C) gets zero bytes.  `rows` may be a ColBERTIndex with
+        centroids instead: its tok, tok_centroid and centroids are taken."""
+        if tok_centroid is None:
+            rows, tok_centroid, centroids = rows.tok, rows.tok_centroid, rows.centroids
+        self._require_gpu(rows, tok_centroid, centroids, cutoffs)
+        n, dp = rows.shape
+        nbits = int(nbits)
+        assert rows.dtype == torch.bfloat16 and centroids.dtype == torch.bfloat16 and centroids.shape[1] == dp
+        assert tok_centroid.dtype == torch.int32 and tok_centroid.shape == (n,) and cutoffs.dtype == torch.float32
+        assert cutoffs.shape == ((1 << nbits) - 1,) and all(t.is_contiguous() for t in (rows, tok_centroid, centroids, cutoffs))
+        codes = torch.empty((n, dp * nbits // 8), dtype=torch.uint8, device=rows.device)
+        self._lib.check(self.lib.dprhot_colbert_res_encode(_ptr(rows), _ptr(tok_centroid), n, dp, _ptr(centroids), int(centroids.shape[0]),
+                                                           _ptr(cutoffs), nbits, _ptr(codes), self._stream()), "dprhot_colbert_res_encode")
+        return codes
+
+    def _colbert_res_head(self, index, q, pool, cand_off, cand_doc):
+        """res_code .. n_cand: the arguments both residual entry points begin with; cand_off int64 [nq + 1], cand_doc int32 [n_cand]."""
+        self._require_gpu(index.res_code, index.tok_centroid, index.centroids, index.weights, index.doc_blk, q, cand_off, cand_doc)
+        nq, LQ, dp = q.shape
+        assert cand_off.dtype == torch.int64 and cand_doc.dtype == torch.int32 and cand_off.shape == (nq + 1,)
+        assert cand_off.is_contiguous() and cand_doc.is_contiguous()
+        return (_ptr(index.res_code), _ptr(index.tok_centroid), _ptr(index.centroids), int(index.centroids.shape[0]), _ptr(index.weights),
+                index.nbits, _ptr(index.doc_blk), index.n_blk, index.corpus_len, dp, _ptr(q), nq, LQ, int(pool), _ptr(cand_off),
+                _ptr(cand_doc), int(cand_doc.shape[0]))
+
+    def colbert_res_score(self, index, q, pool, cand_off, cand_doc, pos_begin, cols, S):
+        """colbert_cand_score over the decoded rows of a ColBERTResidualIndex (dprhot_colbert_res_score)."""
+        self._require_gpu(S)
+        self._lib.check(self.lib.dprhot_colbert_res_score(*self._colbert_res_head(index, q, pool, cand_off, cand_doc), int(pos_begin),
+                                                          int(cols), _ptr(S), S.stride(0), self._stream()), "dprhot_colbert_res_score")
+
+    def colbert_res_search(self, index, q, pool, cand_off, cand_doc, max_count, values, indices, chunk, ws):
+        """colbert_cand_search over the decoded rows of a ColBERTResidualIndex (dprhot_colbert_res_search); always from an empty state."""
+        self._require_gpu(values, indices, ws)
+        self._lib.check(self.lib.dprhot_colbert_res_search(*self._colbert_res_head(index, q, pool, cand_off, cand_doc), int(max_count),
+                                                           values.shape[1], int(chunk), _ptr(values), _ptr(indices), _ptr(ws), ws.numel(),
+                                                           self._stream()), "dprhot_colbert_res_search")
+
     # -- SPAR: two resident indexes, a grid of weights in one pass (csrc/spar.h; DESIGN.md section 13; dpr_scale_amd/spar.py) ----
     def spar_workspace(self, nq, W, chunk, k, like):
         return self._chunk_workspace(self._lib.spar_workspace_bytes(nq, W, chunk), W * nq, k, like)

@@ -16,6 +16,9 @@ ColBERTPrunedRetrievalTask      ColBERTRetrievalTask with centroid pruning (DESI
                                 `ndocs` (None: every candidate is scored exactly) as its centroid-interaction stage (section 12.3).
                                 The three are class attributes of ColBERTRetrievalTask (None: exhaustive), whose constructor stays
                                 CITADELRetrievalTask's.  Over a product-quantised index pruning is refused (dense rows only).
+ColBERTResidualRetrievalTask    ColBERTRetrievalTask over a residual-compressed token index (colbert.ColBERTResidualIndex, DESIGN.md
+                                section 12.4), always with centroid pruning: the same kwargs plus `nbits` (2), `nprobe` and
+                                `n_centroids` (both required), `ndocs` and `save_compressed` (False).
 `kernels` (default: the HIP kernels) is the kernel object colbert.py takes.
 """
 import os
@@ -114,5 +117,38 @@ class ColBERTPQRetrievalTask(ColBERTRetrievalTask):
         index = colbert.load_index(self.ctx_embeddings_dir, len(self.ctxs), device, kernels=self.kernels, quantizer="pq",
                                    sub_vec_dim=self.sub_vec_dim)
         if self.save_quantized:
+            index.save(path)
+        return index
+
+
+class ColBERTResidualRetrievalTask(ColBERTRetrievalTask):
+    """ColBERTRetrievalTask over centroid ids plus `nbits` in {1, 2, 4} bits per feature of the residual, searched with search_pruned
+    (`nprobe`, `ndocs`).  `setup` loads `ctx_embeddings_dir/colbert_res.pt` when that file exists (colbert.load_residual_index);
+    otherwise it trains `n_centroids` centroids and the buckets on a sample of the token files and encodes them one at a time
+    (colbert.load_index(..., quantizer="residual")) -- the dense index is never built -- and writes the file when `save_compressed`
+    is set, so that a large index is not retrained at every start."""
+
+    RES_FILE = "colbert_res.pt"
+
+    def __init__(self, *args, nbits=2, nprobe=None, n_centroids=None, ndocs=None, save_compressed=False, **kwargs):
+        if nbits not in colbert.RES_NBITS:
+            raise NotImplementedError(f"nbits={nbits}: {colbert.RES_NBITS} bits per feature")
+        if nprobe is None or n_centroids is None:
+            raise ValueError("the residual index is searched with centroid pruning only: nprobe and n_centroids are required")
+        super().__init__(*args, **kwargs)  # refuses what the plain task refuses
+        self.nbits, self.nprobe, self.n_centroids, self.ndocs = int(nbits), nprobe, n_centroids, ndocs
+        self.save_compressed = bool(save_compressed)
+
+    def _load_index(self, device):
+        path = os.path.join(self.ctx_embeddings_dir, self.RES_FILE)
+        if os.path.exists(path):
+            index = colbert.load_residual_index(path, device, kernels=self.kernels)
+            if index.corpus_len != len(self.ctxs) or index.nbits != self.nbits:
+                raise ValueError(f"{path}: an index of {index.corpus_len} passages with nbits={index.nbits}; "
+                                 f"{len(self.ctxs)} passages and nbits={self.nbits} were asked for")
+            return index
+        index = colbert.load_index(self.ctx_embeddings_dir, len(self.ctxs), device, kernels=self.kernels, quantizer="residual",
+                                   nbits=self.nbits, n_centroids=int(self.n_centroids))
+        if self.save_compressed:
             index.save(path)
         return index

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define DPRHOT_VERSION 174 /* 0.1.74: + dprhot_ivf_workspace_bytes / _score / _search (inverted-index retrieval for CITADEL / COIL); dprhot_router_head_*, dprhot_ivf_compact / _gather, dprhot_maxsim_score and dprhot_pq_encode / dprhot_ivf_pq_score / _search, dprhot_colbert_*, dprhot_colbert_pq_*, dprhot_colbert_cand_* and dprhot_colbert_cen_* joined without a bump: tests/test_ivf.py pins this number */
+#define DPRHOT_VERSION 174 /* 0.1.74: + dprhot_ivf_workspace_bytes / _score / _search (inverted-index retrieval for CITADEL / COIL); dprhot_router_head_*, dprhot_ivf_compact / _gather, dprhot_maxsim_score and dprhot_pq_encode / dprhot_ivf_pq_score / _search, dprhot_colbert_*, dprhot_colbert_pq_*, dprhot_colbert_cand_*, dprhot_colbert_cen_* and dprhot_colbert_res_* joined without a bump: tests/test_ivf.py pins this number */
 
 #define DPRHOT_OK 0
 #define DPRHOT_E_INVALID (-1)     /* bad argument (NULL pointer, non-positive or misaligned size) */
@@ -532,6 +532,42 @@ int dprhot_colbert_cen_score(const int64_t* doc_cen_off, const int32_t* doc_cen,
 int dprhot_colbert_cen_search(const int64_t* doc_cen_off, const int32_t* doc_cen, int64_t n_pairs, int64_t corpus_len, int C, const float* T,
                               int nq, int LQ, int pool, const int64_t* cand_off, const int32_t* cand_doc, int64_t n_cand, int64_t max_count,
                               int k, int chunk, float* values, int64_t* indices, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Residual-compressed token index under the pruned search (csrc/colbert_res.h): the ColBERTv2 format.  nbits (NB)
+ * in {1, 2, 4}, dp in {32, 64, 96, 128}, rb = dp * NB / 8 bytes per row; ONE bucket set per index, cutoffs fp32 [2^NB - 1] (ascending)
+ * and weights fp32 [2^NB].  The block layout is that of dprhot_colbert_score; a token row is tok_centroid int32 [n_blk * 16] (its
+ * centroid among centroids bf16 [C, dp]) and res_code uint8 [n_blk * 16, rb] with
+ *   code(r, t) = (res_code[r][t * NB / 8] >> (NB * (t mod (8 / NB)))) & (2^NB - 1)        (little-endian inside a byte)
+ * The index stands for the dense index
+ *   tok[r][t] = 0 <= tok_centroid[r] < C ? bf16_rne(float(centroids[tok_centroid[r]][t]) + weights[code(r, t)]) : 0
+ * (ONE fp32 addition, then round to nearest even; non-finite centroids are outside the contract).  A row whose id is negative (padding)
+ * or >= C is an exact zero whatever its code bytes hold and its id is never used as an index; every code value decodes.
+ * dprhot_colbert_res_encode WRITES every byte of res_code [n_rows, rb] and nothing else, for tok bf16 [n_rows, dp] (any rows, not only
+ * a block layout) and their ids tok_centroid [n_rows]:
+ *   code(r, t) = number of j with float(tok[r][t]) - float(centroids[tok_centroid[r]][t]) > cutoffs[j]       (one fp32 subtraction)
+ * which is torch.bucketize(res, cutoffs) for a non-NaN residual; a NaN residual encodes as 0; a row whose id lies outside [0, C) gets
+ * zero bytes.  Two runs are bit-identical.
+ * dprhot_colbert_res_score has the contract of dprhot_colbert_cand_score over the decoded index: the same window, the same NaN cells,
+ * every other cell bit for bit the cell dprhot_colbert_cand_score writes for `tok` above (the bf16 fed to the MFMA is the decoded
+ * row's, in the same k order).  Bounds: those of dprhot_colbert_cand_score; nothing behind res_code[n_blk * 16 * rb - 1],
+ * tok_centroid[n_blk * 16 - 1] or centroids[C * dp - 1] is read whatever the index holds.  n_blk == 0 scores 0 for present candidates.
+ * dprhot_colbert_res_search is dprhot_colbert_cand_search with this score: positions [0, max_count) through the one chunk driver, the
+ * streaming top-k from an empty state (the wide selection above k = 4096), ONE final launch from positions to doc ids.
+ * workspace: dprhot_colbert_cand_workspace_bytes(nq, chunk) (+ dprhot_topk_wide_workspace_bytes(nq, k) behind it when k > 4096);
+ * DPRHOT_E_WORKSPACE when smaller.
+ * Limits (DPRHOT_E_INVALID): those of dprhot_colbert_cand_score / _search, plus nbits in {1, 2, 4}, C >= 1, dp % 32 == 0, non-NULL
+ * centroids / weights / cutoffs / tok_centroid (with n_blk > 0 / n_rows > 0), res_code, tok and centroids 16-byte aligned,
+ * 0 <= n_rows < 2^40; dp > 128: DPRHOT_E_UNSUPPORTED. */
+int dprhot_colbert_res_encode(const dprhot_bf16* tok, const int32_t* tok_centroid, int64_t n_rows, int dp, const dprhot_bf16* centroids,
+                              int C, const float* cutoffs, int nbits, uint8_t* res_code, void* stream);
+int dprhot_colbert_res_score(const uint8_t* res_code, const int32_t* tok_centroid, const dprhot_bf16* centroids, int C, const float* weights,
+                             int nbits, const int64_t* doc_blk, int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok, int nq,
+                             int LQ, int pool, const int64_t* cand_off, const int32_t* cand_doc, int64_t n_cand, int64_t pos_begin, int cols,
+                             float* S, int64_t ld, void* stream);
+int dprhot_colbert_res_search(const uint8_t* res_code, const int32_t* tok_centroid, const dprhot_bf16* centroids, int C, const float* weights,
+                              int nbits, const int64_t* doc_blk, int64_t n_blk, int64_t corpus_len, int dp, const dprhot_bf16* q_tok, int nq,
+                              int LQ, int pool, const int64_t* cand_off, const int32_t* cand_doc, int64_t n_cand, int64_t max_count, int k,
+                              int chunk, float* values, int64_t* indices, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Product-quantised token index for the ColBERT search (csrc/colbert_pq.h).  dsub in {2, 4, 8}, m = dp / dsub,
  * dp in {32, 64, 96, 128}, ONE codebook bf16 [m, 256, dsub] per index (the layout and the decode rule of the product-quantised postings
