@@ -194,6 +194,26 @@ def version() -> int:
 
 
 
+_capture_info = None
+
+
+def capture_id(stream: int) -> int:
+    """The id the HIP runtime gave the capture `stream` (a hipStream_t as an integer) is in, 0 when it is not capturing.  Holders of
+    cached device memory (hotpath._ExpectedGradScale) tell one capture's steps from another's by it.  hipStreamGetCaptureInfo is
+    resolved through libdprhot.so, which is linked to the one HIP runtime of the process."""
+    global _capture_info
+    if not stream:
+        return 0  # the null stream never captures (and asking it during another stream's capture would invalidate that capture)
+    if _capture_info is None:
+        _capture_info = lib.hipStreamGetCaptureInfo
+        _capture_info.restype = c_int
+        _capture_info.argtypes = [c_void_p, POINTER(c_int), POINTER(ctypes.c_ulonglong)]
+    status, cid = c_int(0), ctypes.c_ulonglong(0)
+    if _capture_info(stream, ctypes.byref(status), ctypes.byref(cid)) != 0:
+        return -1  # a failed query counts as a capture: the caller then keeps memory
+    return 0 if status.value == 0 else (cid.value or -1)
+
+
 def options_epoch() -> int:
     """The LIBRARY's own counter (dprhot_options_epoch, bumped by every dprhot_set_option whoever calls it): host-side caches of plan
     facts (slab counts, whether a step wants a G buffer) key on it."""

@@ -197,6 +197,24 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
+// Scratch that a call needs zeroed is zeroed by a KERNEL of the caller's stream, never by hipMemsetAsync: the candidate counters of the
+// filtered searches (dprhot_search, dprhot_spar_search, dprhot_dense_fp8_search), the rank counters of dprhot_sim_rank / _rank_loss and
+// the score buffer of an IVF search without CLS vectors.  Eagerly the memsets did their work.  OBSERVED: with the memset captured as
+// the FIRST node of a graph and the graph replayed right behind a caller's fill of the workspace on the same stream, the zeroes were
+// absent when the next kernel node ran -- the IVF scores came out on top of the fill pattern in one run of two, and dprhot_search,
+// whose filter epilogues then indexed their candidate lists by atomicAdd(&cnt[row], 1) without a bound, stored far outside the
+// workspace and faulted (tests/test_stream_capture_gpu.py, rows `ivf-no-cls` and `search`).  SUPPOSED, not established: that the
+// runtime does not order such a memset node behind work already queued on the launching stream.  Either way a kernel node is ordered
+// like every other launch of the call, and the epilogues now check the position against the list's length (gemm_bf16.h, gemm8p.h,
+// spar.h, dense_fp8.h; the merge clamps the count it reads): a stale counter can lose candidates, it cannot store or read outside.
+__global__ void zero_words_kernel(unsigned* p, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = 0u;
+}
+int zero_words(void* p, size_t n_words, hipStream_t st) {
+  const size_t blocks = (n_words + 255) / 256;
+  return launch<zero_words_kernel>(dim3((unsigned)(blocks < 1 ? 1 : (blocks > 4096 ? 4096 : blocks))), dim3(256), 0, st, static_cast<unsigned*>(p), n_words);
+}
+
 bool use_tr() { return opt(OPT_NO_TR) == 0; }
 
 int force_tile() { return opt(OPT_TILE); }
@@ -1892,7 +1910,7 @@ int dprhot_search(const dprhot_bf16* Q, int nq, const dprhot_bf16* C, int64_t n_
   float* S = static_cast<float*>(workspace);
   int* cand_j = reinterpret_cast<int*>(static_cast<char*>(workspace) + (size_t)nq * chunk * 4);
   int* cnt = reinterpret_cast<int*>(static_cast<char*>(workspace) + (size_t)nq * chunk * 8);
-  HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)nq * sizeof(int), st));
+  if (int rc = zero_words(cnt, (size_t)nq, st)) return rc;
   return search_plan(nq, n_ctx, d, chunk, first, [&](const SearchStep& s) -> int {
     const int cols = s.cols;
     const int64_t j0 = s.j0;
@@ -1989,7 +2007,7 @@ int dprhot_sim_rank(const dprhot_bf16* Q, int B, const dprhot_bf16* C, int Nc, i
   epi.gold_val = gold;
   epi.count = count;
   if (int rc = launch<g8_gold_kernel>(dim3(cdiv(B, 32)), dim3(64), 0, st, Q, C, B, Nc, d, y, y_offset, epi.sim, inv_T, gold)) return rc;
-  HIP_TRY(hipMemsetAsync(count, 0, (size_t)B * sizeof(int), st));
+  if (int rc = zero_words(count, (size_t)B, st)) return rc;
   GemmArgs a8{Q, C, B, Nc, d, d, d, d};
   if (int rc = launch_g8(a8, epi, st)) return rc;
   return launch<g8_rank_finish_kernel>(dim3(cdiv(B, 256)), dim3(256), 0, st, count, B, rank);
@@ -2023,7 +2041,7 @@ int dprhot_sim_rank_loss(const dprhot_bf16* Q, int B, const dprhot_bf16* C, int 
   epi.part_s = reinterpret_cast<float*>(ws + wl.part_s);
   epi.npart = cdiv(Nc, G2_B) * 4;
   if (int rc = launch<g8_gold_kernel>(dim3(cdiv(B, 32)), dim3(64), 0, st, Q, C, B, Nc, d, y, y_offset, epi.sim, inv_T, gold)) return rc;
-  HIP_TRY(hipMemsetAsync(count, 0, (size_t)B * sizeof(int), st));
+  if (int rc = zero_words(count, (size_t)B, st)) return rc;
   GemmArgs a8{Q, C, B, Nc, d, d, d, d};
   if (int rc = launch_g8(a8, epi, st)) return rc;
   if (int rc = launch<g8_rank_finish_kernel>(dim3(cdiv(B, 256)), dim3(256), 0, st, count, B, rank)) return rc;
@@ -2648,7 +2666,7 @@ static int ivf_search_with(Score score, int nq, const dprhot_bf16* cls_q, const 
     if (cls_q) {
       if (int rc = dprhot_sim_fwd(cls_q, nq, cls_doc + (size_t)j0 * dc, ld, dc, nullptr, 1.0f, S, stream)) return rc;
     } else {
-      HIP_TRY(hipMemsetAsync(S, 0, (size_t)nq * ld * sizeof(float), (hipStream_t)stream));
+      if (int rc = zero_words(S, (size_t)nq * ld, (hipStream_t)stream)) return rc;
     }
     return score(j0, cols, S, ld);
   };
@@ -3212,7 +3230,7 @@ int dprhot_spar_search(const dprhot_bf16* Q1, const dprhot_bf16* Q2, int nq, int
   float* S = static_cast<float*>(workspace);
   int* cand_j = reinterpret_cast<int*>(static_cast<char*>(workspace) + (size_t)rows * chunk * 4);
   int* cnt = reinterpret_cast<int*>(static_cast<char*>(workspace) + (size_t)rows * chunk * 8);
-  HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)rows * sizeof(int), st));
+  if (int rc = zero_words(cnt, (size_t)rows, st)) return rc;
   for (int64_t j0 = id_begin; j0 < id_end; j0 += chunk) {
     const int cols = (int)(id_end - j0 < chunk ? id_end - j0 : chunk);
     const int ld = (cols + 7) / 8 * 8;  // (<= chunk: chunk is a multiple of 8)
@@ -3323,7 +3341,7 @@ int dprhot_dense_fp8_search(const uint8_t* Qc, const float* qs, int nq, const ui
   float* S = static_cast<float*>(workspace);
   int* cand_j = reinterpret_cast<int*>(static_cast<char*>(workspace) + (size_t)nq * chunk * 4);
   int* cnt = reinterpret_cast<int*>(static_cast<char*>(workspace) + (size_t)nq * chunk * 8);
-  HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)nq * sizeof(int), st));
+  if (int rc = zero_words(cnt, (size_t)nq, st)) return rc;
   for (int64_t j0 = id_begin; j0 < id_end; j0 += chunk) {
     const int cols = (int)(id_end - j0 < chunk ? id_end - j0 : chunk);
     const int ld = (cols + 7) / 8 * 8;  // (<= chunk: chunk is a multiple of 8)

@@ -974,8 +974,10 @@ struct Epi8Filter {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           if ((mask >> (b * 16 + r)) & 1u) {
-            cand_v[(size_t)m * N + pos] = acc.v[a][b][r];
-            cand_j[(size_t)m * N + pos] = j_bias + t.n0 + t.wn * 64 + b * 32 + (r >> 2) * 8 + h * 4 + (r & 3);
+            if ((unsigned)pos < (unsigned)N) {  // a row's list holds N entries: a stale counter loses candidates, it never stores outside
+              cand_v[(size_t)m * N + pos] = acc.v[a][b][r];
+              cand_j[(size_t)m * N + pos] = j_bias + t.n0 + t.wn * 64 + b * 32 + (r >> 2) * 8 + h * 4 + (r & 3);
+            }
             ++pos;
           }
         }

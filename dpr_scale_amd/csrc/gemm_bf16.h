@@ -756,6 +756,7 @@ struct EpiFilter {
           }
           if (take) {
             const int pos = atomicAdd(&cnt[m], 1);
+            if ((unsigned)pos >= (unsigned)N) continue;  // a row's list holds N entries: a stale counter loses candidates, it never stores outside
             cand_v[(size_t)m * N + pos] = v;
             cand_j[(size_t)m * N + pos] = n;
           }

@@ -29,6 +29,7 @@ using pstep_fn = int (*)(const float*, const void*, void*, int, int, int, int, i
 using rows_fn = int (*)(int, int, int*);
 using cast_fn = int (*)(const float*, void*, size_t, void*);
 using epoch_fn = long long (*)();
+using capinfo_fn = int (*)(void*, int*, unsigned long long*);  // hipStreamGetCaptureInfo of the HIP runtime libdprhot.so is linked to
 
 struct Api {
   ws_fn workspace_bytes = nullptr;
@@ -40,6 +41,7 @@ struct Api {
   rows_fn packed_rows = nullptr;
   cast_fn cast_bf16 = nullptr;
   epoch_fn options_epoch = nullptr;
+  capinfo_fn capture_info = nullptr;
 } g_api;
 
 struct Plan { size_t ws_bytes; int wants_g, nslabs; };
@@ -48,6 +50,11 @@ std::map<std::tuple<int, int, int, int64_t>, Plan> g_plans;  // (B, Nc, d, the L
 // one workspace per (device, stream): steps on different streams never share one, and the tensor is allocated on the stream that
 // uses it (the caching allocator orders reuse on the allocating stream)
 std::map<std::pair<int, void*>, at::Tensor> g_ws;
+// LIFETIME RULE of the two caches here (g_ws, g_scale): a captured graph bakes in every address a library call received, so a cached
+// tensor that is handed out while its stream is capturing is kept for the life of the process (g_kept) -- replacing it later, eagerly
+// or under capture, only drops the cache's own reference, never the memory a replay still reads or writes.  These are four-byte
+// scalars and a few workspaces per capture.
+std::map<void*, at::Tensor> g_kept;  // by data pointer: one reference per tensor
 std::map<std::tuple<int, int, int, int64_t>, int> g_dc_bf16_ok;  // (B, Nc, d, epoch) -> this shape's plan has a bf16 dC epilogue (1) or not (0)
 
 void check(int rc, const char* what) {
@@ -67,9 +74,11 @@ bool init(const std::string& lib_path) {
   g_api.packed_rows = (rows_fn)dlsym(h, "dprhot_packed_rows");
   g_api.cast_bf16 = (cast_fn)dlsym(h, "dprhot_cast_bf16");
   g_api.options_epoch = (epoch_fn)dlsym(h, "dprhot_options_epoch");
+  g_api.capture_info = (capinfo_fn)dlsym(h, "hipStreamGetCaptureInfo");  // (found in the library's own dependency, the HIP runtime)
   TORCH_CHECK(g_api.workspace_bytes && g_api.step_wants_g && g_api.train_dq_slabs && g_api.last_error && g_api.train_step_f32 && g_api.rescale_grads &&
                   g_api.train_step_packed_f32 && g_api.packed_rows && g_api.cast_bf16 && g_api.options_epoch,
               "libdprhot.so lacks an entry point of include/dprhot.h");
+  TORCH_CHECK(g_api.capture_info, "the HIP runtime behind libdprhot.so lacks hipStreamGetCaptureInfo");
   return true;
 }
 
@@ -87,13 +96,28 @@ Plan plan_of(int B, int Nc, int d, int64_t /*caller's epoch: superseded by the l
   return p;
 }
 
+// The id the runtime gave the capture `stream` is in, 0 when it is not capturing (the null stream never is, and asking it during
+// another stream's capture would invalidate that capture).  A failed query counts as a capture (id ~0): the caller then keeps memory.
+unsigned long long capture_id(void* stream) {
+  if (stream == nullptr) return 0;
+  int status = 0;
+  unsigned long long id = 0;
+  if (g_api.capture_info(stream, &status, &id) != 0) return ~0ull;
+  return status == 0 ? 0 : (id ? id : ~0ull);
+}
+
+void keep(const at::Tensor& t) { g_kept.emplace(t.data_ptr(), t); }  // (g_mu held)
+
 // The tensor is returned BY VALUE: the caller holds it across its launches, so a concurrent call that grows the map's entry cannot
-// free memory this call's kernels are about to use.
+// free memory this call's kernels are about to use.  Handed out under capture it is kept (the lifetime rule above): a larger shape
+// that arrives later replaces the entry, and the captured graph goes on writing into the buffer it was given.
 at::Tensor workspace(const at::Device& dev, void* stream, size_t bytes) {
+  const bool capturing = capture_id(stream) != 0;
   std::lock_guard<std::mutex> lk(g_mu);
   at::Tensor& w = g_ws[std::make_pair((int)dev.index(), stream)];
   if (!w.defined() || (size_t)w.numel() < bytes)
     w = at::empty({(int64_t)std::max<size_t>(bytes, 1 << 20)}, at::TensorOptions().dtype(at::kByte).device(dev));
+  if (capturing) keep(w);
   return w;
 }
 
@@ -234,18 +258,47 @@ std::vector<at::Tensor> packed_backward(const at::Tensor& dQ, const c10::optiona
 // computed by the forward call for the grad_output the previous backward saw (a device scalar per (device, B, Nc, d)), backward
 // compares and rescales in one launch (dprhot_rescale_grads) and hands the tensors to autograd without keeping a reference --
 // AccumulateGrad takes a gradient nobody else holds as .grad itself instead of cloning it.
-std::map<std::tuple<int, int, int, int>, at::Tensor> g_scale;  // (device, B, Nc, d) -> [1] fp32: expected grad_output
+// Eager steps and captured steps keep separate chains.  A scalar published under capture lives in the graph's pool and holds nothing
+// until the first replay, so it is visible to steps of THAT capture only (g_scale_cap, by capture id); the first captured step of a site
+// reads the eager entry, which is kept from then on (the lifetime rule above): replays read it as `used` for ever, and
+// dprhot_rescale_grads makes the gradients right whatever it holds.
+// (g_scale_cap keeps the last scalar of a finished capture -- a block of that graph's pool, even after the graph is gone -- until the
+// next capture at the same site overwrites it: nobody reads it, its id matches no other capture.  Captures whose id query fails all
+// get the id ~0 and would share one chain: the later one then reads the earlier one's last scalar as `used`, which the rescale makes
+// right like any other value.)
+using site_key = std::tuple<int, int, int, int>;
+std::map<site_key, at::Tensor> g_scale;  // (device, B, Nc, d) -> [1] fp32: expected grad_output
+std::map<site_key, std::pair<unsigned long long, at::Tensor>> g_scale_cap;  // -> (capture id, the scalar its last captured backward wrote)
 py::object* g_regen = nullptr;  // Python: second backward through a retained graph (hotpath._opx_regen); leaked on purpose (interpreter exit)
 
 at::Tensor scale_get(const at::Device& dev, int B, int Nc, int d) {
+  const unsigned long long cid = capture_id((void*)c10::hip::getCurrentHIPStream(dev.index()).stream());
   std::lock_guard<std::mutex> lk(g_mu);
-  at::Tensor& t = g_scale[std::make_tuple((int)dev.index(), B, Nc, d)];
-  if (!t.defined()) t = at::ones({1}, at::TensorOptions().dtype(at::kFloat).device(dev));
-  return t;
+  const site_key key = std::make_tuple((int)dev.index(), B, Nc, d);
+  if (cid != 0) {
+    auto it = g_scale_cap.find(key);
+    if (it != g_scale_cap.end() && it->second.first == cid) return it->second.second;
+  }
+  auto it = g_scale.find(key);
+  if (it == g_scale.end()) {
+    at::Tensor one = at::ones({1}, at::TensorOptions().dtype(at::kFloat).device(dev));
+    if (cid != 0) {  // no eager step came first: the fill is part of the graph, the scalar belongs to this capture
+      g_scale_cap[key] = std::make_pair(cid, one);
+      return one;
+    }
+    it = g_scale.emplace(key, one).first;
+  }
+  if (cid != 0) keep(it->second);
+  return it->second;
 }
 void scale_put(const at::Device& dev, int B, int Nc, int d, const at::Tensor& t) {
+  const unsigned long long cid = capture_id((void*)c10::hip::getCurrentHIPStream(dev.index()).stream());
   std::lock_guard<std::mutex> lk(g_mu);
-  g_scale[std::make_tuple((int)dev.index(), B, Nc, d)] = t;
+  const site_key key = std::make_tuple((int)dev.index(), B, Nc, d);
+  if (cid != 0)
+    g_scale_cap[key] = std::make_pair(cid, t);
+  else
+    g_scale[key] = t;
 }
 
 struct InBatchFn : public torch::autograd::Function<InBatchFn> {

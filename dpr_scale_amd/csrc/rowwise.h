@@ -919,7 +919,7 @@ __global__ __launch_bounds__(256, TK_P <= 1024 ? 4 : 2) void topk_stream_kernel(
   const int row = blockIdx.x, tid = threadIdx.x, k = p.k;
   const float* Srow = p.S + (size_t)row * p.ld;
   const int* Jrow = p.cand_j != nullptr ? p.cand_j + (size_t)row * p.ld : nullptr;
-  const int ncols = p.cnt != nullptr ? p.cnt[row] : p.cols;
+  const int ncols = p.cnt != nullptr ? min(max(p.cnt[row], 0), p.cols) : p.cols;  // (a list never holds more than the chunk's columns)
   if (p.cnt != nullptr && ncols == 0) return;  // (uniform) nothing qualified for this row in this chunk
   for (int i = tid; i < k; i += 256) {
     const long long j = p.first ? -1 : (long long)p.idx[(size_t)row * k + i];

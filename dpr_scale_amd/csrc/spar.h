@@ -195,6 +195,7 @@ __global__ __launch_bounds__(256) void spar_kernel(SparArgs p) {
             }
             if (take) {
               const int pos = atomicAdd(&p.cnt[row], 1);
+              if ((unsigned)pos >= (unsigned)p.ldc) continue;  // a row's list holds ldc entries: a stale counter never stores outside it
               p.cand_v[row * (size_t)p.ldc + pos] = v;
               p.cand_j[row * (size_t)p.ldc + pos] = n;
             }

@@ -24,9 +24,28 @@ _KIND = {torch.bfloat16: 0, torch.float16: 1, torch.float32: 2}  # storage kinds
 class _ExpectedGradScale:
     """Per device: the DEVICE scalar the next training step should scale its gradients by -- the grad_output the previous backward
     saw (AMP's loss scale; 1 for a plain backward()).  Every backward publishes a FRESH one-float tensor (written once by
-    dprhot_rescale_grads, never modified afterwards), so a step that read an older one can still compare against it."""
+    dprhot_rescale_grads, never modified afterwards), so a step that read an older one can still compare against it.
+
+    Lifetime under graph capture (the same rule as g_scale in csrc/opx.cpp).  A captured graph bakes in the address of the scalar its
+    forward read, so an entry handed out while the current stream is capturing is kept for the life of the process (_kept): replacing
+    it later never frees memory a replay reads.  Eager steps and captured steps keep separate chains: a scalar published under capture
+    lives in the graph's pool and holds nothing until the first replay, so only steps of THAT capture see it (_cap, by capture id).
+    Replays read the kept eager scalar as `used` for ever; dprhot_rescale_grads makes the gradients right whatever it holds.
+    Two things that look like leaks and are not: _cap keeps the last scalar of a finished capture (a block of that graph's pool, even
+    after the graph is gone) until the next capture at the same site overwrites it -- nobody reads it, its id matches no other capture;
+    and a capture whose id query fails gets the id -1 (_lib.capture_id), so two such captures would share one chain: the second would
+    then read the first one's last scalar as `used`, which the rescale makes right like any other value."""
 
     _cur = {}
+    _cap = {}   # (dev, site) -> (capture id, the scalar the capture's last backward wrote)
+    _kept = {}  # data_ptr -> tensor: eager entries whose address a captured graph holds
+
+    @staticmethod
+    def _capture_id(dev):
+        if torch.device(dev).type != "cuda" or not torch.cuda.is_current_stream_capturing():
+            return 0
+        from . import _lib
+        return _lib.capture_id(torch.cuda.current_stream(dev).cuda_stream)
 
     @classmethod
     def get(cls, dev, site=None):
@@ -34,14 +53,29 @@ class _ExpectedGradScale:
         main loss receive different constant upstream factors in the same step; one shared prediction made each of them mispredict
         the other every step (and pay the full rescale pass)."""
         k = (dev, site)
+        cid = cls._capture_id(dev)
+        if cid:
+            e = cls._cap.get(k)
+            if e is not None and e[0] == cid:
+                return e[1]
         t = cls._cur.get(k)
         if t is None:
-            t = cls._cur[k] = torch.ones(1, dtype=torch.float32, device=dev)
+            t = torch.ones(1, dtype=torch.float32, device=dev)
+            if cid:  # no eager step came first: the fill is part of the graph, the scalar belongs to this capture
+                cls._cap[k] = (cid, t)
+                return t
+            cls._cur[k] = t
+        if cid:
+            cls._kept[t.data_ptr()] = t
         return t
 
     @classmethod
     def publish(cls, dev, t, site=None):
-        cls._cur[(dev, site)] = t
+        cid = cls._capture_id(dev)
+        if cid:
+            cls._cap[(dev, site)] = (cid, t)
+        else:
+            cls._cur[(dev, site)] = t
 
 
 def _fp32_g_mode():
@@ -95,6 +129,7 @@ class HipKernels:
         self._lib = _lib
         self.lib = _lib.lib
         self._ws = {}
+        self._ws_kept = {}
         self._nslabs = {}
         self._wg = {}
 
@@ -111,10 +146,16 @@ class HipKernels:
         return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
     def _workspace(self, device, nbytes):
-        ws = self._ws.get(device)
+        """The cached step workspace, one per (device, stream) as in csrc/opx.cpp: steps on two streams never share one.  A buffer handed
+        out while the stream is capturing is kept for the life of the process (_ws_kept): the graph bakes its address in, and a larger
+        shape that replaces the entry later must not free what a replay still writes into."""
+        key = (device, torch.cuda.current_stream(device).cuda_stream)
+        ws = self._ws.get(key)
         if ws is None or ws.numel() < nbytes:
             ws = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
-            self._ws[device] = ws
+            self._ws[key] = ws
+        if torch.cuda.is_current_stream_capturing():
+            self._ws_kept[ws.data_ptr()] = ws
         return ws
 
     def empty(self, shape, dtype, like):

@@ -15,8 +15,15 @@
  *   - Every pointer is a DEVICE pointer owned by the caller (e.g. torch's caching allocator) unless its
  *     name starts with h_.  Nothing is allocated, freed or retained by the library.
  *   - All matrices are row-major and contiguous; rows are 16-byte aligned: d % 8 == 0, Nc % 8 == 0.
- *   - `stream` is a hipStream_t passed as void* (NULL = the null stream).  Kernels are enqueued
- *     asynchronously; no entry point synchronises with the host.
+ *   - `stream` is a hipStream_t passed as void* (NULL = the null stream).  The stream contract: a call ONLY ENQUEUES on `stream`
+ *     (kernel launches and nothing else -- no memset, no copy; nothing on another stream or the null stream), it DOES NOT SYNCHRONISE with the host or
+ *     read device memory from the host -- loop bounds that live in device memory (labels, masks, offsets, candidate lists) are read
+ *     by the kernels, every time -- and it MAY BE CAPTURED into a HIP graph (hipStreamBeginCapture on `stream`) after one eager call at
+ *     the same shape, which is when anything lazily initialised gets initialised.  A replay computes what the eager call computes for
+ *     whatever the buffers then hold, bit for bit (tests/test_stream_capture_gpu.py holds every stream-taking entry point to this).
+ *     The exception are the collectives (dprhot_allgather_ctx, _reducescatter_dc, _reducescatter_rows, _allreduce_sum,
+ *     _allgather_allpairs, _reducescatter_allpairs): they hand `stream` to RCCL, and a capture next to a live communicator is
+ *     outside this contract.
  *   - bf16 values travel as uint16_t bit patterns (round-to-nearest-even from fp32).
  *   - Return value: 0 = OK, <0 = error (DPRHOT_E_*); dprhot_last_error() returns a thread-local message.
  *     Functions are re-entrant; the only process-wide state is the explicit option table below (test / A-B switches that
