@@ -1,4 +1,4 @@
-"""ctypes binding of libdprhot.so (include/dprhot.h).  There is no CPU fallback: if the library is missing
+"""ctypes binding of libdprhot.so (include/dprhot.h and include/dprhot_union.h).  There is no CPU fallback: if the library is missing
 or fails to load, importing this module raises -- the product path must fail loudly (it never routes
 through oracle/)."""
 import ctypes
@@ -172,7 +172,16 @@ SIGNATURES = {
                                    c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
-for _name, (_res, _args) in SIGNATURES.items():
+# the candidate stage of the pruned ColBERT search: every symbol include/dprhot_union.h declares (tests/test_colbert_union.py checks),
+# exported by the same library.  A table of its own: SIGNATURES is held equal to include/dprhot.h
+UNION_SIGNATURES = {
+    "dprhot_colbert_union_workspace_bytes": (c_int, [c_int, c_int64, POINTER(c_size_t)]),
+    "dprhot_colbert_union_count": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                           c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dprhot_colbert_union_fill": (c_int, [c_int, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_size_t, c_void_p]),
+}
+
+for _name, (_res, _args) in (*SIGNATURES.items(), *UNION_SIGNATURES.items()):
     _fn = getattr(lib, _name)  # AttributeError here == ABI mismatch: fail at import
     _fn.restype = _res
     _fn.argtypes = _args
@@ -304,6 +313,12 @@ def colbert_workspace_bytes(nq: int, chunk: int) -> int:
 def colbert_cand_workspace_bytes(nq: int, chunk: int) -> int:
     out = c_size_t(0)
     check(lib.dprhot_colbert_cand_workspace_bytes(int(nq), int(chunk), ctypes.byref(out)), "dprhot_colbert_cand_workspace_bytes")
+    return out.value
+
+
+def colbert_union_workspace_bytes(nq: int, corpus_len: int) -> int:
+    out = c_size_t(0)
+    check(lib.dprhot_colbert_union_workspace_bytes(int(nq), int(corpus_len), ctypes.byref(out)), "dprhot_colbert_union_workspace_bytes")
     return out.value
 
 

@@ -31,6 +31,11 @@ passages -- with the exhaustive score, bit for bit (dprhot_colbert_cand_search) 
 the candidate set; what it may lose is a passage none of whose tokens lies in a probed centroid.  Assignment and probing are exact bf16
 top-k searches on the MFMA path (hotpath.CorpusSearch), ties to the lower centroid id.
 
+Candidate lists: the union is built by kernels (dprhot_colbert_union_count / _fill: a bitmap of the corpus per
+query, marked with atomic ORs and read out in order -- no sort) whenever the index's kernel set defines `colbert_union_count`, as
+hotpath.HipKernels does; queries go through in batches whose bitmaps stay under UNION_WS_BYTES.  A kernel set without that method takes
+`_union_torch`, the same lists from torch.unique: it is the definition the kernels are held to.
+
 Centroid interaction: `search_pruned(..., ndocs=n)` first scores every candidate approximately, each passage
 token replaced by its centroid --
 
@@ -66,6 +71,7 @@ _POOL = {"sum": 0, "max": 1}  # DPRHOT_POOL_SUM / DPRHOT_POOL_MAX
 BLOCK = 16                    # token rows per block: one MFMA fragment, one passage
 MAX_QUERY_LEN = 512           # DPRHOT_MAXSIM_MAX_LEN
 CEN_TABLE_BYTES = 1 << 28     # centroid interaction: queries go through in batches whose table fp32 [b, C, LT] stays under this (b >= 1)
+UNION_WS_BYTES = 1 << 28      # candidate lists: queries go through in batches whose membership bitmaps stay under this (b >= 1)
 PQ_MAX_DP = 128               # dprhot_colbert_pq_score keeps the codebook (dp * 512 bytes) in LDS and the query fragments in registers
 
 
@@ -225,6 +231,43 @@ class _CentroidPruning:
         return self._union(qb, self._probe(qb, nprobe))
 
     def _union(self, qb, cids):
+        """(cand_off, cand_doc, n_cand, max_count) of `candidates` from the probed centroid ids [nq, LQ, nprobe].  Runs the kernels of
+        DESIGN.md section 12.5 (dprhot_colbert_union_count / _fill) when the index's kernel set defines `colbert_union_count` --
+        hotpath.HipKernels does -- and `_union_torch`, the definition, otherwise.  The kernel route takes the queries in batches whose
+        workspace stays under UNION_WS_BYTES; each batch makes ONE host read (its two counts, which size cand_doc)."""
+        kn = self._kernels()
+        if not hasattr(kn, "colbert_union_count"):  # the one capability check: kernel sets written before section 12.5 keep the torch route
+            return self._union_torch(qb, cids)
+        self._need_centroids()
+        nq, dev = int(qb.shape[0]), self.device
+        cids = cids.to(torch.int64).contiguous()
+        cand_off = torch.empty(nq + 1, dtype=torch.int64, device=dev)
+        parts, n_cand, max_count = [], 0, 0
+        for lo, hi in self._union_batches(nq):
+            ws = kn.colbert_union_workspace(hi - lo, self.corpus_len, self.cen_off)
+            off, totals = cand_off[lo:hi + 1], torch.empty(2, dtype=torch.int64, device=dev)
+            if lo:  # a later batch counts into a buffer of its own: its offsets start at 0 and are shifted behind the fill
+                off = torch.empty(hi - lo + 1, dtype=torch.int64, device=dev)
+            kn.colbert_union_count(self, cids[lo:hi], qb[lo:hi], off, totals, ws)
+            n, longest = totals.tolist()
+            docs = torch.empty(n, dtype=torch.int32, device=dev)
+            kn.colbert_union_fill(self, off, docs, ws)
+            if lo:
+                cand_off[lo + 1:hi + 1] = off[1:] + n_cand
+            parts.append(docs)
+            n_cand, max_count = n_cand + n, max(max_count, longest)
+        return cand_off, parts[0] if len(parts) == 1 else torch.cat(parts), n_cand, max_count
+
+    def _union_batches(self, nq):
+        """(lo, hi) query ranges whose union workspace (a bitmap of corpus_len bits per query) stays under UNION_WS_BYTES, at least one
+        query each; no range has more than the 65535 queries of one launch."""
+        from . import _lib
+
+        per_query = _lib.colbert_union_workspace_bytes(1, self.corpus_len)  # host code; n queries need at most n times this
+        step = min(65535, max(1, UNION_WS_BYTES // per_query))
+        return [(lo, min(lo + step, nq)) for lo in range(0, nq, step)]
+
+    def _union_torch(self, qb, cids):
         """(cand_off, cand_doc, n_cand, max_count) of `candidates` from the probed centroid ids [nq, LQ, nprobe]; ONE host read of its
         own (the two counts) -- torch.unique and repeat_interleave size their outputs on the host themselves."""
         C, dev = self._need_centroids(), self.device

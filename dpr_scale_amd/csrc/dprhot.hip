@@ -3364,3 +3364,5 @@ int dprhot_dense_fp8_search(const uint8_t* Qc, const float* qs, int nq, const ui
 }
 
 }  // extern "C"
+
+#include "colbert_union.h"  // the candidate stage of the pruned ColBERT search: kernels and the entry points of include/dprhot_union.h

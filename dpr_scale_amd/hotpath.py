@@ -670,6 +670,37 @@ class HipKernels:
                                                             values.shape[1], int(chunk), _ptr(values), _ptr(indices), _ptr(ws), ws.numel(),
                                                             self._stream()), "dprhot_colbert_cand_search")
 
+    # -- the candidate lists themselves (csrc/colbert_union.h) ------------------------------------------
+    def colbert_union_workspace(self, nq, corpus_len, like):
+        """The membership state of `nq` queries over `corpus_len` passages: the cached workspace of the current stream (at least
+        dprhot_colbert_union_workspace_bytes), written by colbert_union_count and read by the colbert_union_fill behind it."""
+        return self._workspace(like.device, self._lib.colbert_union_workspace_bytes(nq, corpus_len))
+
+    def colbert_union_count(self, index, cids, qb, cand_off, totals, ws):
+        """Marks every query's candidate set in `ws` and writes cand_off int64 [nq + 1] and totals int64 [2] = (n_cand, the longest
+        list) (dprhot_colbert_union_count); cids int64 [nq, LQ, nprobe], qb bf16 [nq, LQ, dp]."""
+        self._require_gpu(cids, qb, index.cen_off, index.cen_doc, cand_off, totals, ws)
+        nq, LQ, dp = qb.shape
+        assert cids.dtype == torch.int64 and cids.is_contiguous() and cids.shape[:2] == (nq, LQ) and qb.dtype == _BF16 and qb.is_contiguous()
+        assert index.cen_off.dtype == torch.int64 and index.cen_doc.dtype == torch.int32
+        assert cand_off.dtype == torch.int64 and cand_off.shape == (nq + 1,) and totals.dtype == torch.int64 and totals.shape == (2,)
+        assert cand_off.is_contiguous() and totals.is_contiguous()
+        n_list = int(index.cen_doc.shape[0])
+        self._lib.check(self.lib.dprhot_colbert_union_count(_ptr(cids), _ptr(qb), dp, nq, LQ, int(cids.shape[2]), int(index.cen_off.shape[0]) - 1,
+                                                            _ptr(index.cen_off), _ptr(index.cen_doc) if n_list else None, n_list,
+                                                            index.corpus_len, _ptr(cand_off), _ptr(totals), _ptr(ws), ws.numel(), self._stream()),
+                        "dprhot_colbert_union_count")
+
+    def colbert_union_fill(self, index, cand_off, cand_doc, ws):
+        """Writes every query's sorted candidate list at cand_doc[cand_off[n] ..] from the state colbert_union_count left in `ws`; the
+        length of cand_doc int32 is a capacity, nothing behind it is written (dprhot_colbert_union_fill)."""
+        self._require_gpu(cand_off, cand_doc, ws)
+        assert cand_off.dtype == torch.int64 and cand_doc.dtype == torch.int32 and cand_off.is_contiguous() and cand_doc.is_contiguous()
+        n_cand = int(cand_doc.shape[0])
+        self._lib.check(self.lib.dprhot_colbert_union_fill(int(cand_off.shape[0]) - 1, index.corpus_len, _ptr(cand_off),
+                                                           _ptr(cand_doc) if n_cand else None, n_cand, _ptr(ws), ws.numel(), self._stream()),
+                        "dprhot_colbert_union_fill")
+
     # -- centroid interaction over candidate lists (csrc/colbert_cen.h; DESIGN.md section 12.3) --------------------------------
     def colbert_cen_workspace(self, nq, chunk, k, like):
         return self._chunk_workspace(self._lib.colbert_cen_workspace_bytes(nq, chunk), nq, k, like)
